@@ -7,21 +7,29 @@ status==1 and deliver the records to the host -- i.e. one iteration of the outer
 GenerateOpticalFlowDatabase (reference cpp/opticalflow.cc:237-316) without the SQLite insert
 (reported separately under "end_to_end").  Frames are resident in HBM before the timed region starts.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c1]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c1] [--dump-outputs DIR] [--full]
 
-What is timed: after at least 24 untimed frames (every ring slot used, clocks up; --warmup adds to that),
-EXACTLY K steps between barrier + synchronize on both sides.  A K-step region shorter than half a second
-(K = 20 at 1080p is 11 ms) is measured several times over consecutive stretches of the clip and the MEDIAN
-region is reported (`config.timed_regions`), so that a short driver run is not a cold one-off sample.
-The headline line is the 1080p configuration C2 (BASELINE.json configs[1]); the same JSON object carries
-the 4K configuration C3 under "c3" (the >= 30x target is quoted on 4K) unless --no-c3 -- with N > 1 that block is C4's
-per-rank workload and says so -- and, with one GPU, "c5": C5 end to end (analysis -> tracking -> refinement, pose error
-against the CPU reference of the tracking step) unless --no-c5.
+What is timed: after at least 24 untimed frames (every ring slot used, clocks up; --warmup adds to that) and 8 more,
+EXACTLY K steps between barrier + synchronize on both sides: ms_per_step = that region / K.  The headline line is the
+1080p configuration C2 (BASELINE.json configs[1]).
+
+A plain run does only that: set-up, warm-up, the K timed steps, the line.  --full adds everything else the line has
+carried since the first rounds, each block switched off by its --no-* option: a K-step region shorter than half a second
+(K = 20 at 1080p is 11 ms) is measured several times over consecutive stretches of the clip and the MEDIAN region is
+reported (`config.timed_regions`); the 4K configuration C3 under "c3" (the >= 30x target is quoted on 4K) unless --no-c3
+-- with N > 1 that block is C4's per-rank workload and says so --; the CPU baseline, the end-to-end product call, the
+per-class kernel breakdown, the rooflines with their own passes (below), the other arithmetic mode, the hard-content
+ratios, "c5": C5 end to end (analysis -> tracking -> refinement, pose error against the CPU reference of the tracking
+step) unless --no-c5, and "host"; with N > 1 the second stitch and the analysis-only rate of the same job.
+
+--dump-outputs DIR: after the timed steps, the records the timed path delivered for its last step (the last step of the
+first region with --full) -- keypoints and, per target frame, source indices, tracked positions and errors -- as
+DIR/<name>.npy in float32 / float64 (rank 0).  The clip, the frame ids and so these arrays depend only on the arguments.
 
 Arithmetic: the library's default mode, PC_ARITH_OPENCV_X86 (what the OpenCV build the reference links executes; DESIGN.md
-section 2), named in config.arith; "arith_modes" carries the same K steps in the canonical mode beside it.
+section 2), named in config.arith; with --full "arith_modes" carries the same K steps in the canonical mode beside it.
 
-roofline = the contract's HBM block of the dominant kernel (algorithmic bytes of an LK launch / its average duration,
+roofline (--full) = the contract's HBM block of the dominant kernel (algorithmic bytes of an LK launch / its average duration,
 against 8 TB/s); valu_roofline = what actually bounds that kernel (VALU issue), with both ceilings.  Counters
 (SQ_INSTS_VALU, FETCH_SIZE, WRITE_SIZE) come from short `rocprofv3 --pmc` passes of tools/lk_bench.py that this script
 runs itself after the timed regions ("counters_measured_in_run": true), or, without rocprofv3 / with --no-counters, from
@@ -458,9 +466,31 @@ def hard_content_block():
     return out
 
 
-def run_config(cfg, K, W, args, rank, world, dev, with_cpu, with_e2e, arith=None, light=False):
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, frame1, kps, flows):
+    """The records of one step as a caller of the analysis path receives them: frame1's keypoints and, per target frame,
+    the source keypoint indices (uint32, exact in float64), the tracked positions and the errors (float32).  Names:
+    keypoints.npy, flow_<m|p><skip>_{src_indices,xy,err}.npy (m8 = frame1 - 8).  Above DUMP_LIMIT_BYTES in all, every
+    n-th row of each array is kept (a fixed sample: the same rows from run to run)."""
+    arrays = {"frame1": np.array([frame1], np.float64), "keypoints": np.asarray(kps, np.float32)}
+    for t in sorted(flows):
+        idx, xy, err = flows[t]
+        tag = ("m%d" if t < frame1 else "p%d") % abs(t - frame1)
+        arrays[f"flow_{tag}_src_indices"] = np.asarray(idx).astype(np.float64)
+        arrays[f"flow_{tag}_xy"] = np.asarray(xy, np.float32)
+        arrays[f"flow_{tag}_err"] = np.asarray(err, np.float32)
+    stride = -(-sum(a.nbytes for a in arrays.values()) // DUMP_LIMIT_BYTES)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a[::stride] if name != "frame1" else a)
+
+
+def run_config(cfg, K, W, args, rank, world, dev, with_cpu, with_e2e, arith=None, light=False, dump_dir=None):
     """One configuration: returns the result object of this rank (rank 0's is printed).  light: the timed regions of the
-    headline path only (the other arithmetic mode beside the headline)."""
+    headline path only (the other arithmetic mode beside the headline).  Without --full: one K-step region, nothing but
+    the headline.  dump_dir: where the records of the last timed step go (dump_outputs)."""
     import torch
     import torch.distributed as dist
 
@@ -488,6 +518,7 @@ def run_config(cfg, K, W, args, rank, world, dev, with_cpu, with_e2e, arith=None
     gopt_kw, fopt_kw = {}, {"max_level": max_level}
     prewarm = max(MIN_PREWARM, W)
     dist_path = world > 1 or args.force_dist_path
+    extra = args.full and not light   # the blocks beside the headline (a plain run measures the headline alone)
 
     # ---- how many K-step regions: a short probe after the pre-warm gives the step time ----
     first_id = 1 + rank * RANK_ID_STRIDE
@@ -518,7 +549,7 @@ def run_config(cfg, K, W, args, rank, world, dev, with_cpu, with_e2e, arith=None
     barrier()
     est_step = (time.perf_counter() - t0) / 8
     nxt += 8
-    regions = int(min(40, max(1, -(-MIN_REGION_S // max(K * est_step, 1e-6)))))
+    regions = int(min(40, max(1, -(-MIN_REGION_S // max(K * est_step, 1e-6))))) if args.full else 1
     if dist.is_initialized():
         tt = torch.tensor([regions], dtype=torch.int64, device=dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
@@ -555,7 +586,7 @@ def run_config(cfg, K, W, args, rank, world, dev, with_cpu, with_e2e, arith=None
         first_mode = "peer" if isinstance(first, D.PeerLogStitch) else "rccl"
         stitches[first_mode] = prepare(first)
         modes = [first_mode]
-        if not light:
+        if extra:
             # A/B inside ONE job: the other stitch over the same log, and the N = 1 path on all ranks at once
             if first_mode == "peer":
                 stitches["rccl"] = prepare(D.ChunkedLogStitch(log, side_group=side))
@@ -574,6 +605,9 @@ def run_config(cfg, K, W, args, rank, world, dev, with_cpu, with_e2e, arith=None
             wd_tick(f"{cfg} {arith_name}: mode {mode}, region {region + 1} of {regions}")
             timed = range(nxt, nxt + K)
             nxt += K
+            # the records of the last step of the first timed region (with N > 1: of the N = 1 code path timed first): a frame
+            # id that depends on the arguments alone
+            dump_last = timed[-1] if dump_dir is not None and region == 0 and "records" not in last_step else None
             if stitch is not None:
                 an.an.set_device_log(log)   # resets the log (synchronises: outside the timed region)
                 stitch.reset()              # ... and the pieces gathered in the previous region
@@ -583,7 +617,7 @@ def run_config(cfg, K, W, args, rank, world, dev, with_cpu, with_e2e, arith=None
             finish_ms = 0.0
             t0 = time.perf_counter()
             if stitch is None:
-                an.run(timed, sink, copy=False)
+                an.run(timed, sink if dump_last is None else keep_last(dump_last), copy=False)
             else:
                 # the same loop as ClipAnalyzer.run, plus: whenever the last frame1 of a piece has been collected (its log
                 # bytes are complete), all-gather that piece -- the transfer runs beside the LK launches of the
@@ -592,10 +626,12 @@ def run_config(cfg, K, W, args, rank, world, dev, with_cpu, with_e2e, arith=None
                 log_end = {}
                 piece_start = 0
 
+                step_sink = sink if dump_last is None else keep_last(dump_last)
+
                 def collect_one():
                     nonlocal piece_start
                     r = an.an.collect(False)
-                    sink(*r)
+                    step_sink(*r)
                     done = r[0] - timed.start + 1
                     # the last frames of the region go one by one: what is still on the wire when the last job has been
                     # collected is one frame, not a piece
@@ -617,6 +653,9 @@ def run_config(cfg, K, W, args, rank, world, dev, with_cpu, with_e2e, arith=None
                 res["log_bytes"].append(int(an.an.device_log_used))
             barrier()
             dt = time.perf_counter() - t0
+            if dump_last is not None:
+                frame1, kps, flows = last_step.pop("views")
+                last_step["records"] = (frame1, kps.copy(), {t: tuple(a.copy() for a in v) for t, v in flows.items()})
             mine = [dt, finish_ms]
             if dist.is_initialized():
                 allr = [torch.zeros(2, dtype=torch.float64, device=dev) for _ in range(world)]
@@ -651,6 +690,17 @@ def run_config(cfg, K, W, args, rank, world, dev, with_cpu, with_e2e, arith=None
         res["mid"] = int(order[len(order) // 2])      # the median region
         return res
 
+    last_step = {}
+
+    def keep_last(fid):
+        """sink + frame fid's records as they are handed out: views of buffers that the next jobs reuse (collect(copy=False)),
+        copied by run_regions once the region is timed"""
+        def f(frame1, kps, detected, flows):
+            sink(frame1, kps, detected, flows)
+            if frame1 == fid:
+                last_step["views"] = (frame1, kps, flows)
+        return f
+
     kp_hint = max(n_kps)
     n_kps.clear()
     n_rows.clear()
@@ -680,6 +730,8 @@ def run_config(cfg, K, W, args, rank, world, dev, with_cpu, with_e2e, arith=None
             results[m] = run_regions(m)
     wd_tick(f"{cfg} {arith_name}: after the timed regions")
     gc.enable()
+    if dump_dir is not None:
+        dump_outputs(dump_dir, *last_step["records"])
     stitch_names = {m: st.name for m, st in stitches.items()}
     for st in stitches.values():
         st.close()
@@ -714,7 +766,7 @@ def run_config(cfg, K, W, args, rank, world, dev, with_cpu, with_e2e, arith=None
 
     # per-class kernel breakdown from a short extra pass over the same frames (not part of `value`)
     breakdown = None
-    if not args.no_breakdown and not light:
+    if not args.no_breakdown and extra:
         n_extra = min(K, 20)
         an = ClipAnalyzer(ctx, w, h, first_id, 1 << 30, source, hip.gftt_options(**gopt_kw), hip.flow_options(**fopt_kw), max_jobs=3)
         an.run(range(first_id + 8, first_id + 8 + 20), None)
@@ -731,7 +783,7 @@ def run_config(cfg, K, W, args, rank, world, dev, with_cpu, with_e2e, arith=None
     # the HIP events around a launch on its lane's stream bracket that launch alone.  This is the recipe of the committed
     # profiles/r0N_c{2,3}_rocprofv3_kernel_stats.csv (tools/collect_profiles.sh), whose average must agree.  Not part of `value`.
     lk_own_ms = None
-    if not light and rank == 0:
+    if extra and rank == 0:
         prev = os.environ.get("POLYCHASE_LK_LANES")
         os.environ["POLYCHASE_LK_LANES"] = "1"
         try:
@@ -845,13 +897,16 @@ def run_config(cfg, K, W, args, rank, world, dev, with_cpu, with_e2e, arith=None
                        "parallelism": f"frame-shard x{world}" if world > 1 else "single GPU",
                        "untimed_prewarm_steps": prewarm + 8, "timed_regions": len(head["region_s"]),
                        "region_ms_min_median_max": [min(head["region_s"]) * 1e3, dt * 1e3, max(head["region_s"]) * 1e3], **cfg_extra},
-            "roofline": roofline,
-            "valu_roofline": valu_roofline,
-            "path_roofline": {"algorithmic_bytes_per_frame": frame_bytes,
-                              "achieved_GBs": frame_bytes * (K / dt) / 1e9,
-                              "frac": frame_bytes * (K / dt) / 1e9 / HBM_PEAK_GBS},
-            "kernel_ms_per_frame": breakdown,
         }
+        if args.full:
+            out.update({
+                "roofline": roofline,
+                "valu_roofline": valu_roofline,
+                "path_roofline": {"algorithmic_bytes_per_frame": frame_bytes,
+                                  "achieved_GBs": frame_bytes * (K / dt) / 1e9,
+                                  "frac": frame_bytes * (K / dt) / 1e9 / HBM_PEAK_GBS},
+                "kernel_ms_per_frame": breakdown,
+            })
         if dist.is_initialized():
             out["collectives_backend"] = dist.get_backend()   # "nccl" = RCCL; "gloo" only under the SHARE_GPU testing aid
             out["world_size"] = dist.get_world_size()
@@ -863,7 +918,7 @@ def run_config(cfg, K, W, args, rank, world, dev, with_cpu, with_e2e, arith=None
                             "end-to-end product rate with the SQLite insert does not scale with N (one writer) -- see product_rate_with_insert")
         if modes[0] != "n1":
             out["config"]["stitch"] = stitch_names[modes[0]]
-            if not light:
+            if extra:
                 ab = {m: mode_summary(m) for m in modes if m != "n1"}
                 ab.update({m: {"unavailable": why} for m, why in unavailable.items()})
                 out["stitch_ab"] = ab
@@ -939,7 +994,16 @@ def main():
     ap.add_argument("--no-arith-modes", action="store_true", help="skip the second run of the K steps in the other arithmetic mode")
     ap.add_argument("--no-c5", action="store_true", help="skip the C5 end-to-end block (analysis -> tracking -> refinement)")
     ap.add_argument("--arith", default=None, choices=sorted(ARITH_FLAGS), help="arithmetic mode of the headline (default: the library's)")
+    ap.add_argument("--full", action="store_true",
+                    help="every block beside the headline (median of several regions, C3, CPU baseline, end to end, breakdown, "
+                         "rooflines, counters, the other arithmetic mode, hard content, C5, host); without it: the headline alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the records of the last timed step to DIR/<name>.npy (float32 / float64)")
     args = ap.parse_args()
+    if not args.full:
+        # a plain run: set-up, warm-up, the K timed steps of the headline, the line
+        args.no_c3 = args.no_cpu_baseline = args.no_end_to_end = args.no_breakdown = True
+        args.no_counters = args.no_arith_modes = args.no_c5 = True
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args.gpus))     # N ranks of this very command; rank 0 of them prints the JSON line
@@ -987,6 +1051,7 @@ def main():
         dist.init_process_group("nccl", init_method=f"tcp://127.0.0.1:{port}", rank=0, world_size=1, device_id=dev)
 
     K, W = args.steps, args.warmup
+    dump_dir = args.dump_outputs if rank == 0 else None
     single = world == 1 and not args.force_dist_path
     under_profiler = any(k.startswith("ROCPROF") for k in os.environ)   # a run under rocprofv3 starts no counter passes of its own
     if under_profiler:
@@ -994,7 +1059,7 @@ def main():
 
     def with_arith_modes(cfg, steps, **kw):
         """the configuration in the headline's arithmetic mode, then the same K steps in the other one (light: regions only)"""
-        o = run_config(cfg, steps, W, args, rank, world, dev, arith=args.arith, **kw)
+        o = run_config(cfg, steps, W, args, rank, world, dev, arith=args.arith, dump_dir=dump_dir if cfg == args.config else None, **kw)
         if not args.no_arith_modes:
             head_mode = LAST_ARITH
             other = "canonical" if head_mode != "canonical" else "opencv_x86"
@@ -1026,10 +1091,11 @@ def main():
         except Exception as e:
             out["c5"] = {"error": f"{type(e).__name__}: {e}"}
     if rank == 0:
-        try:
-            out["host"] = host_block()
-        except Exception as e:
-            out["host"] = {"error": f"{type(e).__name__}: {e}"}
+        if args.full:
+            try:
+                out["host"] = host_block()
+            except Exception as e:
+                out["host"] = {"error": f"{type(e).__name__}: {e}"}
         print(json.dumps(out), flush=True)
     _WD["printed"] = True
     wd_tick("shutting the process group down")

@@ -13,7 +13,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_forced_dist_path_runs_several_regions():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--force-dist-path", "--no-cpu-baseline", "--no-c3",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--force-dist-path", "--no-cpu-baseline", "--no-c3",
                         "--no-end-to-end", "--no-breakdown", "--config", "c1", "--steps", "16", "--warmup", "4"],
                        text=True, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -53,7 +53,7 @@ def test_two_ranks_on_one_gpu_over_gloo(stitch):
     if stitch == "peer-broken":
         env["POLYCHASE_TEST_BREAK_PEER_EXPORT"] = "1"
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
-                        "127.0.0.1", "--master-port", "29541", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "16",
+                        "127.0.0.1", "--master-port", "29541", os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "16",
                         "--warmup", "4", "--config", "c1", "--no-c3", "--no-breakdown"],
                        text=True, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900, env=env, cwd=ROOT)
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -93,7 +93,7 @@ def _check_multi_gpu_keys(out, n, peer, peer_wanted, arith_modes=True, top=True)
 
 
 def test_gpus_flag_launches_the_ranks_itself():
-    """`python3 bench.py --gpus 2 --steps 16 --warmup 4` -- the form the driver uses, no torchrun around it: bench.py
+    """`python3 bench.py --gpus 2 --steps 16 --warmup 4` -- the form the driver uses (here with --full), no torchrun around it: bench.py
     re-executes itself through torch.distributed.run with two ranks (on this one-GPU box both on GPU 0 over gloo, the
     SHARE_GPU testing aid) and exactly one JSON line with n_gpus == 2 comes out (round 2 parsed --gpus and ignored it)."""
     # (POLYCHASE_BENCH_STITCH=rccl: the chunked all-gather as the headline stitch -- gloo here -- and everything ONE N-GPU run must
@@ -101,7 +101,7 @@ def test_gpus_flag_launches_the_ranks_itself():
     env = dict(os.environ, POLYCHASE_BENCH_SHARE_GPU="1", POLYCHASE_BENCH_STITCH="rccl", HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "16", "--warmup", "4",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "16", "--warmup", "4",
                         "--config", "c1", "--no-c3", "--no-breakdown"],
                        text=True, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900, env=env, cwd=ROOT)
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -131,7 +131,7 @@ def test_four_ranks_push_on_three_streams():
     env = dict(os.environ, POLYCHASE_BENCH_SHARE_GPU="1", POLYCHASE_PEER_PUSH_STREAMS="3", HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--steps", "16", "--warmup", "4",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "4", "--steps", "16", "--warmup", "4",
                         "--config", "c1", "--no-c3", "--no-breakdown"],
                        text=True, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900, env=env, cwd=ROOT)
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -159,7 +159,7 @@ def test_c4_label_of_the_nested_4k_block_with_two_ranks():
     env = dict(os.environ, POLYCHASE_BENCH_SHARE_GPU="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "8", "--warmup", "2",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "8", "--warmup", "2",
                         "--no-breakdown", "--no-arith-modes"],
                        text=True, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=1500, env=env, cwd=ROOT)
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -177,10 +177,10 @@ def test_c4_label_of_the_nested_4k_block_with_two_ranks():
 
 
 def test_one_gpu_line_carries_roofline_counters_arith_modes_and_c5():
-    """the driver's own command on one GPU: roofline = the HBM block with counters measured in the run (rocprofv3 is on the
+    """the driver's own command on one GPU with --full: roofline = the HBM block with counters measured in the run (rocprofv3 is on the
     box), valu_roofline beside it with both ceilings, the other arithmetic mode, and the C5 end-to-end block"""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "POLYCHASE_ARITH")}
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "5", "--no-cpu-baseline",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "20", "--warmup", "5", "--no-cpu-baseline",
                         "--no-end-to-end"], text=True, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=1500, env=env, cwd=ROOT)
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert r.returncode == 0 and len(lines) == 1, (r.stdout[-2000:], r.stderr[-3000:])
@@ -205,3 +205,30 @@ def test_one_gpu_line_carries_roofline_counters_arith_modes_and_c5():
     pe = c5["pose_error_vs_cpu_reference"]
     assert pe["sampled_frames"] >= 10 and pe["rotation_rad_max"] <= 1e-4 and pe["translation_rel_max"] <= 1e-4
     assert c5["tracking_fps"] > 100 and c5["refinement_seconds"] < 10
+
+
+def test_plain_line_times_exactly_the_steps_and_dumps_the_same_outputs_twice(tmp_path):
+    """A plain run (no --full): one region of exactly --steps steps, the headline fields and nothing measured beside them;
+    --dump-outputs writes the last timed step's records, and a second run with the same arguments writes the same arrays."""
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "POLYCHASE_ARITH")}
+    runs = []
+    for i in range(2):
+        d = tmp_path / f"out{i}"
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "c1", "--steps", "12", "--warmup", "3",
+                            "--dump-outputs", str(d)], text=True, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600, env=env, cwd=ROOT)
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert r.returncode == 0 and len(lines) == 1, (r.stdout[-2000:], r.stderr[-3000:])
+        runs.append((json.loads(lines[0]), d))
+    out, d0 = runs[0]
+    assert out["metric"] == "optical-flow frames/sec" and out["unit"] == "frames/s" and out["higher_is_better"] is True
+    assert out["steps"] == 12 and out["config"]["timed_regions"] == 1 and out["dtype"]
+    assert abs(out["value"] - 1e3 / out["ms_per_step"]) < 1e-6 * out["value"]
+    assert not {"c3", "c5", "roofline", "arith_modes", "cpu_baseline", "end_to_end", "hard_content", "host"} & set(out)
+    import numpy as np
+    names = sorted(p.name for p in d0.iterdir())
+    assert "keypoints.npy" in names and any(n.endswith("_xy.npy") for n in names)
+    assert names == sorted(p.name for p in runs[1][1].iterdir())
+    for n in names:
+        a, b = np.load(d0 / n), np.load(runs[1][1] / n)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), n
+    assert len(np.load(d0 / "keypoints.npy")) > 0

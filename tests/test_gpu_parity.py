@@ -536,7 +536,7 @@ def _golden_case(ctx, G):
         x.close()
 
 
-def test_detection_slow_path_and_launch_hint(ctx):
+def test_detection_slow_path_and_launch_hint(ctx, tmp_path):
     """Detection keeps every count on the device and sizes its launches from the previous frames' candidate counts; a
     frame beyond those bounds is redone on the slow path (counts on the host, rocPRIM sort).  (a) The forced slow path
     (POLYCHASE_GFTT_SLOW_PATH, read once per process: a subprocess) gives the keypoints of the fast path; (b) a clip
@@ -571,9 +571,10 @@ def test_detection_slow_path_and_launch_hint(ctx):
     for f1 in range(1, 25):
         assert np.array_equal(got[f1], want[f1]), f1
     # (a) the slow path in a fresh process
-    np.save("/tmp/_pc_slow_in.npy", frames[18])
+    slow_in, slow_out = str(tmp_path / "slow_in.npy"), str(tmp_path / "slow_out.npy")
+    np.save(slow_in, frames[18])
     code = ("import sys, numpy as np; sys.path.insert(0, %r); from polychase_amd import hip; c = hip.Context(0); "
-            "f = hip.Frame(c, %d, %d); f.set_rgb(np.load('/tmp/_pc_slow_in.npy')); f.detect(); np.save('/tmp/_pc_slow_out.npy', f.keypoints())"
-            % (ROOT, w, h))
+            "f = hip.Frame(c, %d, %d); f.set_rgb(np.load(%r)); f.detect(); np.save(%r, f.keypoints())"
+            % (ROOT, w, h, slow_in, slow_out))
     subprocess.check_call([sys.executable, "-c", code], env=dict(os.environ, POLYCHASE_GFTT_SLOW_PATH="1"))
-    assert np.array_equal(np.load("/tmp/_pc_slow_out.npy"), want[19])
+    assert np.array_equal(np.load(slow_out), want[19])

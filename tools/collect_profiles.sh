@@ -17,10 +17,10 @@ export TMPDIR=/tmp
 cd /tmp
 if want bench; then
 for c in c2 c3; do
-  $T python "$ROOT/bench.py" --no-c3 --config $c 2>/dev/null | tail -1 > "$OUT/${TAG}_${c}_bench.json"
+  $T python "$ROOT/bench.py" --full --no-c3 --config $c 2>/dev/null | tail -1 > "$OUT/${TAG}_${c}_bench.json"
 done
-# the driver's own command line
-$T python "$ROOT/bench.py" --steps 20 --warmup 5 2>/dev/null | tail -1 > "$OUT/${TAG}_bench_driver_style.json"
+# the driver's own command line, with every block of the line (--full)
+$T python "$ROOT/bench.py" --full --steps 20 --warmup 5 2>/dev/null | tail -1 > "$OUT/${TAG}_bench_driver_style.json"
 fi
 # per-kernel durations (rocprofv3 --kernel-trace --stats) of the default bench command, and of the 4K configuration.
 # POLYCHASE_LK_LANES=1: all jobs on one lane, so no two LK launches overlap and a dispatch's duration is the launch's
@@ -30,7 +30,7 @@ fi
 # number the CSV's average must agree with.
 if want kstats; then
 for c in c2 c3; do
-  rm -rf /tmp/kstats && POLYCHASE_LK_LANES=1 $T rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kstats -- python "$ROOT/bench.py" --no-cpu-baseline --no-c3 --no-end-to-end --no-breakdown --config $c > /tmp/kstats.log 2>&1
+  rm -rf /tmp/kstats && POLYCHASE_LK_LANES=1 $T rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kstats -- python "$ROOT/bench.py" --full --no-cpu-baseline --no-c3 --no-end-to-end --no-breakdown --config $c > /tmp/kstats.log 2>&1
   grep "^{" /tmp/kstats.log | tail -1 > "$OUT/${TAG}_${c}_bench_under_rocprofv3.json"
   f=$(find /tmp/kstats -name "*kernel_stats.csv" | head -1)
   [ -n "$f" ] && cp "$f" "$OUT/${TAG}_${c}_rocprofv3_kernel_stats.csv"

@@ -4,13 +4,14 @@
 ROOT=$(cd "$(dirname "$0")/../.." && pwd)
 CFG=${1:-c2}; shift
 cd "$ROOT"
+OUT=${OUT:-$(mktemp -d)}   # the bench line of each library: $OUT/ab_<config>_<library>.json
 python tools/lk_variants/lk_variants.py run --config $CFG --reps 20 "$@" 2>&1 | cut -c1-260
 LIBS="default $@"
 [ $# -eq 0 ] && LIBS="default $(ls polychase_amd/lib/variants 2>/dev/null | sed 's/libpolychase_hip_//; s/.so//')"
 for l in $LIBS; do
   if [ $l = default ]; then unset POLYCHASE_HIP_LIB; else export POLYCHASE_HIP_LIB=$ROOT/polychase_amd/lib/variants/libpolychase_hip_$l.so; fi
-  python bench.py --no-cpu-baseline --no-c3 --no-end-to-end --config $CFG 2>/dev/null > gpurun_out/ab_${CFG}_$l.json
-  python - "$l" "gpurun_out/ab_${CFG}_$l.json" <<'PY'
+  python bench.py --full --no-cpu-baseline --no-c3 --no-end-to-end --config $CFG 2>/dev/null > "$OUT/ab_${CFG}_$l.json"
+  python - "$l" "$OUT/ab_${CFG}_$l.json" <<'PY'
 import json, sys
 try:
     d = json.load(open(sys.argv[2]))

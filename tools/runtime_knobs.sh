@@ -4,7 +4,7 @@
 #   tools/runtime_knobs.sh > gpurun_out/runtime_knobs.jsonl
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
 one() { # label ; env from the caller
-  b=$(timeout 300 python "$ROOT/bench.py" --no-cpu-baseline --no-end-to-end --no-breakdown --steps 20 --warmup 5 2>/dev/null | python -c "
+  b=$(timeout 300 python "$ROOT/bench.py" --full --no-cpu-baseline --no-end-to-end --no-breakdown --steps 20 --warmup 5 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.readlines()[-1]); print(round(d['value'],1), round(d['c3']['value'],1))")
   e=$(timeout 300 python "$ROOT/tools/e2e_bench.py" --config c2 --frames 300 2>/dev/null | grep "^{" | python -c "
