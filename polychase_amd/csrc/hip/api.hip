@@ -151,14 +151,26 @@ int validate_gftt(const pc_gftt_options* opt, int w, int h, pc::GfttGrid* g) {
     return PC_OK;
 }
 
+// the detector's default response (block 3, Sobel 3, min-eig): the tiled kernel
+static bool tiled_response(const pc_gftt_options& opt) {
+    // POLYCHASE_GFTT_GENERAL=1: the general kernels for the default options too (cross-check of the tiled kernel)
+    static const bool force_general = getenv("POLYCHASE_GFTT_GENERAL") && atoi(getenv("POLYCHASE_GFTT_GENERAL")) == 1;
+    return opt.block_size == 3 && opt.gradient_size == 3 && !opt.use_harris && !force_general;
+}
+
+// The fused chain for the detector's default (tiled response, table-driven suppression): NMS -> rank sort ->
+// suppression with its own ordered compaction -> visiting order, four launches after the response map where the
+// general chain has six (bucket scatter and compaction folded into their neighbours).
+static bool fused_detection(const pc_gftt_options& opt) {
+    return tiled_response(opt) && opt.min_distance >= 1 && !(opt.min_distance > pc::kSuppressMaxTableRadius);
+}
+
 // cornerMinEigenVal / cornerHarris of the frame (gftt.cc:31-36) + per-cell maxima: the tiled kernel for the detector's
 // default, the general pair of kernels otherwise (their covariance scratch is allocated on first use: not the addon's path)
 static int corner_response(pc_context* ctx, const pc_frame* f, DetectScratch& d, const pc::GfttGrid& grid, const pc_gftt_options& opt,
                            uint32_t* cell_max) {
     const int fma = ((ctx->arith & PC_ARITH_SOBEL_FMA) ? 1 : 0) | ((ctx->arith & PC_ARITH_SOBEL_ROW_FMA) ? 2 : 0);
-    // POLYCHASE_GFTT_GENERAL=1: the general kernels for the default options too (cross-check of the tiled kernel)
-    static const bool force_general = getenv("POLYCHASE_GFTT_GENERAL") && atoi(getenv("POLYCHASE_GFTT_GENERAL")) == 1;
-    if (opt.block_size == 3 && opt.gradient_size == 3 && !opt.use_harris && !force_general) {
+    if (tiled_response(opt)) {
         pc::launch_min_eig(f->levels[0], d.eig.p, grid, cell_max, fma, ctx->work);
         return PC_OK;
     }
@@ -175,7 +187,7 @@ static int corner_response(pc_context* ctx, const pc_frame* f, DetectScratch& d,
 // threshold + NMS -> candidates (gftt.cc:64-86).  The candidate count is copied to pinned memory; `ev` fires after.
 // every buffer a detection of a w x h frame needs (the analyzer calls this per slot at creation: an allocation inside the
 // running pipeline synchronises the device)
-int detect_reserve(pc_context* ctx, int w, int h, DetectScratch& d) {
+int detect_reserve(pc_context* ctx, int w, int h, DetectScratch& d, const pc_gftt_options* opt) {
     const size_t npx = (size_t)w * h;
     // 3x3 local maxima: at most one per 2x2 block unless the response has plateaus; more than that takes the slow path
     const size_t cand_cap = std::min(npx, npx / 4 + 65536);
@@ -183,6 +195,8 @@ int detect_reserve(pc_context* ctx, int w, int h, DetectScratch& d) {
     PC_HIP(d.cstate.ensure(npx + 16));
     PC_HIP(d.keys.ensure(cand_cap));
     PC_HIP(d.keys_bucketed.ensure(cand_cap));
+    // the NMS kernel's bucket slots (32 MiB whatever the frame size), only where the fused chain runs
+    if (opt && fused_detection(*opt)) PC_HIP(d.key_slots.ensure((size_t)pc::kSortBuckets * pc::kBucketSlots, /*exact=*/true));
     PC_HIP(d.keys_sorted.ensure(cand_cap));
     d.cand_cap = (uint32_t)std::min<size_t>(d.keys.cap, std::min(d.keys_bucketed.cap, d.keys_sorted.cap));
     d.ticket_stride = ticket_stride(w, h, d.cand_cap);
@@ -238,7 +252,7 @@ static int ensure_perm_capacity(pc_frame* f, int n) {
 int detect_enqueue(pc_context* ctx, pc_frame* f, const pc::GfttGrid& grid, const pc_gftt_options& opt, DetectScratch& d,
                    DevBuf<uint32_t>& hist, bool full_launch) {
     const int w = f->w, h = f->h;
-    int rc = detect_reserve(ctx, w, h, d);
+    int rc = detect_reserve(ctx, w, h, d, &opt);
     if (rc != PC_OK) return rc;
     if ((rc = upload_suppression_offsets(ctx, opt)) != PC_OK) return rc;
     if (f->kp_cap < 4096 && (rc = ensure_kp_capacity(f, 4096)) != PC_OK) return rc;
@@ -249,6 +263,11 @@ int detect_enqueue(pc_context* ctx, pc_frame* f, const pc::GfttGrid& grid, const
     if (!d.cleared) PC_HIP(hipMemsetAsync(cnt, 0, (size_t)d.counter_words * sizeof(uint32_t), ctx->work));
     uint32_t* const tickets = cnt + kTicketsAt;
     d.cleared = false;
+    // launches sized for the expected number of candidates (workgroups that find nothing to do still queue for a slot
+    // beside the LK wavefronts), the buffers for the capacity
+    const uint32_t n_launch = (ctx->cand_hint > 0 && !full_launch) ? std::min(ctx->cand_hint, d.cand_cap) : d.cand_cap;
+    const bool large_radius = opt.min_distance > pc::kSuppressMaxTableRadius;
+    const bool fused = fused_detection(opt);
     {
         ScopedTimer t(ctx, PC_K_MINEIG);
         if ((rc = corner_response(ctx, f, d, grid, opt, cnt + kCellMaxAt)) != PC_OK) return rc;
@@ -256,21 +275,26 @@ int detect_enqueue(pc_context* ctx, pc_frame* f, const pc::GfttGrid& grid, const
     {
         ScopedTimer t(ctx, PC_K_NMS);
         pc::launch_nms(d.eig.p, w, h, grid, cnt + kCellMaxAt, opt.quality_level, d.keys.p, d.cand_cap, cnt + kCntCand, d.cstate.p,
-                       cnt + kCntSortParams, cnt + kHistAt, tickets, d.bucket_offsets.p, hist.p, ctx->work);
+                       cnt + kCntSortParams, cnt + kHistAt, tickets, d.bucket_offsets.p, hist.p, ctx->work,
+                       fused ? d.key_slots.p : nullptr, fused ? d.per_block.p : nullptr, pc::suppress_num_blocks(n_launch));
     }
-    // launches sized for the expected number of candidates (workgroups that find nothing to do still queue for a slot
-    // beside the LK wavefronts), the buffers for the capacity
-    const uint32_t n_launch = (ctx->cand_hint > 0 && !full_launch) ? std::min(ctx->cand_hint, d.cand_cap) : d.cand_cap;
     {
         ScopedTimer t(ctx, PC_K_SORT);
-        pc::launch_bucket_sort(d.keys.p, d.cand_cap, n_launch, cnt + kCntCand, cnt + kCntSortParams, d.bucket_offsets.p,
-                               cnt + kCursorAt, d.keys_bucketed.p, d.keys_sorted.p, cnt + kCntOverflow, ctx->work);
+        if (fused)
+            pc::launch_bucket_sort_slots(d.key_slots.p, d.bucket_offsets.p, d.keys_sorted.p, cnt + kCntOverflow, ctx->work);
+        else
+            pc::launch_bucket_sort(d.keys.p, d.cand_cap, n_launch, cnt + kCntCand, cnt + kCntSortParams, d.bucket_offsets.p,
+                                   cnt + kCursorAt, d.keys_bucketed.p, d.keys_sorted.p, cnt + kCntOverflow, ctx->work);
     }
     // keypoints beyond the frame's buffer are not written; the count then exceeds the capacity and the slow path redoes it
     const uint32_t limit = opt.max_corners > 0 ? std::min<uint32_t>((uint32_t)opt.max_corners, (uint32_t)f->kp_cap) : (uint32_t)f->kp_cap;
-    const bool large_radius = opt.min_distance > pc::kSuppressMaxTableRadius;
     if (large_radius) PC_HIP(d.sup_grid.ensure((size_t)pc::suppress_large_grid_words(w, h, opt.min_distance)));
-    {
+    if (fused) {
+        ScopedTimer t(ctx, PC_K_SUPPRESS);
+        pc::launch_suppress_compact(d.keys_sorted.p, n_launch, cnt + kCntCand, w, h, d.eig.p, d.cstate.p, ctx->sup_offsets.p,
+                                    ctx->n_sup_offsets, ctx->sup_rows.p, ctx->sup_R, d.per_block.p, cnt + kCntStuck, limit, f->d_kps,
+                                    cnt + kCntKps, hist.p, cnt + kCntOverflow, tickets + d.ticket_stride, ctx->work);
+    } else {
         ScopedTimer t(ctx, PC_K_SUPPRESS);
         pc::launch_suppress_and_compact(d.keys_sorted.p, n_launch, cnt + kCntCand, w, h, d.eig.p, d.cstate.p, ctx->sup_offsets.p,
                                         ctx->n_sup_offsets, ctx->sup_rows.p, ctx->sup_R, opt.min_distance >= 1, d.per_block.p,

@@ -195,7 +195,7 @@ int pc_analyzer_create(pc_context* ctx, int width, int height, const pc_gftt_opt
             break;
         }
         s.frame->perm_cap = kp0;
-        if ((rc = detect_reserve(ctx, width, height, s.scratch)) != PC_OK) break;
+        if ((rc = detect_reserve(ctx, width, height, s.scratch, &a->gopt)) != PC_OK) break;
         if (s.scratch.bin_hist.ensure((size_t)pc::bin_num_tiles(width, height) + 1) != hipSuccess) {
             rc = fail(PC_E_HIP, "allocation failed");
             break;

@@ -63,7 +63,7 @@ int collect_timing(pc_context* c);
 int ensure_kp_capacity(pc_frame* f, int n);
 int validate_gftt(const pc_gftt_options* opt, int w, int h, pc::GfttGrid* g);
 // GoodFeaturesToTrack (internal.hpp DetectScratch): everything enqueued on the current work stream / the count on the host
-int detect_reserve(pc_context* ctx, int w, int h, DetectScratch& d);
+int detect_reserve(pc_context* ctx, int w, int h, DetectScratch& d, const pc_gftt_options* opt = nullptr);   // opt: also the fused chain's buffers
 int detect_enqueue(pc_context* ctx, pc_frame* f, const pc::GfttGrid& grid, const pc_gftt_options& opt, DetectScratch& d,
                    DevBuf<uint32_t>& hist, bool full_launch = false);
 // *redone (may be null): the frame took the slow path, its keypoints were written again just now

@@ -51,12 +51,12 @@ template <typename T>
 struct DevBuf {
     T* p = nullptr;
     size_t cap = 0;  // elements
-    hipError_t ensure(size_t n) {
+    hipError_t ensure(size_t n, bool exact = false) {   // exact: a buffer of fixed size, no room to grow
         if (n <= cap) return hipSuccess;
         if (p) (void)hipFree(p);
         p = nullptr;
         cap = 0;
-        size_t want = n + n / 2 + 64;   // generous: a reallocation synchronises the device
+        size_t want = exact ? n : n + n / 2 + 64;   // generous: a reallocation synchronises the device
         if (trace_allocations()) fprintf(stderr, "[polychase_hip] device buffer %zu -> %zu bytes\n", cap * sizeof(T), want * sizeof(T));
         hipError_t e = hipMalloc(reinterpret_cast<void**>(&p), want * sizeof(T));
         if (e == hipSuccess) cap = want;
@@ -110,6 +110,7 @@ using pc::fail;
 //   redoes the frame on the slow path (candidate count on the host, rocPRIM sort) if a fast-path bound was exceeded.
 struct DetectScratch {
     DevBuf<unsigned long long> keys, keys_bucketed, keys_sorted;
+    DevBuf<unsigned long long> key_slots;  // kSortBuckets x kBucketSlots bucket slots of the fused chain (launch_nms), when it runs
     DevBuf<float> eig;                     // min-eig map (K2 -> K3, K5)
     DevBuf<float> cov;                     // covariance planes of the general corner response (block_size != 3 / Harris), on demand
     DevBuf<double> box_rows;               // row sums of the box filter for large block sizes (kernels.hpp kBoxRowsFromBlock), on demand
@@ -130,6 +131,7 @@ struct DetectScratch {
     void release() {
         keys.release();
         keys_bucketed.release();
+        key_slots.release();
         keys_sorted.release();
         eig.release();
         cov.release();

@@ -67,10 +67,16 @@ bool launch_corner_response(const Level& l0, float* eig, float* cov, double* box
 // of the candidates for launch_bucket_sort (hist zeroed by the caller).  The workgroup that finishes last scans the
 // bucket counts into bucket_offsets[kSortBuckets + 1] (`ticket`: pc::last_workgroup_words(workgroups) zeroed words); bin_hist (may be null):
 // bin_num_tiles(w, h) words zeroed here for launch_suppress_and_compact.
+// With `slots` (kSortBuckets * kBucketSlots keys; the fused chain below) the keys go straight into their value bucket
+// instead of `keys`: bucket b's keys at slots[b * kBucketSlots ...], in arrival order (a bucket beyond kBucketSlots keys keeps
+// only valid keys and is flagged by the sort); `zero` / zero_words (may be null / 0): scratch zeroed in passing (the
+// look-back words of launch_suppress_compact).
 constexpr int kSortBuckets = 8192;
+constexpr int kBucketSlots = 512;
 void launch_nms(const float* eig, int w, int h, const GfttGrid& g, const uint32_t* cell_max, double quality_level,
                 unsigned long long* keys, uint32_t cap, uint32_t* counter, uint8_t* cstate, uint32_t* sort_params, uint32_t* hist,
-                uint32_t* ticket, uint32_t* bucket_offsets, uint32_t* bin_hist, hipStream_t s);
+                uint32_t* ticket, uint32_t* bucket_offsets, uint32_t* bin_hist, hipStream_t s,
+                unsigned long long* slots = nullptr, uint32_t* zero = nullptr, int zero_words = 0);
 // K4: the candidates in descending (value, address) order -> out; no count on the host (scan of the bucket counts,
 // scatter into bucket order via `scratch`, rank sort per bucket).  offsets[kSortBuckets + 1], cursor[kSortBuckets]
 // (zeroed by the caller); n_launch sizes the scatter's grid (it walks all candidates whatever the grid);
@@ -78,6 +84,9 @@ void launch_nms(const float* eig, int w, int h, const GfttGrid& g, const uint32_
 void launch_bucket_sort(const unsigned long long* keys, uint32_t cap, uint32_t n_launch, const uint32_t* counter, const uint32_t* sort_params,
                         const uint32_t* offsets, uint32_t* cursor, unsigned long long* scratch, unsigned long long* out,
                         uint32_t* overflow, hipStream_t s);
+// K4 of the fused chain: the rank sort alone, from the bucket slots launch_nms filled (`slots`, see there) -> out.
+void launch_bucket_sort_slots(const unsigned long long* slots, const uint32_t* offsets, unsigned long long* out, uint32_t* overflow,
+                              hipStream_t s);
 // offsets[n_offsets]: the (dx, dy) of the suppression neighbourhood; row_hw[2 R + 1]: the same set as half-widths per row
 // (row dy holds |dx| <= row_hw[dy + R], -1: none), the form the kernel walks.
 // K5: exact greedy min-distance suppression (gftt.cc:100-164) over the candidates SORTED by priority (keys descending),
@@ -96,6 +105,18 @@ void launch_suppress_and_compact(const unsigned long long* keys, uint32_t n_max,
                                  uint32_t* stuck, uint32_t max_corners, float2* xy, uint32_t* n_out, uint32_t* bin_hist,
                                  uint32_t* overflow, uint32_t* tickets, uint32_t ticket_stride, double large_min_distance, uint32_t* large_grid,
                                  hipStream_t s);
+// K5 of the fused chain (table-driven suppression, 1 <= min_distance <= kSuppressMaxTableRadius): suppression AND ordered
+// compaction in ONE launch.  A workgroup that has decided its candidates takes its first keypoint position from the
+// workgroups before it (decoupled look-back over `lookback`: suppress_num_blocks(n_max) words, zeroed before the launch --
+// launch_nms does that) and writes its keypoints and tile counts itself; its last workgroup writes *n_out and scans
+// bin_hist (bin_num_tiles(w, h) zeroed words) into the tiles' first positions of the LK visiting order.  `ticket`:
+// pc::last_workgroup_words(suppress_num_blocks(n_max)) zeroed words.  Otherwise what launch_suppress_and_compact computes --
+// except for a frame the fast path cannot hold (*overflow bit 1 from the sort, or *n_dev > n_max): nothing is decided,
+// *n_out = 0, and the caller redoes the frame on the slow path.
+void launch_suppress_compact(const unsigned long long* keys, uint32_t n_max, const uint32_t* n_dev, int w, int h, const float* eig,
+                             uint8_t* cstate, const int2* offsets, int n_offsets, const int* row_hw, int R, uint32_t* lookback,
+                             uint32_t* stuck, uint32_t max_corners, float2* xy, uint32_t* n_out, uint32_t* bin_hist,
+                             uint32_t* overflow, uint32_t* ticket, hipStream_t s);
 // min_distance above this: the neighbourhood table is not built; large_grid (suppress_large_grid_words words of scratch) and
 // large_min_distance select the one-wavefront greedy kernel (the reference's loop against a grid of accepted corners)
 constexpr double kSuppressMaxTableRadius = 64.0;

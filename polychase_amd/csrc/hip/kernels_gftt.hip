@@ -661,7 +661,9 @@ __global__ __launch_bounds__(256) void nms_kernel(const float* __restrict__ eig,
                                                   uint32_t* __restrict__ counter, uint8_t* __restrict__ cstate,
                                                   uint32_t* __restrict__ sort_params, uint32_t* __restrict__ hist,
                                                   uint32_t* __restrict__ ticket, uint32_t* __restrict__ bucket_offsets,
-                                                  uint32_t* __restrict__ bin_hist, int n_tiles, int hi_prio) {
+                                                  uint32_t* __restrict__ bin_hist, int n_tiles,
+                                                  unsigned long long* __restrict__ slots, uint32_t* __restrict__ zero, int zero_words,
+                                                  int hi_prio) {
     helper_priority(hi_prio);
     __shared__ float s_thr[kMaxGridCells];
     __shared__ uint32_t s_hi, s_lo;
@@ -695,6 +697,8 @@ __global__ __launch_bounds__(256) void nms_kernel(const float* __restrict__ eig,
         if (bin_hist)
             for (int i = tid; i < n_tiles; i += 256) bin_hist[i] = 0u;
     }
+    // scratch of a later launch of the chain, one word per lane at most (the look-back words of the suppression)
+    for (int i = (blockIdx.y * gridDim.x + blockIdx.x) * 256 + tid; i < zero_words; i += gridDim.x * gridDim.y * 256) zero[i] = 0u;
     const int r = tid >> 4, q = tid & 15;
     const int x = x0 + 4 * q;
     uint32_t flags = 0;                 // bit 4 * sub + i: pixel i of this lane's quad in tile `sub` is a candidate
@@ -811,8 +815,18 @@ __global__ __launch_bounds__(256) void nms_kernel(const float* __restrict__ eig,
                 if (flags & (1u << (4 * sub + i))) {
                     const uint32_t ord = float_to_ordered(vals[sub][i]);
                     if (pos < cap) {
-                        keys[pos] = ((unsigned long long)ord << 32) | (unsigned long long)(uint32_t)(y * w + x + i);
-                        atomicAdd(&hist[bucket_of(ord, range)], 1u);
+                        const unsigned long long key = ((unsigned long long)ord << 32) | (unsigned long long)(uint32_t)(y * w + x + i);
+                        const uint32_t b = bucket_of(ord, range);
+                        if (slots) {
+                            // straight into the bucket (no scatter launch); past its slots the bucket is flagged by the
+                            // sort, the frame is redone on the slow path and the suppression decides nothing (keys past
+                            // the slots are lost here); the last slot keeps a valid key for the launches behind it
+                            const uint32_t at = atomicAdd(&hist[b], 1u);
+                            slots[(size_t)b * kBucketSlots + min(at, (uint32_t)kBucketSlots - 1u)] = key;
+                        } else {
+                            keys[pos] = key;
+                            atomicAdd(&hist[b], 1u);
+                        }
                     }
                     pos++;
                 }
@@ -829,10 +843,12 @@ __global__ __launch_bounds__(256) void nms_kernel(const float* __restrict__ eig,
 
 void launch_nms(const float* eig, int w, int h, const GfttGrid& g, const uint32_t* cell_max, double quality_level,
                 unsigned long long* keys, uint32_t cap, uint32_t* counter, uint8_t* cstate, uint32_t* sort_params, uint32_t* hist,
-                uint32_t* ticket, uint32_t* bucket_offsets, uint32_t* bin_hist, hipStream_t s) {
+                uint32_t* ticket, uint32_t* bucket_offsets, uint32_t* bin_hist, hipStream_t s,
+                unsigned long long* slots, uint32_t* zero, int zero_words) {
     dim3 grid((w + TW - 1) / TW, (h + NMS_SUB * TH - 1) / (NMS_SUB * TH));
     hipLaunchKernelGGL(nms_kernel, grid, dim3(256), 0, s, eig, w, h, g, cell_max, quality_level, keys, cap, counter, cstate,
-                       sort_params, hist, ticket, bucket_offsets, bin_hist, bin_hist ? bin_num_tiles(w, h) : 0, helper_prio_arg());
+                       sort_params, hist, ticket, bucket_offsets, bin_hist, bin_hist ? bin_num_tiles(w, h) : 0, slots, zero,
+                       zero ? zero_words : 0, helper_prio_arg());
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -867,6 +883,9 @@ constexpr int kBucketsPerWave = 4;
 // per workgroup stays inside the helpers' LDS budget beside the LK wavefronts, which hold 120 of a CU's 160 KB).  (Rounds 2-4:
 // one wavefront per workgroup = 2048 workgroups per launch.)
 constexpr int kSortWaves = 4;
+// SLOTS: the keys come from the bucket slots the NMS kernel filled (launch_nms `slots`) instead of the scatter's bucket order
+static_assert(kBucketSlots == kBucketLds, "a bucket beyond its slots is a bucket beyond the fast path");
+template <bool SLOTS>
 __global__ __launch_bounds__(64 * kSortWaves) void bucket_sort_kernel(const unsigned long long* __restrict__ in, const uint32_t* __restrict__ offsets,
                                                          unsigned long long* __restrict__ out, uint32_t* __restrict__ overflow, int hi_prio) {
     helper_priority(hi_prio);
@@ -889,7 +908,15 @@ __global__ __launch_bounds__(64 * kSortWaves) void bucket_sort_kernel(const unsi
 #pragma unroll
         for (int q = 0; q < kBucketLds / 64; q++) {
             const uint32_t i = lane + 64 * q;
-            ld[q] = i < n4 ? in[lo + i] : 0ull;
+            size_t at = lo + i;
+            if (SLOTS) {
+                int k = 0;
+#pragma unroll
+                for (int kk = 1; kk < kBucketsPerWave; kk++)
+                    if (lo + i >= o[kk]) k = kk;
+                at = (size_t)(b0 + k) * kBucketSlots + (lo + i - o[k]);
+            }
+            ld[q] = i < n4 ? in[at] : 0ull;
         }
 #pragma unroll
         for (int q = 0; q < kBucketLds / 64; q++) {
@@ -927,16 +954,17 @@ __global__ __launch_bounds__(64 * kSortWaves) void bucket_sort_kernel(const unsi
     // more keys than the buffer holds at once: bucket by bucket
     for (int b = b0; b < b0 + kBucketsPerWave && b < kSortBuckets; b++) {
         const uint32_t base = offsets[b], n = offsets[b + 1] - base;
+        const unsigned long long* const src = SLOTS ? in + (size_t)b * kBucketSlots : in + base;
         if (n == 0) continue;
         if (n > (uint32_t)kBucketLds) {
             // beyond the fast path: the caller redoes the frame; the kernels queued behind this one still run, so they
             // must find VALID keys (copied unsorted), not whatever the buffer held before
             if (lane == 0) atomicOr(overflow, 1u);
-            for (uint32_t i = lane; i < n; i += 64) out[base + i] = in[base + i];
+            for (uint32_t i = lane; i < n; i += 64) out[base + i] = src[SLOTS ? min(i, (uint32_t)kBucketSlots - 1u) : i];
             continue;
         }
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");   // the previous bucket's readers are done (one wavefront: program order)
-        for (uint32_t i = lane; i < n; i += 64) s_keys[i] = in[base + i];
+        for (uint32_t i = lane; i < n; i += 64) s_keys[i] = src[i];
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
         for (uint32_t i = lane; i < n; i += 64) {
             const unsigned long long mine = s_keys[i];
@@ -953,8 +981,13 @@ void launch_bucket_sort(const unsigned long long* keys, uint32_t cap, uint32_t n
                         uint32_t* overflow, hipStream_t s) {
     const unsigned blocks = std::max(1u, std::min<unsigned>(1024u, (n_launch + 255u) / 256u));
     hipLaunchKernelGGL(bucket_scatter_kernel, dim3(blocks), dim3(256), 0, s, keys, cap, counter, sort_params, offsets, cursor, scratch, helper_prio_arg());
-    hipLaunchKernelGGL(bucket_sort_kernel, dim3((kSortBuckets / kBucketsPerWave + kSortWaves - 1) / kSortWaves), dim3(64 * kSortWaves), 0, s, scratch, offsets,
-                       out, overflow, helper_prio_arg());
+    hipLaunchKernelGGL(bucket_sort_kernel<false>, dim3((kSortBuckets / kBucketsPerWave + kSortWaves - 1) / kSortWaves), dim3(64 * kSortWaves), 0, s, scratch,
+                       offsets, out, overflow, helper_prio_arg());
+}
+void launch_bucket_sort_slots(const unsigned long long* slots, const uint32_t* offsets, unsigned long long* out, uint32_t* overflow,
+                              hipStream_t s) {
+    hipLaunchKernelGGL(bucket_sort_kernel<true>, dim3((kSortBuckets / kBucketsPerWave + kSortWaves - 1) / kSortWaves), dim3(64 * kSortWaves), 0, s, slots,
+                       offsets, out, overflow, helper_prio_arg());
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -998,15 +1031,11 @@ constexpr int SUP_BLOCK = 256;
 __device__ __forceinline__ uint8_t cs_load(const uint8_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ void cs_store(uint8_t* p, uint8_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
-__global__ __launch_bounds__(SUP_BLOCK) void suppress_sorted_kernel(const unsigned long long* __restrict__ keys, uint32_t n_max,
-                                                                    const uint32_t* __restrict__ n_dev, int w, int h,
-                                                                    const float* __restrict__ eig, uint8_t* cstate,
-                                                                    const int2* __restrict__ offsets, int n_offsets,
-                                                                    const int* __restrict__ row_hw, int R,
-                                                                    uint32_t* __restrict__ accepted_per_block,
-                                                                    uint32_t* __restrict__ stuck, AcceptedScan fin, int hi_prio) {
-    helper_priority(hi_prio);
-    const uint32_t n = n_dev ? min(*n_dev, n_max) : n_max;   // the launch covers n_max; workgroups past the count leave at once
+// The decision of lane i = candidate i of `keys` (n candidates): *idx = its pixel, the result = accepted.
+__device__ __forceinline__ bool suppress_decide(const unsigned long long* __restrict__ keys, uint32_t n, int w, int h,
+                                                const float* __restrict__ eig, uint8_t* cstate, const int2* __restrict__ offsets,
+                                                int n_offsets, const int* __restrict__ row_hw, int R, uint32_t* __restrict__ stuck,
+                                                uint32_t* idx_out) {
     const uint32_t i = blockIdx.x * SUP_BLOCK + threadIdx.x;
     const bool live = i < n;
     uint32_t my_val = 0, my_idx = 0;
@@ -1096,9 +1125,123 @@ __global__ __launch_bounds__(SUP_BLOCK) void suppress_sorted_kernel(const unsign
         }
         __builtin_amdgcn_s_sleep(1);
     }
+    *idx_out = my_idx;
+    return accepted;
+}
+
+__global__ __launch_bounds__(SUP_BLOCK) void suppress_sorted_kernel(const unsigned long long* __restrict__ keys, uint32_t n_max,
+                                                                    const uint32_t* __restrict__ n_dev, int w, int h,
+                                                                    const float* __restrict__ eig, uint8_t* cstate,
+                                                                    const int2* __restrict__ offsets, int n_offsets,
+                                                                    const int* __restrict__ row_hw, int R,
+                                                                    uint32_t* __restrict__ accepted_per_block,
+                                                                    uint32_t* __restrict__ stuck, AcceptedScan fin, int hi_prio) {
+    helper_priority(hi_prio);
+    const uint32_t n = n_dev ? min(*n_dev, n_max) : n_max;   // the launch covers n_max; workgroups past the count leave at once
+    uint32_t idx;
+    const bool accepted = suppress_decide(keys, n, w, h, eig, cstate, offsets, n_offsets, row_hw, R, stuck, &idx);
     const int c = __syncthreads_count(accepted);
     if (threadIdx.x == 0) publish(&accepted_per_block[blockIdx.x], (uint32_t)c);
     finish_accepted_scan(accepted_per_block, fin, n_max, n_dev);
+}
+
+// Decoupled look-back (Merrill and Garland's single-pass prefix scan) over one word per workgroup: 0 = not yet,
+// kLbAggregate | count = this workgroup's own count, kLbPrefix | count = the inclusive prefix.  Wavefront 0 of workgroup b
+// publishes its count, then reads up to 64 predecessors at a time -- summing back to the nearest inclusive prefix -- and
+// publishes its own.  It waits only on LOWER-numbered workgroups (the suppression's progress argument holds unchanged).
+constexpr uint32_t kLbAggregate = 1u << 30, kLbPrefix = 1u << 31, kLbCount = kLbAggregate - 1u;
+__device__ __forceinline__ uint32_t lookback_exclusive(uint32_t* lookback, uint32_t b, uint32_t c, uint32_t* __restrict__ stuck) {
+    const int lane = (int)(threadIdx.x & 63);
+    if (b == 0) {
+        if (lane == 0) publish(&lookback[0], kLbPrefix | c);
+        return 0u;
+    }
+    if (lane == 0) publish(&lookback[b], kLbAggregate | c);
+    uint32_t excl = 0;
+    int top = (int)b - 1;
+    for (uint32_t spin = 0;; spin++) {
+        const int j = top - lane;
+        const uint32_t v = j >= 0 ? __hip_atomic_load(&lookback[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : kLbPrefix;
+        const unsigned long long pre = __ballot((v & kLbPrefix) != 0u);
+        const int stop = pre ? __ffsll((long long)pre) - 1 : 63;              // lanes 0 .. stop are summed
+        const unsigned long long upto = stop == 63 ? ~0ull : ((2ull << stop) - 1ull);
+        if ((__ballot(v == 0u) & upto) == 0ull) {
+            uint32_t part = lane <= stop ? (v & kLbCount) : 0u;
+#pragma unroll
+            for (int d = 32; d >= 1; d >>= 1) part += __shfl_xor(part, d);
+            excl += part;
+            if (pre) break;
+            top -= 64;
+            continue;
+        }
+        if (spin > (1u << 22)) {          // tripwire, as in the suppression
+            if (lane == 0) atomicAdd(stuck, 1u);
+            break;
+        }
+        __builtin_amdgcn_s_sleep(1);
+    }
+    if (lane == 0) publish(&lookback[b], kLbPrefix | (excl + c));
+    return excl;
+}
+
+// Suppression + ordered compaction in one launch (launch_suppress_compact): the decisions as above, then the workgroup's
+// accepted candidates go to their keypoint positions at once -- the accepted_scatter_kernel's work without its launch.
+__global__ __launch_bounds__(SUP_BLOCK) void suppress_compact_kernel(const unsigned long long* __restrict__ keys, uint32_t n_max,
+                                                                     const uint32_t* __restrict__ n_dev, int w, int h,
+                                                                     const float* __restrict__ eig, uint8_t* cstate,
+                                                                     const int2* __restrict__ offsets, int n_offsets,
+                                                                     const int* __restrict__ row_hw, int R, uint32_t* lookback,
+                                                                     uint32_t* __restrict__ stuck, uint32_t max_corners,
+                                                                     float2* __restrict__ xy, uint32_t* __restrict__ n_out,
+                                                                     uint32_t* __restrict__ bin_hist, int tiles_x, int n_tiles,
+                                                                     uint32_t* __restrict__ overflow, uint32_t* __restrict__ ticket,
+                                                                     int hi_prio) {
+    helper_priority(hi_prio);
+    __shared__ uint32_t s_wave[SUP_BLOCK / 64];
+    __shared__ uint32_t s_excl;
+    // A frame the fast path cannot hold is redone on the slow path (detect_finish): a value bucket beyond its slots (the sort
+    // raised overflow bit 1; candidates past the slots own no lane, and a lane within min_distance of one would wait for it
+    // until the tripwire) or more candidates than this launch covers.  Then nothing is decided and no workgroup waits.
+    const uint32_t n_all = n_dev ? *n_dev : n_max;
+    const bool redo = (overflow && (*overflow & 1u) != 0u) || n_all > n_max;
+    const uint32_t n = redo ? 0u : n_all;
+    if (blockIdx.x * SUP_BLOCK < n) {    // workgroup-uniform; workgroups past the count only take their ticket
+        uint32_t idx;
+        const bool accepted = suppress_decide(keys, n, w, h, eig, cstate, offsets, n_offsets, row_hw, R, stuck, &idx);
+        const unsigned long long ballot = __ballot(accepted);
+        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+        if (lane == 0) s_wave[wave] = (uint32_t)__popcll(ballot);
+        __syncthreads();
+        if (wave == 0) {
+            uint32_t c = 0;
+#pragma unroll
+            for (int wv = 0; wv < SUP_BLOCK / 64; wv++) c += s_wave[wv];
+            const uint32_t excl = lookback_exclusive(lookback, blockIdx.x, c, stuck);
+            if (lane == 0) s_excl = excl;
+        }
+        __syncthreads();
+        if (accepted) {
+            uint32_t pos = s_excl + (uint32_t)__popcll(ballot & ((1ull << lane) - 1ull));
+            for (int wv = 0; wv < wave; wv++) pos += s_wave[wv];
+            if (!(max_corners > 0 && pos >= max_corners)) {
+                const uint32_t y = idx / (uint32_t)w, x = idx - y * (uint32_t)w;
+                xy[pos] = make_float2((float)x, (float)y);
+                if (bin_hist) atomicAdd(&bin_hist[min(n_tiles - 1, (int)((y >> 6) * tiles_x + (x >> 6)))], 1u);
+            }
+        }
+    }
+    // the last workgroup: the keypoint count (the inclusive prefix of the last workgroup with candidates, truncated to
+    // max_corners, gftt.cc:160-162) and the tiles' first positions in the LK visiting order
+    if (last_workgroup(ticket, gridDim.x)) {
+        __shared__ uint32_t s_scan[256];
+        if (threadIdx.x == 0) {
+            const uint32_t total =
+                n ? (__hip_atomic_load(&lookback[(n - 1u) / SUP_BLOCK], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & kLbCount) : 0u;
+            *n_out = (max_corners > 0 && total > max_corners) ? max_corners : total;
+            if (n_dev && overflow && *n_dev > n_max) atomicOr(overflow, 4u);
+        }
+        if (bin_hist) (void)scan_exclusive_256(bin_hist, bin_hist, n_tiles, s_scan);
+    }
 }
 
 // no suppression (min_distance < 1, gftt.cc:165-181): every candidate is accepted
@@ -1283,6 +1426,17 @@ void launch_suppress_and_compact(const unsigned long long* keys, uint32_t n_max,
     const int tiles_x = (w + 63) >> 6, n_tiles = bin_hist ? bin_num_tiles(w, h) : 0;
     hipLaunchKernelGGL(accepted_scatter_kernel, dim3(nb), dim3(SUP_BLOCK), 0, s, keys, n_max, n_dev, w, cstate, per_block, max_corners, xy,
                        bin_hist, tiles_x, n_tiles, tickets + ticket_stride, helper_prio_arg());
+}
+
+void launch_suppress_compact(const unsigned long long* keys, uint32_t n_max, const uint32_t* n_dev, int w, int h, const float* eig,
+                             uint8_t* cstate, const int2* offsets, int n_offsets, const int* row_hw, int R, uint32_t* lookback,
+                             uint32_t* stuck, uint32_t max_corners, float2* xy, uint32_t* n_out, uint32_t* bin_hist,
+                             uint32_t* overflow, uint32_t* ticket, hipStream_t s) {
+    const int nb = suppress_num_blocks(n_max);
+    if (nb == 0) return;
+    const int tiles_x = (w + 63) >> 6, n_tiles = bin_hist ? bin_num_tiles(w, h) : 0;
+    hipLaunchKernelGGL(suppress_compact_kernel, dim3(nb), dim3(SUP_BLOCK), 0, s, keys, n_max, n_dev, w, h, eig, cstate, offsets, n_offsets,
+                       row_hw, R, lookback, stuck, max_corners, xy, n_out, bin_hist, tiles_x, n_tiles, overflow, ticket, helper_prio_arg());
 }
 
 // ------------------------------------------------------------------------------------------------
