@@ -125,7 +125,7 @@ int pc_context_get_arithmetic(const pc_context* ctx);
 /* hipStream_t the context enqueues on (for callers that time with HIP events / torch streams). */
 void* pc_context_stream(pc_context* ctx);
 /* Timing of the context's kernels with HIP events on the stream each launch is enqueued on.  `class_mask` bit k
- * enables kernel class PC_K_k (0 = off, 0xff = all); enabled classes accumulate (launches, total ms).
+ * enables kernel class PC_K_k (0 = off, 0x1ff = all); enabled classes accumulate (launches, total ms).
  * Two event records per timed launch: keep the mask to the class of interest inside timed regions.
  * pc_analyzer overlaps the LK launches of consecutive frames (two job lanes), so `total_ms` -- the sum of the
  * launches' own start-to-end durations -- exceeds the time the class kept the GPU busy; pc_context_get_busy_time
@@ -161,7 +161,8 @@ int pc_debug_llt9(pc_context* ctx, const float* a81, const float* b9, float* l81
 #define PC_K_SUPPRESS 5
 #define PC_K_LK 6
 #define PC_K_COMPACT 7
-#define PC_K_COUNT 8
+#define PC_K_LK_FB 8   /* the backward launch of the forward-backward check (pc_lk_track_fb, pc_analyzer_set_fb_threshold) */
+#define PC_K_COUNT 9
 
 /* ---- frame: gray image + LK pyramid (+ Scharr derivative planes) + keypoints, resident in HBM ----
  * Replaces the per-frame state of cpp/opticalflow.cc:223-226 (frame1_gray, features, frame1_pyramid)
@@ -229,6 +230,25 @@ int pc_lk_track(pc_context* ctx, const pc_frame* frame1, const pc_frame* const* 
 int pc_lk_track_filtered(pc_context* ctx, const pc_frame* frame1, const pc_frame* const* targets,
                          int n_targets, const pc_flow_options* opt, uint32_t* src_indices,
                          float* tgt_xy, float* flow_err, int64_t* row_offset);
+
+/* ---- forward-backward consistency check (Kalal et al., 2010; not in the reference, off by default) ----
+ * fb_threshold (pixels at level 0) > 0: every row with forward status 1 is tracked back,
+ * calcOpticalFlowPyrLK(prev = target, next = frame1, pts = {q}, the same options, no initial flow), from the fp32 end point
+ * q the forward pass stored, in one additional launch (kernels_lk_fb.hip), bit for bit the oracle's pco_lk in the context's
+ * arithmetic mode.  With b the backward end point, p the keypoint, dx = b.x - p.x, dy = b.y - p.y, d2 = dx * dx + dy * dy
+ * (every operation rounded to fp32 on its own) and thr2 = (float)((double)fb_threshold * fb_threshold), the row's final status
+ * is 1 iff status_f == 1 && status_b == 1 && d2 <= thr2 (a NaN fails).  next_xy and err stay the forward pass's values.
+ * fb_threshold == 0: exactly pc_lk_track / pc_lk_track_filtered (nothing else is enqueued).  Negative, NaN or infinite:
+ * PC_E_INVALID.
+ * pc_lk_track_fb: `status` is the final status; back_xy [n_targets][N][2] and back_status [n_targets][N] (either may be NULL)
+ * receive b and status_b -- (0, 0) and 0 where the forward status is 0, and everywhere when fb_threshold == 0. */
+int pc_lk_track_fb(pc_context* ctx, const pc_frame* frame1, const pc_frame* const* targets, int n_targets,
+                   const pc_flow_options* opt, double fb_threshold, float* next_xy, uint8_t* status, float* err,
+                   float* back_xy, uint8_t* back_status);
+/* pc_lk_track_filtered on the final status. */
+int pc_lk_track_filtered_fb(pc_context* ctx, const pc_frame* frame1, const pc_frame* const* targets,
+                            int n_targets, const pc_flow_options* opt, double fb_threshold, uint32_t* src_indices,
+                            float* tgt_xy, float* flow_err, int64_t* row_offset);
 
 /* ---- analyzer: the pipelined per-clip engine behind GenerateOpticalFlowDatabase ----
  * (cpp/opticalflow.cc:209-321).  Holds a ring of resident frames (the reference's 17-frame
@@ -309,6 +329,10 @@ int pc_analyzer_redirect_device_log(pc_analyzer* a, void* d_log, size_t capacity
 /* enabled = 0: the records of the following jobs are not downloaded to pinned host memory (a rank whose records leave
  * through the device log only); pc_analyzer_collect then returns counts and NULL array pointers.  Default 1. */
 int pc_analyzer_set_host_records(pc_analyzer* a, int enabled);
+/* Forward-backward check (pc_lk_track_fb) for the jobs submitted from now on: the backward launch goes onto the job's lane
+ * between the LK launch and the compaction, so rejected rows are simply absent from the records.  0 (the default): off, the
+ * jobs enqueue what they always did.  Negative, NaN or infinite: PC_E_INVALID.  pc_analyzer_reset keeps the value. */
+int pc_analyzer_set_fb_threshold(pc_analyzer* a, double fb_threshold);
 /* Wait for the oldest submitted job.  Pointers stay valid until the job slot is reused, i.e. for
  * the next max_jobs-1 submits. */
 int pc_analyzer_collect(pc_analyzer* a, pc_frame_result* out);

@@ -141,6 +141,8 @@ def main(argv=None) -> int:
     ap.add_argument("--first-frame", type=int, default=1)
     ap.add_argument("--max-level", type=int, default=None)
     ap.add_argument("--database", required=True)
+    ap.add_argument("--fb-threshold", type=float, default=0.0, metavar="PX",
+                    help="forward-backward check: drop flow rows whose backward track misses the keypoint by more than PX pixels (0: off)")
     ap.add_argument("--piece-frames", type=int, default=16, help="frames per piece of the record log handed to rank 0")
     ap.add_argument("--gpus", type=int, default=0, help="launch this many ranks (one per GPU) of this command")
     args = ap.parse_args(argv)
@@ -189,6 +191,7 @@ def main(argv=None) -> int:
             return clip.frame_torch(t if t < clip.n else period - t)
     if args.max_level is not None:
         fopt.max_level = args.max_level
+    fopt.forward_backward_threshold = args.fb_threshold
     if int(os.environ.get("RANK", "0")) == 0 and os.path.exists(args.database):
         os.remove(args.database)
     if world > 1:

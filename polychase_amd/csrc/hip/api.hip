@@ -491,6 +491,48 @@ int run_lk(pc_context* ctx, const pc_frame* frame1, const pc_frame* const* targe
     return PC_OK;
 }
 
+int check_fb_threshold(double fb_threshold) {
+    if (!(fb_threshold >= 0.0) || std::isinf(fb_threshold)) return fail(PC_E_INVALID, "fb_threshold must be finite and >= 0");
+    return PC_OK;
+}
+
+int run_lk_fb(pc_context* ctx, const pc_frame* frame1, const pc_frame* const* targets, int n_targets, const pc_flow_options* opt,
+              double fb_threshold, int set, float2* back_xy, uint8_t* back_status) {
+    hipStream_t const lk_stream = ctx->lane_stream(set);
+    const int n = frame1->n_kps;
+    if (n == 0) return PC_OK;
+    pc::LKFBParams p;
+    std::memset(&p, 0, sizeof(p));
+    int max_level = std::min(opt->max_level, frame1->nlevels - 1);
+    for (int t = 0; t < n_targets; t++) max_level = std::min(max_level, targets[t]->nlevels - 1);
+    if (max_level < 0) max_level = 0;
+    for (int l = 0; l <= max_level; l++) {
+        p.f1[l] = frame1->levels[l];
+        for (int t = 0; t < n_targets; t++) {
+            p.timg[t][l] = targets[t]->levels[l].img;
+            p.tder[t][l] = targets[t]->levels[l].der;
+        }
+    }
+    p.n_targets = n_targets;
+    p.max_level = max_level;
+    p.n = n;
+    p.win = frame1->win;
+    p.pts = frame1->d_kps;
+    p.perm = frame1->perm_valid ? frame1->d_perm : ctx->lk_perm.p;   // the order run_lk visited the keypoints in
+    p.max_iters = std::min(std::max(opt->term_max_iters, 0), 100);
+    const double eps = std::min(std::max(opt->term_epsilon, 0.), 10.);
+    p.eps_sq = eps * eps;
+    p.min_eig_thr = (float)opt->min_eigen_threshold;
+    p.thr2 = (float)(fb_threshold * fb_threshold);
+    p.rec = ctx->lk_rec[set].p;
+    p.back_xy = back_xy;
+    p.back_status = back_status;
+    p.x86_order = (ctx->arith & PC_ARITH_LK_X86_ORDER) ? 1 : 0;
+    ScopedTimer tm(ctx, PC_K_LK_FB, lk_stream);
+    if (!pc::launch_lk_fb(p, lk_stream)) return fail(PC_E_INVALID, "unsupported window size %d", frame1->win);
+    return PC_OK;
+}
+
 }  // namespace pc_api
 
 using namespace pc_api;
@@ -726,6 +768,8 @@ void pc_context_destroy(pc_context* c) {
     c->lk_cxy.release();
     c->lk_ustatus.release();
     c->lk_cerr.release();
+    c->lk_back_xy.release();
+    c->lk_back_status.release();
     c->lk_cidx.release();
     for (auto& b : c->lk_block_counts) b.release();
     c->lk_perm.release();
@@ -1138,16 +1182,32 @@ int pc_frame_set_keypoints(pc_context* ctx, pc_frame* f, const float* xy, int n)
 }
 
 // ---------------------------------------------------------------------------------------------
-int pc_lk_track(pc_context* ctx, const pc_frame* frame1, const pc_frame* const* targets, int n_targets,
-                const pc_flow_options* opt, float* next_xy, uint8_t* status, float* err) {
+static int lk_track_impl(pc_context* ctx, const pc_frame* frame1, const pc_frame* const* targets, int n_targets,
+                         const pc_flow_options* opt, double fb_threshold, float* next_xy, uint8_t* status, float* err,
+                         float* back_xy, uint8_t* back_status) {
     int rc = check_lk_args(ctx, frame1, targets, n_targets, opt);
     if (rc != PC_OK) return rc;
     if (!next_xy || !status || !err) return fail(PC_E_INVALID, "null output");
+    if ((rc = check_fb_threshold(fb_threshold)) != PC_OK) return rc;
     PC_HIP(hipSetDevice(ctx->device));
     if (int jrc = join_prep(ctx)) return jrc;
     rc = run_lk(ctx, frame1, targets, n_targets, opt);
     if (rc != PC_OK) return rc;
     const size_t rows = (size_t)frame1->n_kps * n_targets;
+    const bool fb = fb_threshold > 0.0;
+    if (rows > 0 && !fb) {
+        if (back_xy) std::memset(back_xy, 0, rows * sizeof(float2));
+        if (back_status) std::memset(back_status, 0, rows);
+    }
+    if (rows > 0 && fb) {
+        if (back_xy) PC_HIP(ctx->lk_back_xy.ensure(rows));
+        if (back_status) PC_HIP(ctx->lk_back_status.ensure(rows));
+        rc = run_lk_fb(ctx, frame1, targets, n_targets, opt, fb_threshold, 0, back_xy ? ctx->lk_back_xy.p : nullptr,
+                       back_status ? ctx->lk_back_status.p : nullptr);
+        if (rc != PC_OK) return rc;
+        if (back_xy) PC_HIP(hipMemcpyAsync(back_xy, ctx->lk_back_xy.p, rows * sizeof(float2), hipMemcpyDeviceToHost, ctx->stream));
+        if (back_status) PC_HIP(hipMemcpyAsync(back_status, ctx->lk_back_status.p, rows, hipMemcpyDeviceToHost, ctx->stream));
+    }
     if (rows > 0) {
         // the kernel's records are in visiting order: bring them into the [target][n] arrays of the call
         PC_HIP(ctx->lk_cxy.ensure(rows));
@@ -1163,16 +1223,29 @@ int pc_lk_track(pc_context* ctx, const pc_frame* frame1, const pc_frame* const* 
     return PC_OK;
 }
 
-int pc_lk_track_filtered(pc_context* ctx, const pc_frame* frame1, const pc_frame* const* targets, int n_targets,
-                         const pc_flow_options* opt, uint32_t* src_indices, float* tgt_xy, float* flow_err,
-                         int64_t* row_offset) {
+int pc_lk_track(pc_context* ctx, const pc_frame* frame1, const pc_frame* const* targets, int n_targets,
+                const pc_flow_options* opt, float* next_xy, uint8_t* status, float* err) {
+    return lk_track_impl(ctx, frame1, targets, n_targets, opt, 0.0, next_xy, status, err, nullptr, nullptr);
+}
+
+int pc_lk_track_fb(pc_context* ctx, const pc_frame* frame1, const pc_frame* const* targets, int n_targets,
+                   const pc_flow_options* opt, double fb_threshold, float* next_xy, uint8_t* status, float* err,
+                   float* back_xy, uint8_t* back_status) {
+    return lk_track_impl(ctx, frame1, targets, n_targets, opt, fb_threshold, next_xy, status, err, back_xy, back_status);
+}
+
+static int lk_track_filtered_impl(pc_context* ctx, const pc_frame* frame1, const pc_frame* const* targets, int n_targets,
+                                  const pc_flow_options* opt, double fb_threshold, uint32_t* src_indices, float* tgt_xy,
+                                  float* flow_err, int64_t* row_offset) {
     int rc = check_lk_args(ctx, frame1, targets, n_targets, opt);
     if (rc != PC_OK) return rc;
     if (!row_offset) return fail(PC_E_INVALID, "null row_offset");
+    if ((rc = check_fb_threshold(fb_threshold)) != PC_OK) return rc;
     PC_HIP(hipSetDevice(ctx->device));
     if (int jrc = join_prep(ctx)) return jrc;
     rc = run_lk(ctx, frame1, targets, n_targets, opt);
     if (rc != PC_OK) return rc;
+    if (fb_threshold > 0.0 && (rc = run_lk_fb(ctx, frame1, targets, n_targets, opt, fb_threshold)) != PC_OK) return rc;
     const int n = frame1->n_kps;
     const size_t rows = (size_t)n * n_targets;
     PC_HIP(ctx->lk_cxy.ensure(rows + 1));
@@ -1200,6 +1273,18 @@ int pc_lk_track_filtered(pc_context* ctx, const pc_frame* frame1, const pc_frame
         PC_HIP(hipStreamSynchronize(ctx->stream));
     }
     return PC_OK;
+}
+
+int pc_lk_track_filtered(pc_context* ctx, const pc_frame* frame1, const pc_frame* const* targets, int n_targets,
+                         const pc_flow_options* opt, uint32_t* src_indices, float* tgt_xy, float* flow_err,
+                         int64_t* row_offset) {
+    return lk_track_filtered_impl(ctx, frame1, targets, n_targets, opt, 0.0, src_indices, tgt_xy, flow_err, row_offset);
+}
+
+int pc_lk_track_filtered_fb(pc_context* ctx, const pc_frame* frame1, const pc_frame* const* targets, int n_targets,
+                            const pc_flow_options* opt, double fb_threshold, uint32_t* src_indices, float* tgt_xy,
+                            float* flow_err, int64_t* row_offset) {
+    return lk_track_filtered_impl(ctx, frame1, targets, n_targets, opt, fb_threshold, src_indices, tgt_xy, flow_err, row_offset);
 }
 
 }  // extern "C"

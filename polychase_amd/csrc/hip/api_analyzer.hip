@@ -103,6 +103,7 @@ struct pc_analyzer {
     int32_t put_newest = 0, put_previous = 0;   // frame ids of the two most recent put_frame calls
     int puts = 0;
     bool host_records = true;            // download every job's records to pinned host memory
+    double fb_threshold = 0.0;           // forward-backward check of the jobs submitted from now on (0: off)
     uint8_t* d_log = nullptr;            // optional device-resident record log
     size_t log_cap = 0, log_used = 0;
     std::vector<PinBuf<long long>> log_hdr;  // one pinned header per job slot
@@ -469,6 +470,9 @@ int pc_analyzer_submit(pc_analyzer* a, int32_t frame1, const int32_t* targets, i
             a->gate_armed = true;
         }
         if ((rc = run_lk(ctx, s1->frame, tg, n_targets, &a->fopt, lane)) != PC_OK) return rc;
+        // forward-backward check: the backward launch follows on the same lane and rewrites the status of the records the
+        // compaction below filters; the gate is the forward launch's alone
+        if (a->fb_threshold > 0.0 && (rc = run_lk_fb(ctx, s1->frame, tg, n_targets, &a->fopt, a->fb_threshold, lane)) != PC_OK) return rc;
     }
     SlowSection ss_post("submit/post enqueue");
     uint8_t* const pack = ctx->lk_pack[lane].p;
@@ -545,6 +549,13 @@ int pc_analyzer_redirect_device_log(pc_analyzer* a, void* d_log, size_t capacity
 int pc_analyzer_set_host_records(pc_analyzer* a, int enabled) {
     if (!a) return fail(PC_E_INVALID, "null analyzer");
     a->host_records = enabled != 0;
+    return PC_OK;
+}
+
+int pc_analyzer_set_fb_threshold(pc_analyzer* a, double fb_threshold) {
+    if (!a) return fail(PC_E_INVALID, "null analyzer");
+    if (int rc = check_fb_threshold(fb_threshold)) return rc;
+    a->fb_threshold = fb_threshold;
     return PC_OK;
 }
 

@@ -77,6 +77,11 @@ int check_lk_args(pc_context* ctx, const pc_frame* frame1, const pc_frame* const
 // LK launch into output set `set` on job lane `set` (0: the context's main stream)
 int run_lk(pc_context* ctx, const pc_frame* frame1, const pc_frame* const* targets, int n_targets, const pc_flow_options* opt,
            int set = 0);
+// forward-backward check on the records run_lk has just left in set `set`, on the same lane (fb_threshold > 0);
+// back_xy / back_status: device arrays [n_targets][n] or null
+int check_fb_threshold(double fb_threshold);
+int run_lk_fb(pc_context* ctx, const pc_frame* frame1, const pc_frame* const* targets, int n_targets, const pc_flow_options* opt,
+              double fb_threshold, int set = 0, float2* back_xy = nullptr, uint8_t* back_status = nullptr);
 // gray (+ pyramid) of a frame from u8 gray / u8 RGB / float32 RGB(A) pixels, host or device, on the work stream
 // `clear` (may be null): clear_words words zeroed in front of the frame's kernels (by the level-0 kernel where there is one)
 int set_image(pc_context* ctx, pc_frame* f, const uint8_t* src, size_t row_pitch, int on_device, int channels, int elem_size = 1,

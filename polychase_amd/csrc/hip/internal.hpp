@@ -209,6 +209,8 @@ struct pc_context {
     DevBuf<float2> lk_cxy;
     DevBuf<uint8_t> lk_ustatus;            // pc_lk_track: unpacked status
     DevBuf<float> lk_cerr;
+    DevBuf<float2> lk_back_xy;             // pc_lk_track_fb: backward end points / status, [target][n]
+    DevBuf<uint8_t> lk_back_status;
     DevBuf<uint32_t> lk_cidx, lk_block_counts[2], lk_perm, lk_hist;
     DevBuf<uint32_t> lk_gate;              // LKParams::gate of the analyzer's launches (one word)
     PinBuf<uint32_t> lk_gate_timed_out;    // raised by a gate kernel that gave up (its stream shares a hardware queue with the other lane)

@@ -203,6 +203,32 @@ void launch_compact(const float4* rec, const uint32_t* slot_of, int n, int n_tar
 void launch_unpack_records(const float4* rec, const uint32_t* slot_of, int n, int n_targets, float2* xy, uint8_t* status,
                            float* err, hipStream_t s);
 int compact_num_blocks(int n);
+
+// ---- kernels_lk_fb.hip ----
+// Forward-backward check: every record of the forward launch with status 1 is tracked back from its target into frame1
+// (calcOpticalFlowPyrLK(prev = target, next = frame1, pts = {q})); rec[...].w becomes 0 unless the backward pass succeeds and
+// lands within sqrt(thr2) of the keypoint (d2 <= thr2 in separately rounded fp32 operations).  One launch per frame1 job.
+struct LKFBParams {
+    Level f1[kMaxLevels];                  // frame1 levels: the image the backward pass searches
+    const uint8_t* timg[8][kMaxLevels];    // [target][level] interior origins of the targets' u8 planes (the templates)
+    const int32_t* tder[8][kMaxLevels];    // ... and of their Scharr planes
+    int n_targets;
+    int max_level;                         // effective (min over pyramids), as in the forward launch
+    int n;                                 // keypoints
+    int win;                               // 3 .. PC_MAX_WINDOW
+    const float2* pts;                     // frame1's keypoints
+    const uint32_t* perm;                  // visiting order of the forward launch (slot -> keypoint) or null
+    int max_iters;
+    double eps_sq;
+    float min_eig_thr;
+    float thr2;                            // (float)((double)thr * (double)thr)
+    float4* rec;                           // the forward launch's records, LKParams::out_rec
+    float2* back_xy;                       // [target][n] in keypoint order, (0, 0) where status_f == 0; or null
+    uint8_t* back_status;                  // [target][n]; or null
+    int x86_order;                         // PC_ARITH_LK_X86_ORDER
+};
+// false: window or target count out of range (nothing enqueued)
+bool launch_lk_fb(const LKFBParams& p, hipStream_t s);
 // keypoints -> packed record buffer (both 16-byte aligned)
 void launch_copy_keypoints(const float2* src, float2* dst, int n, hipStream_t s);
 

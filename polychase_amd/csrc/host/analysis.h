@@ -35,6 +35,8 @@ struct OpticalFlowOptions {
     int term_max_iters = 30;
     double term_epsilon = 0.01;
     double min_eigen_threshold = 1e-4;
+    // not in the reference: forward-backward check (include/polychase_hip.h: pc_lk_track_fb), pixels at level 0; 0 = off
+    double forward_backward_threshold = 0.0;
 };
 
 // The clip: frames first_frame .. first_frame + num_frames - 1, all width x height.

@@ -420,6 +420,8 @@ static void RunAnalysis(const VideoInfo& video_info, FrameAccessorFunction frame
             ThrowHip("pc_analyzer_create");
     }
     Engine& eng = *engine;
+    // set on every run: a parked engine may have served another threshold (the cache is not keyed on it)
+    if (pc_analyzer_set_fb_threshold(eng.an, flow_options.forward_backward_threshold) != PC_OK) ThrowHip("pc_analyzer_set_fb_threshold");
     // the threads that feed this GPU stay on its NUMA node (numa_pin.h): this one for the duration of the call, the writer and its
     // page-write worker (started below / when the database opens its file) for their lives
     numa::ScopedPin near_gpu(eng.ctx, "analysis: calling thread");

@@ -357,7 +357,8 @@ PYBIND11_MODULE(polychase_core, m) {
         .def_readwrite("max_level", &OpticalFlowOptions::max_level)
         .def_readwrite("term_max_iters", &OpticalFlowOptions::term_max_iters)
         .def_readwrite("term_epsilon", &OpticalFlowOptions::term_epsilon)
-        .def_readwrite("min_eigen_threshold", &OpticalFlowOptions::min_eigen_threshold);
+        .def_readwrite("min_eigen_threshold", &OpticalFlowOptions::min_eigen_threshold)
+        .def_readwrite("forward_backward_threshold", &OpticalFlowOptions::forward_backward_threshold);   // not in the reference; 0 = off
 
     py::class_<OpticalFlowProgress>(m, "OpticalFlowProgress")
         .def_readonly("progress", &OpticalFlowProgress::progress)

@@ -14,7 +14,7 @@ import numpy as np
 from . import build as _build
 
 PC_MAX_TARGETS = 8
-KERNEL_CLASSES = ["gray", "pyramid", "min_eig", "nms", "sort", "suppress", "lk", "compact"]
+KERNEL_CLASSES = ["gray", "pyramid", "min_eig", "nms", "sort", "suppress", "lk", "compact", "lk_fb"]
 
 # every symbol include/polychase_hip.h declares (tests check they are all exported)
 SYMBOLS = [
@@ -28,12 +28,12 @@ SYMBOLS = [
     "pc_frame_num_levels", "pc_frame_level_size", "pc_frame_download_gray", "pc_frame_download_level",
     "pc_frame_download_deriv", "pc_frame_detect", "pc_frame_download_min_eig", "pc_frame_num_candidates",
     "pc_frame_num_keypoints", "pc_frame_download_keypoints", "pc_frame_set_keypoints",
-    "pc_lk_track", "pc_lk_track_filtered",
+    "pc_lk_track", "pc_lk_track_filtered", "pc_lk_track_fb", "pc_lk_track_filtered_fb",
     "pc_analyzer_create", "pc_analyzer_destroy", "pc_analyzer_reset", "pc_analyzer_put_frame", "pc_analyzer_put_frame_f32",
     "pc_analyzer_has_frame", "pc_analyzer_frame_ingested",
     "pc_analyzer_set_keypoints", "pc_analyzer_submit", "pc_analyzer_pending", "pc_analyzer_collect",
     "pc_analyzer_set_device_log", "pc_analyzer_device_log_used", "pc_analyzer_redirect_device_log",
-    "pc_analyzer_set_host_records",
+    "pc_analyzer_set_host_records", "pc_analyzer_set_fb_threshold",
     "pc_peer_buffer_alloc", "pc_peer_buffer_free", "pc_peer_buffer_export", "pc_peer_buffer_open", "pc_peer_buffer_close",
     "pc_peer_copy_async", "pc_peer_buffer_download",
     "pc_comm_unique_id", "pc_comm_create", "pc_comm_destroy", "pc_comm_world_size", "pc_comm_rank", "pc_comm_all_gather_log",
@@ -141,6 +141,8 @@ def load():
     L.pc_frame_set_keypoints.argtypes = [vp, vp, vp, C.c_int]
     L.pc_lk_track.argtypes = [vp, vp, C.POINTER(vp), C.c_int, C.POINTER(FlowOptions), vp, vp, vp]
     L.pc_lk_track_filtered.argtypes = [vp, vp, C.POINTER(vp), C.c_int, C.POINTER(FlowOptions), vp, vp, vp, vp]
+    L.pc_lk_track_fb.argtypes = [vp, vp, C.POINTER(vp), C.c_int, C.POINTER(FlowOptions), C.c_double, vp, vp, vp, vp, vp]
+    L.pc_lk_track_filtered_fb.argtypes = [vp, vp, C.POINTER(vp), C.c_int, C.POINTER(FlowOptions), C.c_double, vp, vp, vp, vp]
     L.pc_analyzer_create.argtypes = [vp, C.c_int, C.c_int, C.POINTER(GfttOptions), C.POINTER(FlowOptions), C.c_int,
                                      C.c_int, C.POINTER(vp)]
     L.pc_analyzer_destroy.argtypes = [vp]
@@ -158,6 +160,7 @@ def load():
     L.pc_analyzer_reset.argtypes = [vp]
     L.pc_analyzer_redirect_device_log.argtypes = [vp, vp, C.c_size_t]
     L.pc_analyzer_set_host_records.argtypes = [vp, C.c_int]
+    L.pc_analyzer_set_fb_threshold.argtypes = [vp, C.c_double]
     L.pc_peer_buffer_alloc.argtypes = [C.c_int, C.c_size_t, C.POINTER(vp)]
     L.pc_peer_buffer_free.argtypes = [C.c_int, vp]
     L.pc_peer_buffer_export.argtypes = [C.c_int, vp, C.c_char_p]
@@ -233,7 +236,7 @@ class Context:
     def enable_timing(self, classes=True):
         """classes: True = all, False = none, or an iterable of KERNEL_CLASSES names."""
         if classes is True:
-            mask = 0xFF
+            mask = (1 << len(KERNEL_CLASSES)) - 1
         elif not classes:
             mask = 0
         else:
@@ -424,6 +427,41 @@ def lk_track_filtered(ctx: Context, frame1: Frame, targets: list[Frame], opt: Fl
     return out
 
 
+def lk_track_fb(ctx: Context, frame1: Frame, targets: list[Frame], fb_threshold: float, opt: FlowOptions | None = None):
+    """lk_track with the forward-backward check (include/polychase_hip.h: pc_lk_track_fb): next_xy [T,N,2], final status
+    [T,N], err [T,N], back_xy [T,N,2], back_status [T,N].  fb_threshold == 0: lk_track and zeros."""
+    opt = opt or flow_options()
+    n, t = frame1.num_keypoints, len(targets)
+    xy = np.zeros((t, n, 2), np.float32)
+    st = np.zeros((t, n), np.uint8)
+    err = np.zeros((t, n), np.float32)
+    bxy = np.zeros((t, n, 2), np.float32)
+    bst = np.zeros((t, n), np.uint8)
+    arr = (C.c_void_p * t)(*[f._h for f in targets])
+    _check(load().pc_lk_track_fb(ctx._h, frame1._h, arr, t, C.byref(opt), float(fb_threshold), xy.ctypes.data, st.ctypes.data,
+                                 err.ctypes.data, bxy.ctypes.data, bst.ctypes.data))
+    return xy, st, err, bxy, bst
+
+
+def lk_track_filtered_fb(ctx: Context, frame1: Frame, targets: list[Frame], fb_threshold: float, opt: FlowOptions | None = None):
+    """lk_track_filtered on the final status of the forward-backward check (pc_lk_track_filtered_fb)."""
+    opt = opt or flow_options()
+    n, t = frame1.num_keypoints, len(targets)
+    rows = max(1, n * t)
+    idx = np.zeros(rows, np.uint32)
+    xy = np.zeros((rows, 2), np.float32)
+    err = np.zeros(rows, np.float32)
+    off = np.zeros(t + 1, np.int64)
+    arr = (C.c_void_p * t)(*[f._h for f in targets])
+    _check(load().pc_lk_track_filtered_fb(ctx._h, frame1._h, arr, t, C.byref(opt), float(fb_threshold), idx.ctypes.data,
+                                          xy.ctypes.data, err.ctypes.data, off.ctypes.data))
+    out = []
+    for k in range(t):
+        a, b = int(off[k]), int(off[k + 1])
+        out.append((idx[a:b].copy(), xy[a:b].copy(), err[a:b].copy()))
+    return out
+
+
 class Analyzer:
     """pc_analyzer: pipelined per-clip engine (ring of resident frames + asynchronous frame1 jobs)."""
 
@@ -501,6 +539,10 @@ class Analyzer:
 
     def set_host_records(self, enabled: bool):
         _check(load().pc_analyzer_set_host_records(self._h, 1 if enabled else 0))
+
+    def set_fb_threshold(self, fb_threshold: float):
+        """forward-backward check for the jobs submitted from now on; 0 = off (pc_analyzer_set_fb_threshold)"""
+        _check(load().pc_analyzer_set_fb_threshold(self._h, float(fb_threshold)))
 
     @property
     def device_log_used(self) -> int:

@@ -7,7 +7,11 @@ C ABI, then `pc_lk_track` is repeated: the LK class is timed with HIP events by 
 the average launch time and a checksum of the raw outputs (equal checksums <=> bit-identical
 results, the way kernel variants are compared: POLYCHASE_HIP_LIB selects the library).
 
-    python tools/lk_bench.py [--config c2|c3] [--reps 20]
+    python tools/lk_bench.py [--config c2|c3] [--reps 20] [--fb PX]
+
+--fb PX also times the forward-backward check (pc_lk_track_fb, threshold PX): the forward launch and the backward launch of
+the same call, and as the baseline the same backward work through the calls that existed before it -- per target,
+set_keypoints(q[status_f == 1]) on the target frame and pc_lk_track(target, [frame1]): eight launches.
 
 (Parity against the CPU oracle is the test suite's business: tests/test_gpu_parity.py, tests/test_fullsize_gpu.py.)
 """
@@ -28,6 +32,45 @@ CONFIGS = {"c1": (640, 480, 3), "c2": (1920, 1080, 3), "c3": (3840, 2160, 4)}
 SKIPS = (-8, -4, -2, -1, 1, 2, 4, 8)
 
 
+def fb_timing(ctx, hip, f1, targets, fopt, thr, reps, xy, st, err):
+    """forward + backward launch of pc_lk_track_fb against the eight-launch composition; the two must agree bit for bit.
+    Call it last: the composition leaves the forward end points as the target frames' keypoints."""
+    kps = f1.keypoints()
+    res = hip.lk_track_fb(ctx, f1, targets, thr, fopt)      # warm-up + the output that is compared
+    fxy, fst, ferr, bxy, bst = res
+    assert np.array_equal(fxy, xy) and np.array_equal(ferr, err), "the check changed a forward value"
+    ctx.enable_timing(["lk", "lk_fb"])
+    ctx.reset_timing()
+    for _ in range(reps):
+        hip.lk_track_fb(ctx, f1, targets, thr, fopt)
+    t = ctx.timing()
+    fwd_ms, back_ms = t["lk"][1] / max(1, t["lk"][0]), t["lk_fb"][1] / max(1, t["lk_fb"][0])
+    # the composition: every target's surviving end points become ITS keypoints, tracked into frame1 by the forward kernel
+    thr2 = np.float32(np.float64(thr) * np.float64(thr))
+    comp_ms, agree = 0.0, True
+    for rep in range(reps + 1):
+        ctx.reset_timing()
+        for k, tg in enumerate(targets):
+            idx = np.nonzero(st[k] == 1)[0]
+            tg.set_keypoints(xy[k][idx])
+            b, sb, _ = hip.lk_track(ctx, tg, [f1], fopt)
+            if rep == 0:      # warm-up round: compare
+                d = b[0] - kps[idx]
+                keep = (sb[0] == 1) & ((d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) <= thr2)
+                final = np.zeros(len(kps), np.uint8)
+                final[idx] = keep
+                agree = agree and np.array_equal(final, fst[k]) and np.array_equal(b[0], bxy[k][idx]) and np.array_equal(sb[0], bst[k][idx])
+        if rep > 0:
+            comp_ms += ctx.timing()["lk"][1]
+    ctx.enable_timing(False)
+    fwd_rows, kept_rows = int((st == 1).sum()), int((fst == 1).sum())
+    return {"threshold": thr, "forward_ms": fwd_ms, "backward_ms": back_ms, "forward_plus_backward_ms": fwd_ms + back_ms,
+            "backward_over_forward": back_ms / fwd_ms if fwd_ms else None, "composition_8_launches_ms": comp_ms / max(1, reps),
+            "composition_note": "LK launches only: the eight set_keypoints uploads and spatial-bin launches the composition also needs are outside the timer",
+            "composition_agrees_bitwise": bool(agree), "forward_rows": fwd_rows, "kept_rows": kept_rows,
+            "dropped_fraction": (fwd_rows - kept_rows) / max(1, fwd_rows), "status_b_zero": int(((st == 1) & (bst == 0)).sum())}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", default="c2", choices=sorted(CONFIGS))
@@ -37,6 +80,7 @@ def main():
     ap.add_argument("--arith", default="canonical", choices=["canonical", "lk_x86", "sobel_fma", "opencv_x86"])
     ap.add_argument("--max-iters", type=int, default=30, help="term_max_iters (30 = the reference's default); smaller values CUT the "
                     "stragglers' iterations off -- wrong results, but the time saved is the ceiling of what deferring them could gain")
+    ap.add_argument("--fb", type=float, default=0.0, metavar="PX", help="also time the forward-backward check at this threshold")
     args = ap.parse_args()
 
     import torch
@@ -91,6 +135,8 @@ def main():
            "sha256": hsh.hexdigest()[:16], "lib": os.environ.get("POLYCHASE_HIP_LIB", "default")}
     if x86_stats is not None:
         out["x86_stats_one_launch"] = x86_stats
+    if args.fb > 0:
+        out["fb"] = fb_timing(ctx, hip, f1, targets, fopt, args.fb, args.reps, xy, st, err)
     prof = ctx.lk_profile()
     if any(prof):
         names = ["i_stage", "i_eval", "pickup", "j_stage", "iterate", "err", "life", "waves", "wave_iters", "stagings"]
