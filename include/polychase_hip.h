@@ -209,6 +209,17 @@ int pc_frame_download_deriv(pc_context* ctx, const pc_frame* f, int level, int16
 /* GoodFeaturesToTrack (cpp/feature_detection/gftt.cc:14-192, called at opticalflow.cc:160) on the
  * frame's gray image; keypoints stay on the device, in acceptance order. */
 int pc_frame_detect(pc_context* ctx, pc_frame* f, const pc_gftt_options* opt);
+/* The `mask` argument of GoodFeaturesToTrack (gftt.cc:45-83) for the next pc_frame_detect of this frame: H rows of W bytes,
+ * row_pitch bytes apart, host memory (on_device = 0, copied before the call returns) or device memory (on_device = 1, read
+ * stream-ordered: keep it until the next synchronising call).  Any non-zero byte is "on".  As in the reference, the response
+ * map is that of the whole image; a grid cell's maxVal is the maximum over its pixels that are on (0.0 for a cell with none,
+ * what cv::minMaxLoc reports for an empty mask); the threshold maxVal * quality_level and the 3x3 dilation apply to every
+ * pixel, on or off; and only a pixel that is on can become a candidate.  This is NOT the unmasked result filtered by the mask:
+ * a pixel that is off still suppresses its neighbours in the dilation, and masking out a cell's brightest region lowers that
+ * cell's threshold.  Sort, greedy suppression, max_corners and the keypoint order are untouched.  The mask stays with the
+ * frame until it is replaced or cleared (mask = NULL); a frame that never had one allocates nothing and runs the unmasked
+ * kernels.  Null context or frame, or row_pitch < W: PC_E_INVALID. */
+int pc_frame_set_mask(pc_context* ctx, pc_frame* f, const uint8_t* mask, size_t row_pitch, int on_device);
 /* cv::cornerMinEigenVal map of the last pc_frame_detect (gftt.cc:35), w*h floats (tests). */
 int pc_frame_download_min_eig(pc_context* ctx, const pc_frame* f, float* out_eig);
 /* Number of local-maximum candidates of the last pc_frame_detect (gftt.cc:76-86) (tests). */
@@ -333,6 +344,15 @@ int pc_analyzer_set_host_records(pc_analyzer* a, int enabled);
  * between the LK launch and the compaction, so rejected rows are simply absent from the records.  0 (the default): off, the
  * jobs enqueue what they always did.  Negative, NaN or infinite: PC_E_INVALID.  pc_analyzer_reset keeps the value. */
 int pc_analyzer_set_fb_threshold(pc_analyzer* a, double fb_threshold);
+/* Detection mask (pc_frame_set_mask, gftt.cc:45-83) of the frames put FROM NOW ON with will_detect != 0; NULL: no mask (the
+ * default).  Detection is enqueued inside pc_analyzer_put_frame, so every slot of the ring keeps a mask plane of its own: a
+ * detection already enqueued keeps the mask it was enqueued with, and the mask may change from frame to frame.  A host mask
+ * (on_device = 0) is consumed before the call returns; a device mask (on_device = 1) is read when a frame is put and must
+ * stay alive and unmodified until pc_analyzer_frame_ingested says so for the frames put under it.  Frames put with
+ * will_detect = 0 (their keypoints come from the caller, or they are detected without a mask when submitted as frame1) never
+ * take the mask.  The planes are allocated by the first call with a mask; an analyzer that never sees one allocates nothing
+ * and enqueues what it always did.  pc_analyzer_reset clears the mask.  Null analyzer, or row_pitch < width: PC_E_INVALID. */
+int pc_analyzer_set_mask(pc_analyzer* a, const uint8_t* mask, size_t row_pitch, int on_device);
 /* Wait for the oldest submitted job.  Pointers stay valid until the job slot is reused, i.e. for
  * the next max_jobs-1 submits. */
 int pc_analyzer_collect(pc_analyzer* a, pc_frame_result* out);

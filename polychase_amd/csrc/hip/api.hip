@@ -165,20 +165,24 @@ static bool fused_detection(const pc_gftt_options& opt) {
     return tiled_response(opt) && opt.min_distance >= 1 && !(opt.min_distance > pc::kSuppressMaxTableRadius);
 }
 
+// the frame's detection mask plane, or null: the unmasked kernels
+static const uint8_t* frame_mask(const pc_frame* f) { return f->mask_on ? f->d_mask : nullptr; }
+
 // cornerMinEigenVal / cornerHarris of the frame (gftt.cc:31-36) + per-cell maxima: the tiled kernel for the detector's
 // default, the general pair of kernels otherwise (their covariance scratch is allocated on first use: not the addon's path)
 static int corner_response(pc_context* ctx, const pc_frame* f, DetectScratch& d, const pc::GfttGrid& grid, const pc_gftt_options& opt,
                            uint32_t* cell_max) {
     const int fma = ((ctx->arith & PC_ARITH_SOBEL_FMA) ? 1 : 0) | ((ctx->arith & PC_ARITH_SOBEL_ROW_FMA) ? 2 : 0);
+    const uint8_t* const mask = frame_mask(f);
     if (tiled_response(opt)) {
-        pc::launch_min_eig(f->levels[0], d.eig.p, grid, cell_max, fma, ctx->work);
+        pc::launch_min_eig(f->levels[0], d.eig.p, grid, cell_max, fma, ctx->work, mask);
         return PC_OK;
     }
     PC_HIP(d.cov.ensure((size_t)3 * f->w * f->h));
     const bool two_pass = opt.block_size >= pc::kBoxRowsFromBlock;
     if (two_pass) PC_HIP(d.box_rows.ensure((size_t)3 * f->w * f->h));
     if (!pc::launch_corner_response(f->levels[0], d.eig.p, d.cov.p, two_pass ? d.box_rows.p : nullptr, grid, cell_max, opt.block_size, opt.gradient_size, opt.use_harris != 0, opt.harris_k,
-                                    fma, ctx->work))
+                                    fma, ctx->work, mask))
         return fail(PC_E_INVALID, "gradient_size must be 3, 5, 7 (Sobel) or -1 (Scharr)");
     return PC_OK;
 }
@@ -276,7 +280,7 @@ int detect_enqueue(pc_context* ctx, pc_frame* f, const pc::GfttGrid& grid, const
         ScopedTimer t(ctx, PC_K_NMS);
         pc::launch_nms(d.eig.p, w, h, grid, cnt + kCellMaxAt, opt.quality_level, d.keys.p, d.cand_cap, cnt + kCntCand, d.cstate.p,
                        cnt + kCntSortParams, cnt + kHistAt, tickets, d.bucket_offsets.p, hist.p, ctx->work,
-                       fused ? d.key_slots.p : nullptr, fused ? d.per_block.p : nullptr, pc::suppress_num_blocks(n_launch));
+                       fused ? d.key_slots.p : nullptr, fused ? d.per_block.p : nullptr, pc::suppress_num_blocks(n_launch), frame_mask(f));
     }
     {
         ScopedTimer t(ctx, PC_K_SORT);
@@ -330,7 +334,7 @@ static int detect_slow_path(pc_context* ctx, pc_frame* f, const pc::GfttGrid& gr
     uint32_t* const tickets = cnt + kTicketsAt;
     if (int crc = corner_response(ctx, f, d, grid, opt, cnt + kCellMaxAt)) return crc;
     pc::launch_nms(d.eig.p, w, h, grid, cnt + kCellMaxAt, opt.quality_level, d.keys.p, npx, cnt + kCntCand, d.cstate.p,
-                   cnt + kCntSortParams, cnt + kHistAt, tickets, d.bucket_offsets.p, hist.p, ctx->work);
+                   cnt + kCntSortParams, cnt + kHistAt, tickets, d.bucket_offsets.p, hist.p, ctx->work, nullptr, nullptr, 0, frame_mask(f));
     PC_HIP(hipMemcpyAsync(d.h_counters.p, cnt, kHostCells * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->work));
     PC_HIP(hipStreamSynchronize(ctx->work));
     const uint32_t n_cand = std::min(d.h_counters.p[kCntCand], npx);
@@ -957,10 +961,27 @@ void pc_frame_destroy(pc_frame* f) {
     if (f->slab) (void)hipFree(f->slab);
     if (f->d_kps) (void)hipFree(f->d_kps);
     if (f->d_perm) (void)hipFree(f->d_perm);
+    if (f->d_mask) (void)hipFree(f->d_mask);
     delete f;
 }
 
 }  // extern "C"
+
+int pc_api::ensure_mask_plane(pc_frame* f) {
+    if (f->d_mask) return PC_OK;
+    // + 16: the kernels read a quad's bytes as one aligned dword, never past the plane, but a little room costs nothing
+    PC_HIP(hipMalloc(reinterpret_cast<void**>(&f->d_mask), (size_t)f->w * f->h + 16));
+    return PC_OK;
+}
+
+int pc_api::upload_mask(pc_frame* f, const uint8_t* mask, size_t row_pitch, int on_device, hipStream_t s) {
+    int rc = ensure_mask_plane(f);
+    if (rc != PC_OK) return rc;
+    PC_HIP(hipMemcpy2DAsync(f->d_mask, (size_t)f->w, mask, row_pitch, (size_t)f->w, (size_t)f->h,
+                            on_device == 1 ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
+    f->mask_on = true;
+    return PC_OK;
+}
 
 // channels: 1 / 3 = u8 gray / RGB; elem_size 4 = float32 RGB(A) with `channels` floats per pixel
 int pc_api::detect_counter_words(const DetectScratch& d) { return d.counter_words; }
@@ -1073,6 +1094,22 @@ int pc_frame_set_rgb_f32(pc_context* ctx, pc_frame* f, const float* rgb, size_t 
 }
 int pc_frame_set_gray(pc_context* ctx, pc_frame* f, const uint8_t* gray, size_t row_pitch, int on_device) {
     return set_image(ctx, f, gray, row_pitch, on_device, 1);
+}
+
+int pc_frame_set_mask(pc_context* ctx, pc_frame* f, const uint8_t* mask, size_t row_pitch, int on_device) {
+    if (!ctx || !f) return fail(PC_E_INVALID, "null argument");
+    if (f->ctx != ctx) return fail(PC_E_INVALID, "frame belongs to another context");
+    if (!mask) {
+        f->mask_on = false;   // the plane stays for the next mask
+        return PC_OK;
+    }
+    if (row_pitch < (size_t)f->w) return fail(PC_E_INVALID, "row_pitch %zu < %d", row_pitch, f->w);
+    PC_HIP(hipSetDevice(ctx->device));
+    if (int jrc = join_prep(ctx)) return jrc;
+    int rc = upload_mask(f, mask, row_pitch, on_device, ctx->stream);
+    if (rc != PC_OK) return rc;
+    if (on_device != 1) PC_HIP(hipStreamSynchronize(ctx->stream));   // the caller may reuse its host buffer
+    return PC_OK;
 }
 
 int pc_frame_num_levels(const pc_frame* f) { return f ? f->nlevels : 0; }

@@ -104,6 +104,17 @@ struct pc_analyzer {
     int puts = 0;
     bool host_records = true;            // download every job's records to pinned host memory
     double fb_threshold = 0.0;           // forward-backward check of the jobs submitted from now on (0: off)
+    // Detection mask of the frames put from now on with will_detect (pc_analyzer_set_mask).  The mask a detection reads is the
+    // plane of its own slot's frame, filled on the preparation stream when the frame is put: a detection already enqueued keeps
+    // the mask it was enqueued with.  A host mask is copied at once into one of kMaskGens pinned buffers, used in turn, so that
+    // the per-frame copies into the slots never wait for the host; mask_copied[g]: the latest copy out of buffer g is complete.
+    static constexpr int kMaskGens = 4;
+    int mask_kind = 0;                   // 0 none, 1 host (mask_host[mask_gen]), 2 device (mask_dev, mask_dev_pitch)
+    int mask_gen = 0;
+    PinBuf<uint8_t> mask_host[kMaskGens];
+    hipEvent_t mask_copied[kMaskGens] = {};
+    const uint8_t* mask_dev = nullptr;
+    size_t mask_dev_pitch = 0;
     uint8_t* d_log = nullptr;            // optional device-resident record log
     size_t log_cap = 0, log_used = 0;
     std::vector<PinBuf<long long>> log_hdr;  // one pinned header per job slot
@@ -259,6 +270,9 @@ void pc_analyzer_destroy(pc_analyzer* a) {
         s.scratch.release();
     }
     for (auto& hdr : a->log_hdr) hdr.release();
+    for (auto& m : a->mask_host) m.release();
+    for (hipEvent_t e : a->mask_copied)
+        if (e) (void)hipEventDestroy(e);
     for (auto& j : a->jobs) {
         j.h_pack.release();
         if (j.done) (void)hipEventDestroy(j.done);
@@ -282,7 +296,10 @@ int pc_analyzer_reset(pc_analyzer* a) {
         s.frame_id = 0;
         s.last_read[0] = s.last_read[1] = nullptr;
         s.scratch.cleared = false;
+        if (s.frame) s.frame->mask_on = false;
     }
+    a->mask_kind = 0;
+    a->mask_dev = nullptr;
     a->job_head = 0;
     a->d_log = nullptr;
     a->log_cap = a->log_used = 0;
@@ -320,6 +337,18 @@ static int analyzer_put(pc_analyzer* a, int32_t frame_id, const uint8_t* rgb, si
     if (rc != PC_OK) {
         s.valid = false;
         return rc;
+    }
+    // the mask of this frame's detection, into the slot's own plane, in front of img_ready: pc_analyzer_frame_ingested then
+    // also says that a device mask has been read
+    s.frame->mask_on = false;
+    if (will_detect && a->mask_kind == 1) {
+        // TODO(mask-upload): a static mask is uploaded again for every detected frame (w * h bytes; measured -16 % on a whole
+        // 1080p call for an all-on mask, DESIGN.md section 7 "Open follow-ups"): skip the copy when the slot's plane holds this mask
+        const int g = a->mask_gen;
+        if ((rc = upload_mask(s.frame, a->mask_host[g].p, (size_t)a->w, PC_FRAME_PINNED_HOST, a->ctx->prep_stream)) != PC_OK) return rc;
+        PC_HIP(hipEventRecord(a->mask_copied[g], a->ctx->prep_stream));
+    } else if (will_detect && a->mask_kind == 2) {
+        if ((rc = upload_mask(s.frame, a->mask_dev, a->mask_dev_pitch, 1, a->ctx->prep_stream)) != PC_OK) return rc;
     }
     PC_HIP(hipEventRecord(s.img_ready, a->ctx->prep_stream));
     s.frame_id = frame_id;
@@ -556,6 +585,35 @@ int pc_analyzer_set_fb_threshold(pc_analyzer* a, double fb_threshold) {
     if (!a) return fail(PC_E_INVALID, "null analyzer");
     if (int rc = check_fb_threshold(fb_threshold)) return rc;
     a->fb_threshold = fb_threshold;
+    return PC_OK;
+}
+
+int pc_analyzer_set_mask(pc_analyzer* a, const uint8_t* mask, size_t row_pitch, int on_device) {
+    if (!a) return fail(PC_E_INVALID, "null analyzer");
+    if (!mask) {
+        a->mask_kind = 0;
+        a->mask_dev = nullptr;
+        return PC_OK;
+    }
+    if (row_pitch < (size_t)a->w) return fail(PC_E_INVALID, "row_pitch %zu < %d", row_pitch, a->w);
+    PC_HIP(hipSetDevice(a->ctx->device));
+    // every slot's plane now: an allocation inside the running pipeline would stall it
+    for (auto& s : a->slots)
+        if (int rc = ensure_mask_plane(s.frame)) return rc;
+    if (on_device == 1) {
+        a->mask_kind = 2;
+        a->mask_dev = mask;
+        a->mask_dev_pitch = row_pitch;
+        return PC_OK;
+    }
+    const int g = (a->mask_gen + 1) % pc_analyzer::kMaskGens;
+    if (!a->mask_copied[g]) PC_HIP(hipEventCreateWithFlags(&a->mask_copied[g], hipEventDisableTiming));
+    else PC_HIP(hipEventSynchronize(a->mask_copied[g]));   // copies out of this buffer, kMaskGens masks ago
+    PC_HIP(a->mask_host[g].ensure((size_t)a->w * a->h));
+    for (int y = 0; y < a->h; y++) std::memcpy(a->mask_host[g].p + (size_t)y * a->w, mask + (size_t)y * row_pitch, (size_t)a->w);
+    a->mask_gen = g;
+    a->mask_kind = 1;
+    a->mask_dev = nullptr;
     return PC_OK;
 }
 

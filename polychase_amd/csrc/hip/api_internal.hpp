@@ -87,5 +87,9 @@ int run_lk_fb(pc_context* ctx, const pc_frame* frame1, const pc_frame* const* ta
 int set_image(pc_context* ctx, pc_frame* f, const uint8_t* src, size_t row_pitch, int on_device, int channels, int elem_size = 1,
               uint32_t* clear = nullptr, int clear_words = 0);
 int detect_counter_words(const DetectScratch& d);   // words of DetectScratch::counters a detection expects zeroed
+// detection mask of a frame: ensure_mask_plane allocates pc_frame::d_mask (w * h bytes, once); upload_mask copies `mask`
+// (host or device memory, rows row_pitch apart) into it on stream `s`, stream-ordered, and switches the mask on
+int ensure_mask_plane(pc_frame* f);
+int upload_mask(pc_frame* f, const uint8_t* mask, size_t row_pitch, int on_device, hipStream_t s);
 
 }  // namespace pc_api

@@ -247,5 +247,9 @@ struct pc_frame {
     uint32_t* d_perm = nullptr;   // LK visiting order of d_kps (spatial bins) [perm_cap], then its inverse [perm_cap]; valid iff perm_valid
     int perm_cap = 0;
     bool perm_valid = false;
+    // detection mask (gftt.cc:45-83): a packed w x h plane of bytes, allocated the first time the frame is given one;
+    // mask_on: the next detection of this frame honours it
+    uint8_t* d_mask = nullptr;
+    bool mask_on = false;
 };
 

@@ -54,13 +54,18 @@ constexpr int kMaxGridCells = 1024;   // grid_rows x grid_cols (not bound by the
 // cell_max must be zeroed first).
 // sobel_fma, bit 0: the column pass of Dx as ONE fused multiply-add (PC_ARITH_SOBEL_FMA: the AVX2 dispatch of OpenCV's filter);
 // bit 1: the row pass of Dy as a fused chain (PC_ARITH_SOBEL_ROW_FMA)
-void launch_min_eig(const Level& l0, float* eig, const GfttGrid& g, uint32_t* cell_max, int sobel_fma, hipStream_t s);
+// mask (here, launch_corner_response and launch_nms; may be null): the detection mask of GoodFeaturesToTrack (gftt.cc:45-83), a
+// packed w x h plane of bytes, 0 = off, anything else = on.  The response map does not depend on it; the per-cell maxima are
+// taken over the pixels that are on (a cell with none keeps the 0 it was cleared to, which launch_nms reads as maxVal = 0.0);
+// launch_nms thresholds and dilates every pixel and lets only pixels that are on become candidates.  Null: the unmasked
+// kernels, a separate instantiation without a trace of the mask.
+void launch_min_eig(const Level& l0, float* eig, const GfttGrid& g, uint32_t* cell_max, int sobel_fma, hipStream_t s, const uint8_t* mask = nullptr);
 // K2 for any block_size, any gradient_size (3, 5, 7: Sobel; -1: Scharr) and for cornerHarris (gftt.cc:31-36): two plain kernels;
 // cov = 3 * w * h floats of scratch; box_rows = 3 * w * h doubles (the box filter's row sums: block^2 -> 2 * block reads per pixel,
 // the same additions in the same order) or null.  false: not an aperture OpenCV has
 constexpr int kBoxRowsFromBlock = 12;   // callers pass box_rows from this block size on
 bool launch_corner_response(const Level& l0, float* eig, float* cov, double* box_rows, const GfttGrid& g, uint32_t* cell_max, int block_size, int gradient_size,
-                            bool harris, double harris_k, int sobel_fma, hipStream_t s);
+                            bool harris, double harris_k, int sobel_fma, hipStream_t s, const uint8_t* mask = nullptr);
 // K3: per-cell THRESH_TOZERO + 3x3 dilate + strict-interior local maxima -> 64-bit keys
 // (ordered(value) << 32 | y*w+x) appended to `keys` (capacity `cap`), count in *counter; cstate (w*h bytes): 1 at
 // candidates, 0 elsewhere, every pixel written; sort_params[2] / hist[kSortBuckets]: value range and per-bucket counts
@@ -76,7 +81,7 @@ constexpr int kBucketSlots = 512;
 void launch_nms(const float* eig, int w, int h, const GfttGrid& g, const uint32_t* cell_max, double quality_level,
                 unsigned long long* keys, uint32_t cap, uint32_t* counter, uint8_t* cstate, uint32_t* sort_params, uint32_t* hist,
                 uint32_t* ticket, uint32_t* bucket_offsets, uint32_t* bin_hist, hipStream_t s,
-                unsigned long long* slots = nullptr, uint32_t* zero = nullptr, int zero_words = 0);
+                unsigned long long* slots = nullptr, uint32_t* zero = nullptr, int zero_words = 0, const uint8_t* mask = nullptr);
 // K4: the candidates in descending (value, address) order -> out; no count on the host (scan of the bucket counts,
 // scatter into bucket order via `scratch`, rank sort per bucket).  offsets[kSortBuckets + 1], cursor[kSortBuckets]
 // (zeroed by the caller); n_launch sizes the scatter's grid (it walks all candidates whatever the grid);

@@ -59,10 +59,14 @@ __device__ __forceinline__ float smooth_row(float a, float b, float c, float f1,
 // (512 - 3 x 136): the detection then only ran in the gaps of the LK launches -- 4K pipeline 710 -> 537 frames/s, caught by
 // the round's last profile run.  tests/test_kernel_resources_cpu.py now holds every helper kernel to its budget.
 // SOBEL: bit 0 = the fused column pass of Dx (PC_ARITH_SOBEL_FMA), bit 1 = the fused row pass of Dy (PC_ARITH_SOBEL_ROW_FMA)
-template <int SOBEL>
+// MASKED (detection mask, gftt.cc:58-63): `mask` is a w x h plane of bytes; a pixel whose byte is 0 is left out of its cell's
+// maximum (minMaxLoc with a mask) -- its key becomes 0, which no atomicMax takes.  The map itself is the same with and without.
+// A compile-time variant: the unmasked instantiations never look at `mask`.
+template <int SOBEL, bool MASKED>
 __global__ __launch_bounds__(256) void min_eig_kernel(const uint8_t* __restrict__ img, int pitch, int w, int h,
                                                       float* __restrict__ eig, GfttGrid g,
-                                                      uint32_t* __restrict__ cell_max, float f1, float f0, int hi_prio) {
+                                                      uint32_t* __restrict__ cell_max, float f1, float f0, int hi_prio,
+                                                      const uint8_t* __restrict__ mask) {
     constexpr bool sobel_fma = (SOBEL & 1) != 0, row_fma = (SOBEL & 2) != 0;
     helper_priority(hi_prio);
     __shared__ __attribute__((aligned(16))) uint8_t s_gray[GH][G_PITCH];
@@ -171,7 +175,8 @@ __global__ __launch_bounds__(256) void min_eig_kernel(const uint8_t* __restrict_
             e = s_cxy[ty0 + k + 1][tx + PC_MINEIG_DUMP];
 #endif
             eig[(size_t)y * w + x] = e;
-            const uint32_t key = float_to_ordered(e);
+            uint32_t key = float_to_ordered(e);
+            if (MASKED && mask[(size_t)y * w + x] == 0) key = 0u;
             if (small_cells) {
                 const int cx = x / g.cell_w, cy = y / g.cell_h;
                 atomicMax(&cell_max[cy * g.cols + cx], key);
@@ -207,10 +212,12 @@ __global__ __launch_bounds__(256) void min_eig_kernel(const uint8_t* __restrict_
 constexpr int ME_R = 8;                       // output rows per lane
 constexpr int ME_TW = 64, ME_TH = 2 * ME_R;   // pixels per wavefront: 32 column pairs x 2 bands
 
-template <int SOBEL>
+// MASKED: as in the tiled kernel -- the keys of masked-out pixels become 0 before any of the three per-cell paths sees them.
+template <int SOBEL, bool MASKED>
 __global__ __launch_bounds__(256) void min_eig_fused_kernel(const uint8_t* __restrict__ img, int pitch, int w, int h,
                                                             float* __restrict__ eig, GfttGrid g,
-                                                            uint32_t* __restrict__ cell_max, float f1, float f0, int hi_prio) {
+                                                            uint32_t* __restrict__ cell_max, float f1, float f0, int hi_prio,
+                                                            const uint8_t* __restrict__ mask) {
     helper_priority(hi_prio);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     // the four wavefronts of a workgroup: 2 x 2 tiles
@@ -261,7 +268,18 @@ __global__ __launch_bounds__(256) void min_eig_fused_kernel(const uint8_t* __res
                 out[0] = e[0];
                 if (two) out[1] = e[1];
             }
-            const uint32_t k0 = float_to_ordered(e[0]), k1 = two ? float_to_ordered(e[1]) : 0u;
+            uint32_t k0 = float_to_ordered(e[0]), k1 = two ? float_to_ordered(e[1]) : 0u;
+            if (MASKED) {
+                const uint8_t* m = mask + (size_t)y * w + x;
+                if ((w & 1) == 0) {   // x is even: the pair is one aligned 16-bit load, and x + 1 < w
+                    const uint32_t mm = *reinterpret_cast<const uint16_t*>(m);
+                    if ((mm & 0xffu) == 0) k0 = 0u;
+                    if ((mm >> 8) == 0) k1 = 0u;
+                } else {
+                    if (m[0] == 0) k0 = 0u;
+                    if (two && m[1] == 0) k1 = 0u;
+                }
+            }
             if (one_cell) {
                 kmax[0] = max(kmax[0], max(k0, k1));
             } else if (four_regs) {
@@ -411,25 +429,34 @@ static int min_eig_variant() {
     return v;
 }
 
-template <int SOBEL>
-static void launch_min_eig_mode(const Level& l0, float* eig, const GfttGrid& g, uint32_t* cell_max, float f1, float f0, hipStream_t s) {
+template <int SOBEL, bool MASKED>
+static void launch_min_eig_masked(const Level& l0, float* eig, const GfttGrid& g, uint32_t* cell_max, float f1, float f0, hipStream_t s,
+                                  const uint8_t* mask) {
     if (min_eig_variant() == 0) {
         dim3 grid2((l0.w + 2 * ME_TW - 1) / (2 * ME_TW), (l0.h + 2 * ME_TH - 1) / (2 * ME_TH));
-        hipLaunchKernelGGL(min_eig_fused_kernel<SOBEL>, grid2, dim3(256), 0, s, l0.img, l0.pitch, l0.w, l0.h, eig, g, cell_max, f1, f0, helper_prio_arg());
+        hipLaunchKernelGGL((min_eig_fused_kernel<SOBEL, MASKED>), grid2, dim3(256), 0, s, l0.img, l0.pitch, l0.w, l0.h, eig, g, cell_max, f1, f0,
+                           helper_prio_arg(), mask);
         return;
     }
     dim3 grid((l0.w + TW - 1) / TW, (l0.h + TH - 1) / TH);
-    hipLaunchKernelGGL(min_eig_kernel<SOBEL>, grid, dim3(256), 0, s, l0.img, l0.pitch, l0.w, l0.h, eig, g, cell_max, f1, f0, helper_prio_arg());
+    hipLaunchKernelGGL((min_eig_kernel<SOBEL, MASKED>), grid, dim3(256), 0, s, l0.img, l0.pitch, l0.w, l0.h, eig, g, cell_max, f1, f0,
+                       helper_prio_arg(), mask);
 }
-void launch_min_eig(const Level& l0, float* eig, const GfttGrid& g, uint32_t* cell_max, int sobel_fma, hipStream_t s) {
+template <int SOBEL>
+static void launch_min_eig_mode(const Level& l0, float* eig, const GfttGrid& g, uint32_t* cell_max, float f1, float f0, hipStream_t s,
+                                const uint8_t* mask) {
+    if (mask) launch_min_eig_masked<SOBEL, true>(l0, eig, g, cell_max, f1, f0, s, mask);
+    else launch_min_eig_masked<SOBEL, false>(l0, eig, g, cell_max, f1, f0, s, nullptr);
+}
+void launch_min_eig(const Level& l0, float* eig, const GfttGrid& g, uint32_t* cell_max, int sobel_fma, hipStream_t s, const uint8_t* mask) {
     // scale = 1 / (2^(ksize-1) * block_size * 255), folded into the smoothing taps (see oracle)
     const double scale_d = 1.0 / (4.0 * 3.0 * 255.0);
     const float f1 = (float)(1.0 * scale_d), f0 = (float)(2.0 * scale_d);
     switch (sobel_fma & 3) {
-        case 0: launch_min_eig_mode<0>(l0, eig, g, cell_max, f1, f0, s); break;
-        case 1: launch_min_eig_mode<1>(l0, eig, g, cell_max, f1, f0, s); break;
-        case 2: launch_min_eig_mode<2>(l0, eig, g, cell_max, f1, f0, s); break;
-        default: launch_min_eig_mode<3>(l0, eig, g, cell_max, f1, f0, s); break;
+        case 0: launch_min_eig_mode<0>(l0, eig, g, cell_max, f1, f0, s, mask); break;
+        case 1: launch_min_eig_mode<1>(l0, eig, g, cell_max, f1, f0, s, mask); break;
+        case 2: launch_min_eig_mode<2>(l0, eig, g, cell_max, f1, f0, s, mask); break;
+        default: launch_min_eig_mode<3>(l0, eig, g, cell_max, f1, f0, s, mask); break;
     }
 }
 
@@ -543,8 +570,10 @@ __global__ __launch_bounds__(256) void box_rows_kernel(const float* __restrict__
     rows[2 * n + row + x] = ryy;
 }
 
+template <bool MASKED>   // the detection mask, as in min_eig_kernel
 __global__ __launch_bounds__(256) void box_response_kernel(const float* __restrict__ cov, const double* __restrict__ rows, int w, int h, int block, int harris, double harris_k,
-                                                           float* __restrict__ eig, GfttGrid g, uint32_t* __restrict__ cell_max, int hi_prio) {
+                                                           float* __restrict__ eig, GfttGrid g, uint32_t* __restrict__ cell_max, int hi_prio,
+                                                           const uint8_t* __restrict__ mask) {
     helper_priority(hi_prio);
     const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
     if (x >= w || y >= h) return;
@@ -597,6 +626,7 @@ __global__ __launch_bounds__(256) void box_response_kernel(const float* __restri
     eig[(size_t)y * w + x] = e;
     // per-cell maximum: one atomic per wavefront when its 64 pixels of a row lie in one cell
     uint32_t key = float_to_ordered(e);
+    if (MASKED && mask[(size_t)y * w + x] == 0) key = 0u;
     const int cell = (y / g.cell_h) * g.cols + x / g.cell_w;
     const int cell0 = __builtin_amdgcn_readfirstlane(cell);
     if (__all(cell == cell0)) {
@@ -609,7 +639,7 @@ __global__ __launch_bounds__(256) void box_response_kernel(const float* __restri
 }
 
 bool launch_corner_response(const Level& l0, float* eig, float* cov, double* box_rows, const GfttGrid& g, uint32_t* cell_max, int block_size, int gradient_size,
-                            bool harris, double harris_k, int sobel_fma, hipStream_t s) {
+                            bool harris, double harris_k, int sobel_fma, hipStream_t s, const uint8_t* mask) {
     SobelTaps T;
     int taps = 0;
     if (!make_sobel_taps(gradient_size, block_size, &T, &taps)) return false;
@@ -621,8 +651,13 @@ bool launch_corner_response(const Level& l0, float* eig, float* cov, double* box
     else
         hipLaunchKernelGGL(cov_kernel<7>, grid, dim3(256), 0, s, l0.img, l0.pitch, l0.w, l0.h, cov, T, sobel_fma, helper_prio_arg());
     if (box_rows) hipLaunchKernelGGL(box_rows_kernel, grid, dim3(256), 0, s, cov, l0.w, l0.h, block_size, box_rows, helper_prio_arg());
-    hipLaunchKernelGGL(box_response_kernel, grid, dim3(256), 0, s, cov, (const double*)box_rows, l0.w, l0.h, block_size, harris ? ((sobel_fma & 1) ? 2 : 1) : 0, harris_k, eig, g, cell_max,
-                       helper_prio_arg());
+    const int harris_mode = harris ? ((sobel_fma & 1) ? 2 : 1) : 0;
+    if (mask)
+        hipLaunchKernelGGL(box_response_kernel<true>, grid, dim3(256), 0, s, cov, (const double*)box_rows, l0.w, l0.h, block_size, harris_mode, harris_k, eig, g, cell_max,
+                           helper_prio_arg(), mask);
+    else
+        hipLaunchKernelGGL(box_response_kernel<false>, grid, dim3(256), 0, s, cov, (const double*)box_rows, l0.w, l0.h, block_size, harris_mode, harris_k, eig, g, cell_max,
+                           helper_prio_arg(), (const uint8_t*)nullptr);
     return true;
 }
 
@@ -655,6 +690,13 @@ __device__ __forceinline__ uint32_t bucket_of(uint32_t ord, const SortRange& r) 
     return b < (uint32_t)kSortBuckets ? b : (uint32_t)kSortBuckets - 1u;
 }
 
+// MASKED (detection mask, gftt.cc:45-83): a cell whose pixels are all masked out has no maximum (cell_max still 0) and takes
+// maxVal = 0.0, what cv::minMaxLoc leaves for an empty mask; thresholding and the dilation see every pixel; a pixel whose mask
+// byte is 0 is no candidate (gftt.cc:83) -- its bit is cleared before the state byte, the histogram and the keys are written,
+// so every later launch sees the gated set only.  The sort range holds: a candidate is an unmasked pixel of its cell, hence not
+// above that cell's (masked) maximum, hence not above s_hi; a fully masked cell brings threshold 0 into s_lo, which can only
+// widen the range (a coarser `shift`; a bucket that overflows for it takes the slow path like any other).
+template <bool MASKED>
 __global__ __launch_bounds__(256) void nms_kernel(const float* __restrict__ eig, int w, int h, GfttGrid g,
                                                   const uint32_t* __restrict__ cell_max, double quality_level,
                                                   unsigned long long* __restrict__ keys, uint32_t cap,
@@ -663,7 +705,7 @@ __global__ __launch_bounds__(256) void nms_kernel(const float* __restrict__ eig,
                                                   uint32_t* __restrict__ ticket, uint32_t* __restrict__ bucket_offsets,
                                                   uint32_t* __restrict__ bin_hist, int n_tiles,
                                                   unsigned long long* __restrict__ slots, uint32_t* __restrict__ zero, int zero_words,
-                                                  int hi_prio) {
+                                                  int hi_prio, const uint8_t* __restrict__ mask) {
     helper_priority(hi_prio);
     __shared__ float s_thr[kMaxGridCells];
     __shared__ uint32_t s_hi, s_lo;
@@ -680,7 +722,7 @@ __global__ __launch_bounds__(256) void nms_kernel(const float* __restrict__ eig,
     __syncthreads();
     for (int i = tid; i < ncells; i += 256) {
         // cv::threshold on CV_32F compares with (float)(maxVal * quality_level), maxVal a double
-        const float mx = ordered_to_float(cell_max[i]);
+        const float mx = (MASKED && cell_max[i] == 0u) ? 0.f : ordered_to_float(cell_max[i]);
         s_thr[i] = (float)((double)mx * quality_level);
         // value range of the candidates (bucket sort, see bucket_of): above the smallest threshold, up to the largest maximum
         atomicMax(&s_hi, cell_max[i]);
@@ -768,13 +810,24 @@ __global__ __launch_bounds__(256) void nms_kernel(const float* __restrict__ eig,
                 cm[i] = m > c ? m : c;
             }
             uint32_t f4 = 0;
+            uint32_t on = 0xfu;            // bit i: pixel i of the quad may be a candidate
+            if (MASKED) {
+                const uint8_t* mk = mask + (size_t)y * w + x;
+                uint32_t m4 = 0;           // the quad's four mask bytes
+                if (x + 3 < w && ((w & 3) == 0)) {
+                    m4 = *reinterpret_cast<const uint32_t*>(mk);
+                } else {
+                    for (int i = 0; i < 4 && x + i < w; i++) m4 |= (uint32_t)mk[i] << (8 * i);
+                }
+                on = ((m4 & 0xffu) ? 1u : 0u) | ((m4 & 0xff00u) ? 2u : 0u) | ((m4 & 0xff0000u) ? 4u : 0u) | ((m4 & 0xff000000u) ? 8u : 0u);
+            }
 #pragma unroll
             for (int i = 0; i < 4; i++) {
                 const float val = s_v[r + 1][4 * q + 1 + i];
                 float m = cm[i] > cm[i + 1] ? cm[i] : cm[i + 1];
                 m = m > cm[i + 2] ? m : cm[i + 2];
                 const int xi = x + i;
-                if (val != 0.f && val == m && xi >= 1 && xi < w - 1 && y >= 1 && y < h - 1) {
+                if (val != 0.f && val == m && xi >= 1 && xi < w - 1 && y >= 1 && y < h - 1 && (!MASKED || ((on >> i) & 1u))) {
                     f4 |= 1u << i;
                     vals[sub][i] = val;
                 }
@@ -844,11 +897,16 @@ __global__ __launch_bounds__(256) void nms_kernel(const float* __restrict__ eig,
 void launch_nms(const float* eig, int w, int h, const GfttGrid& g, const uint32_t* cell_max, double quality_level,
                 unsigned long long* keys, uint32_t cap, uint32_t* counter, uint8_t* cstate, uint32_t* sort_params, uint32_t* hist,
                 uint32_t* ticket, uint32_t* bucket_offsets, uint32_t* bin_hist, hipStream_t s,
-                unsigned long long* slots, uint32_t* zero, int zero_words) {
+                unsigned long long* slots, uint32_t* zero, int zero_words, const uint8_t* mask) {
     dim3 grid((w + TW - 1) / TW, (h + NMS_SUB * TH - 1) / (NMS_SUB * TH));
-    hipLaunchKernelGGL(nms_kernel, grid, dim3(256), 0, s, eig, w, h, g, cell_max, quality_level, keys, cap, counter, cstate,
-                       sort_params, hist, ticket, bucket_offsets, bin_hist, bin_hist ? bin_num_tiles(w, h) : 0, slots, zero,
-                       zero ? zero_words : 0, helper_prio_arg());
+    if (mask)
+        hipLaunchKernelGGL(nms_kernel<true>, grid, dim3(256), 0, s, eig, w, h, g, cell_max, quality_level, keys, cap, counter, cstate,
+                           sort_params, hist, ticket, bucket_offsets, bin_hist, bin_hist ? bin_num_tiles(w, h) : 0, slots, zero,
+                           zero ? zero_words : 0, helper_prio_arg(), mask);
+    else
+        hipLaunchKernelGGL(nms_kernel<false>, grid, dim3(256), 0, s, eig, w, h, g, cell_max, quality_level, keys, cap, counter, cstate,
+                           sort_params, hist, ticket, bucket_offsets, bin_hist, bin_hist ? bin_num_tiles(w, h) : 0, slots, zero,
+                           zero ? zero_words : 0, helper_prio_arg(), (const uint8_t*)nullptr);
 }
 
 // ------------------------------------------------------------------------------------------------

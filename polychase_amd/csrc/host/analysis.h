@@ -64,6 +64,28 @@ struct FrameView {
     std::shared_ptr<void> owner;
 };
 
+// ---- detection mask (not in the reference's Python surface; its detector has it: cpp/feature_detection/gftt.cc:14-86) ------
+// rows x cols uint8, non-zero = keypoints may be detected here; the semantics are the reference's `mask` argument
+// (include/polychase_hip.h: pc_frame_set_mask), not a filter on the unmasked keypoints.  `data` is host memory (consumed when
+// the mask is handed to the engine) or HIP device memory of the GPU in use (on_device; `owner` keeps it alive while it is read).
+struct MaskView {
+    const uint8_t* data = nullptr;
+    int rows = 0;
+    int cols = 0;
+    size_t row_pitch = 0;  // bytes between rows
+    bool on_device = false;
+    std::shared_ptr<void> owner;
+};
+// Either one mask for every frame the run detects (`fixed`), or a function asked once per such frame (`per_frame`; nothing =
+// that frame is detected without a mask); empty = no mask.  Asked only for frames that WILL be detected: not for the halo
+// frames of a shard, and not for frames whose `keypoints` row exists -- a resumed run keeps the stored keypoints whatever mask
+// is passed.  The mask is not stored in the database.  A mask of another size than the clip: std::invalid_argument.
+struct DetectionMask {
+    std::optional<MaskView> fixed;
+    std::function<std::optional<MaskView>(int32_t frame_id)> per_frame;
+    bool empty() const { return !fixed && !per_frame; }
+};
+
 // Returns the frame with the given id, or nothing if it cannot be supplied.
 using FrameAccessorFunction = std::function<std::optional<FrameView>(int32_t frame_id)>;
 // (progress in [0,1], message); returning false cancels the run.
@@ -97,7 +119,8 @@ struct OpticalFlowRunStats {
 void GenerateOpticalFlowDatabase(const VideoInfo& video_info, FrameAccessorFunction frame_accessor,
                                  OpticalFlowProgressCallback callback, const std::string& database_path,
                                  const GFTTOptions& detector_options = {}, const OpticalFlowOptions& flow_options = {},
-                                 bool write_images = false, OpticalFlowRunStats* stats = nullptr);
+                                 bool write_images = false, OpticalFlowRunStats* stats = nullptr,
+                                 const DetectionMask& detection_mask = {});
 
 // Frees the idle engine a finished run has parked for the next one (GPU memory of ~20 resident frames; analysis_driver.cc:
 // EngineCache).  POLYCHASE_ENGINE_CACHE=0 disables the parking altogether.
@@ -137,13 +160,15 @@ struct OpticalFlowShard {
 };
 void GenerateOpticalFlowShard(const VideoInfo& video_info, FrameAccessorFunction frame_accessor, OpticalFlowProgressCallback callback,
                               const std::string& database_path, OpticalFlowShard& shard, const GFTTOptions& detector_options = {},
-                              const OpticalFlowOptions& flow_options = {}, OpticalFlowRunStats* stats = nullptr);
+                              const OpticalFlowOptions& flow_options = {}, OpticalFlowRunStats* stats = nullptr,
+                              const DetectionMask& detection_mask = {});
 // The same with ONE piece in a buffer of capacity_bytes and nothing stored.  Returns the bytes used; throws
 // ("device log full") when the log is too small.
 size_t GenerateOpticalFlowRecords(const VideoInfo& video_info, FrameAccessorFunction frame_accessor,
                                   OpticalFlowProgressCallback callback, int32_t shard_begin, int32_t shard_end,
                                   void* device_log, size_t capacity_bytes, const GFTTOptions& detector_options = {},
-                                  const OpticalFlowOptions& flow_options = {}, OpticalFlowRunStats* stats = nullptr);
+                                  const OpticalFlowOptions& flow_options = {}, OpticalFlowRunStats* stats = nullptr,
+                                  const DetectionMask& detection_mask = {});
 
 // Stores a record log (host copy, e.g. one rank's part of the all-gather) in the database: per record one transaction
 // with the `keypoints` row and its `optical_flow` rows, rows that exist are kept (opticalflow.cc:168-178, :286) --

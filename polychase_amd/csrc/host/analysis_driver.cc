@@ -348,8 +348,15 @@ struct LogPiece {
 static void RunAnalysis(const VideoInfo& video_info, FrameAccessorFunction frame_accessor,
                         OpticalFlowProgressCallback callback, const std::string& database_path,
                         const GFTTOptions& detector_options, const OpticalFlowOptions& flow_options,
-                        OpticalFlowRunStats* stats, OpticalFlowShard* shard, bool write_images) {
+                        OpticalFlowRunStats* stats, OpticalFlowShard* shard, bool write_images, const DetectionMask& detection_mask) {
     CHECK(frame_accessor);
+    auto check_mask = [&](const MaskView& m) {
+        if (!m.data || m.rows != static_cast<int>(video_info.height) || m.cols != static_cast<int>(video_info.width) ||
+            m.row_pitch < static_cast<size_t>(m.cols))
+            throw std::invalid_argument("detection mask must be " + std::to_string(video_info.height) + " x " + std::to_string(video_info.width) +
+                                        " uint8 (the reference CHECKs CV_8UC1 and the image's size, gftt.cc:22-27)");
+    };
+    if (detection_mask.fixed) check_mask(*detection_mask.fixed);   // before any GPU work
     const double t_begin = Now();
     std::unique_ptr<Database> db;
     if (!database_path.empty()) db = std::make_unique<Database>(database_path, /*bulk_writer=*/true);
@@ -422,6 +429,12 @@ static void RunAnalysis(const VideoInfo& video_info, FrameAccessorFunction frame
     Engine& eng = *engine;
     // set on every run: a parked engine may have served another threshold (the cache is not keyed on it)
     if (pc_analyzer_set_fb_threshold(eng.an, flow_options.forward_backward_threshold) != PC_OK) ThrowHip("pc_analyzer_set_fb_threshold");
+    // ... and so is the detection mask: the run's one mask, or none until the first frame's is asked for
+    auto set_mask = [&](const std::optional<MaskView>& m) {
+        if (m) check_mask(*m);
+        if (pc_analyzer_set_mask(eng.an, m ? m->data : nullptr, m ? m->row_pitch : 0, m && m->on_device ? 1 : 0) != PC_OK) ThrowHip("pc_analyzer_set_mask");
+    };
+    set_mask(detection_mask.fixed);
     // the threads that feed this GPU stay on its NUMA node (numa_pin.h): this one for the duration of the call, the writer and its
     // page-write worker (started below / when the database opens its file) for their lives
     numa::ScopedPin near_gpu(eng.ctx, "analysis: calling thread");
@@ -611,6 +624,16 @@ static void RunAnalysis(const VideoInfo& video_info, FrameAccessorFunction frame
                 std::lock_guard<std::mutex> lk(db_mtx);
                 will_detect = !db->KeypointsExist(fid);
             }
+            // the mask of this frame's detection (asked only for frames that are detected); a device mask is read when the
+            // frame is put, so its owner waits with the frame's for pc_analyzer_frame_ingested
+            std::shared_ptr<void> mask_owner;
+            if (will_detect && detection_mask.per_frame) {
+                std::optional<MaskView> m = detection_mask.per_frame(fid);
+                set_mask(m);
+                if (m && m->on_device) mask_owner = std::move(m->owner);
+            } else if (will_detect && detection_mask.fixed && detection_mask.fixed->on_device) {
+                mask_owner = detection_mask.fixed->owner;
+            }
             static const bool ingest_dma = !(std::getenv("POLYCHASE_INGEST_DMA") && std::atoi(std::getenv("POLYCHASE_INGEST_DMA")) == 0);
             const int where = !f->on_device ? 0 : (f->pinned_host && f->owner && ingest_dma ? PC_FRAME_PINNED_HOST : 1);
             StageClock put_clk(&local_stats.seconds_put);
@@ -645,6 +668,7 @@ static void RunAnalysis(const VideoInfo& video_info, FrameAccessorFunction frame
             // the owner first: put_frame may have enqueued a copy out of the buffer before it failed, and
             // frames_in_flight outlives the engine (whose destructor synchronises) while `f` does not
             if (f->on_device && f->owner) frames_in_flight.emplace_back(fid, std::move(f->owner));
+            if (mask_owner) frames_in_flight.emplace_back(fid, std::move(mask_owner));
             if (put_rc != PC_OK) ThrowHip("pc_analyzer_put_frame");
             release_ingested(frames_in_flight.size() > 24);   // bounded: the pool behind the owners is finite
             highest_put = fid;
@@ -701,33 +725,33 @@ bool EngineCacheTimerRunning() { return EngineCache::TimerRunning(); }
 void GenerateOpticalFlowDatabase(const VideoInfo& video_info, FrameAccessorFunction frame_accessor,
                                  OpticalFlowProgressCallback callback, const std::string& database_path,
                                  const GFTTOptions& detector_options, const OpticalFlowOptions& flow_options,
-                                 bool write_images, OpticalFlowRunStats* stats) {
+                                 bool write_images, OpticalFlowRunStats* stats, const DetectionMask& detection_mask) {
     RunAnalysis(video_info, std::move(frame_accessor), std::move(callback), database_path, detector_options, flow_options, stats,
-                nullptr, write_images);
+                nullptr, write_images, detection_mask);
 }
 
 void GenerateOpticalFlowShard(const VideoInfo& video_info, FrameAccessorFunction frame_accessor, OpticalFlowProgressCallback callback,
                               const std::string& database_path, OpticalFlowShard& shard, const GFTTOptions& detector_options,
-                              const OpticalFlowOptions& flow_options, OpticalFlowRunStats* stats) {
+                              const OpticalFlowOptions& flow_options, OpticalFlowRunStats* stats, const DetectionMask& detection_mask) {
     CHECK(shard.begin <= shard.end);
     CHECK(shard.device_log != nullptr || !database_path.empty());
     shard.used_bytes = 0;
     shard.pieces = 0;
     shard.cancelled = false;
-    RunAnalysis(video_info, std::move(frame_accessor), std::move(callback), database_path, detector_options, flow_options, stats, &shard, false);
+    RunAnalysis(video_info, std::move(frame_accessor), std::move(callback), database_path, detector_options, flow_options, stats, &shard, false, detection_mask);
 }
 
 size_t GenerateOpticalFlowRecords(const VideoInfo& video_info, FrameAccessorFunction frame_accessor,
                                   OpticalFlowProgressCallback callback, int32_t shard_begin, int32_t shard_end,
                                   void* device_log, size_t capacity_bytes, const GFTTOptions& detector_options,
-                                  const OpticalFlowOptions& flow_options, OpticalFlowRunStats* stats) {
+                                  const OpticalFlowOptions& flow_options, OpticalFlowRunStats* stats, const DetectionMask& detection_mask) {
     CHECK(device_log != nullptr);
     OpticalFlowShard shard;
     shard.begin = shard_begin;
     shard.end = shard_end;
     shard.device_log = device_log;
     shard.capacity_bytes = capacity_bytes;
-    GenerateOpticalFlowShard(video_info, std::move(frame_accessor), std::move(callback), "", shard, detector_options, flow_options, stats);
+    GenerateOpticalFlowShard(video_info, std::move(frame_accessor), std::move(callback), "", shard, detector_options, flow_options, stats, detection_mask);
     return shard.used_bytes;
 }
 

@@ -29,13 +29,14 @@ using OpticalFlowThreadMessage = std::variant<OpticalFlowProgress, OpticalFlowRe
 class OpticalFlowThread : public Worker<OpticalFlowThreadMessage> {
    public:
     OpticalFlowThread(VideoInfo video_info, std::string database_path, GFTTOptions detector_options = {},
-                      OpticalFlowOptions flow_options = {}, bool write_images = false) {
+                      OpticalFlowOptions flow_options = {}, bool write_images = false, DetectionMask detection_mask = {}) {
+        // (one mask for the whole clip only: the message protocol has no request for a mask)
         Start(
             [=] {
                 GenerateOpticalFlowDatabase(
                     video_info, [this](int32_t id) { return WaitForFrame(id); },
                     [this](float p, const std::string& msg) { return ReportProgress(p, msg); }, database_path,
-                    detector_options, flow_options, write_images);
+                    detector_options, flow_options, write_images, nullptr, detection_mask);
             },
             [this](const std::string& what) {
                 // request_stop() while the worker waits for a frame makes the accessor come back empty, which

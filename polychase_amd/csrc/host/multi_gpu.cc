@@ -249,7 +249,7 @@ size_t LogPartBytes(const VideoInfo& vi, const MultiGpuConfig& cfg) {
 MultiGpuResult GenerateOpticalFlowDatabaseMultiGpu(const VideoInfo& video_info, FrameAccessorFunction frame_accessor,
                                                    OpticalFlowProgressCallback callback, const std::string& database_path,
                                                    const MultiGpuConfig& cfg, const GFTTOptions& detector_options,
-                                                   const OpticalFlowOptions& flow_options) {
+                                                   const OpticalFlowOptions& flow_options, const DetectionMask& detection_mask) {
     const int world = cfg.world_size, rank = cfg.rank;
     if (world < 1 || rank < 0 || rank >= world) Fail("rank " + std::to_string(rank) + " of " + std::to_string(world));
     if (cfg.transport != "rccl" && cfg.transport != "tcp") Fail("transport must be rccl or tcp");
@@ -267,7 +267,7 @@ MultiGpuResult GenerateOpticalFlowDatabaseMultiGpu(const VideoInfo& video_info, 
     shard.end = res.shard_end;
     shard.device = device;
     if (world == 1) {
-        GenerateOpticalFlowShard(video_info, frame_accessor, callback, database_path, shard, detector_options, flow_options, &res.stats);
+        GenerateOpticalFlowShard(video_info, frame_accessor, callback, database_path, shard, detector_options, flow_options, &res.stats, detection_mask);
         res.cancelled = shard.cancelled;
         res.seconds_analysis = res.seconds_total = Since(t0);
         return res;
@@ -354,7 +354,7 @@ MultiGpuResult GenerateOpticalFlowDatabaseMultiGpu(const VideoInfo& video_info, 
                 });
                 own.Close();
             } else {
-                GenerateOpticalFlowShard(video_info, frame_accessor, callback, database_path, shard, detector_options, flow_options, &res.stats);
+                GenerateOpticalFlowShard(video_info, frame_accessor, callback, database_path, shard, detector_options, flow_options, &res.stats, detection_mask);
             }
             res.seconds_analysis = Since(t0);
             OpticalFlowRecordWriter writer(database_path);
@@ -465,7 +465,7 @@ MultiGpuResult GenerateOpticalFlowDatabaseMultiGpu(const VideoInfo& video_info, 
                 if (!outgoing.Push(std::move(o), &res.seconds_blocked)) Fail("the sender ended (see its error)");
             });
         } else {
-            GenerateOpticalFlowShard(video_info, frame_accessor, callback, "", shard, detector_options, flow_options, &res.stats);
+            GenerateOpticalFlowShard(video_info, frame_accessor, callback, "", shard, detector_options, flow_options, &res.stats, detection_mask);
         }
     } catch (...) {
         failure = std::current_exception();

@@ -55,4 +55,4 @@ struct MultiGpuResult {
 MultiGpuResult GenerateOpticalFlowDatabaseMultiGpu(const VideoInfo& video_info, FrameAccessorFunction frame_accessor,
                                                    OpticalFlowProgressCallback callback, const std::string& database_path,
                                                    const MultiGpuConfig& config, const GFTTOptions& detector_options = {},
-                                                   const OpticalFlowOptions& flow_options = {});
+                                                   const OpticalFlowOptions& flow_options = {}, const DetectionMask& detection_mask = {});

@@ -97,10 +97,50 @@ std::optional<FrameView> FrameFromPython(const py::object& obj, std::deque<py::o
     return v;
 }
 
+// Python detection mask (numpy H x W uint8) -> MaskView owning a packed copy.  ValueError for any other dtype or shape: the
+// reference CHECKs CV_8UC1 and the image's size (gftt.cc:22-27); no silent conversion.
+MaskView MaskFromPython(const py::object& obj, const VideoInfo& video_info) {
+    if (!py::isinstance<py::array>(obj)) throw py::value_error("detection_mask must be a uint8 array of shape (H, W), a callable or None");
+    const py::array arr = py::reinterpret_borrow<py::array>(obj);
+    if (!arr.dtype().is(py::dtype::of<uint8_t>())) throw py::value_error("detection_mask must have dtype uint8");
+    if (arr.ndim() != 2 || arr.shape(0) != static_cast<py::ssize_t>(video_info.height) || arr.shape(1) != static_cast<py::ssize_t>(video_info.width))
+        throw py::value_error("detection_mask must have shape (" + std::to_string(video_info.height) + ", " + std::to_string(video_info.width) + ")");
+    const U8Array a = U8Array::ensure(arr);   // C order (a strided view is packed here)
+    auto copy = std::make_shared<std::vector<uint8_t>>(a.data(), a.data() + a.size());
+    MaskView v;
+    v.data = copy->data();
+    v.rows = static_cast<int>(video_info.height);
+    v.cols = static_cast<int>(video_info.width);
+    v.row_pitch = static_cast<size_t>(video_info.width);
+    v.owner = copy;
+    return v;
+}
+
+// detection_mask=None | array | callable(frame_id) -> array | None.  `obj` must outlive the run (the callable is called with
+// the GIL from the driver's thread).  allow_callable = false: OpticalFlowThread, whose protocol has no mask request.
+DetectionMask DetectionMaskFromPython(const py::object& obj, const VideoInfo& video_info, bool allow_callable = true) {
+    DetectionMask m;
+    if (obj.is_none()) return m;
+    if (PyCallable_Check(obj.ptr())) {
+        if (!allow_callable) throw py::value_error("detection_mask must be a uint8 array of shape (H, W) or None");
+        m.per_frame = [&obj, video_info](int32_t frame_id) -> std::optional<MaskView> {
+            py::gil_scoped_acquire gil;
+            const py::object r = obj(frame_id);
+            if (r.is_none()) return std::nullopt;
+            return MaskFromPython(r, video_info);
+        };
+        return m;
+    }
+    m.fixed = MaskFromPython(obj, video_info);
+    return m;
+}
+
 OpticalFlowRunStats GenerateOpticalFlowDatabasePy(const VideoInfo& video_info, py::object frame_accessor,
                                                   py::object callback, const std::string& database_path,
                                                   const GFTTOptions& detector_options,
-                                                  const OpticalFlowOptions& flow_options, bool write_images) {
+                                                  const OpticalFlowOptions& flow_options, bool write_images,
+                                                  py::object detection_mask) {
+    const DetectionMask mask = DetectionMaskFromPython(detection_mask, video_info);
     std::deque<py::object> keep_alive;
     FrameAccessorFunction accessor;
     if (!frame_accessor.is_none())
@@ -118,7 +158,7 @@ OpticalFlowRunStats GenerateOpticalFlowDatabasePy(const VideoInfo& video_info, p
     {
         py::gil_scoped_release release;  // polychase_pybind.cc:332
         GenerateOpticalFlowDatabase(video_info, accessor, cb, database_path, detector_options, flow_options,
-                                    write_images, &stats);
+                                    write_images, &stats, mask);
     }
     keep_alive.clear();
     return stats;
@@ -127,7 +167,9 @@ OpticalFlowRunStats GenerateOpticalFlowDatabasePy(const VideoInfo& video_info, p
 // one shard of a multi-process analysis: records into a device log (a torch uint8 CUDA tensor's memory)
 py::tuple GenerateOpticalFlowRecordsPy(const VideoInfo& video_info, py::object frame_accessor, py::object callback,
                                        int32_t shard_begin, int32_t shard_end, uintptr_t device_log, size_t capacity_bytes,
-                                       const GFTTOptions& detector_options, const OpticalFlowOptions& flow_options) {
+                                       const GFTTOptions& detector_options, const OpticalFlowOptions& flow_options,
+                                       py::object detection_mask) {
+    const DetectionMask mask = DetectionMaskFromPython(detection_mask, video_info);
     std::deque<py::object> keep_alive;
     FrameAccessorFunction accessor;
     if (!frame_accessor.is_none())
@@ -146,7 +188,7 @@ py::tuple GenerateOpticalFlowRecordsPy(const VideoInfo& video_info, py::object f
     {
         py::gil_scoped_release release;
         used = GenerateOpticalFlowRecords(video_info, accessor, cb, shard_begin, shard_end, reinterpret_cast<void*>(device_log),
-                                          capacity_bytes, detector_options, flow_options, &stats);
+                                          capacity_bytes, detector_options, flow_options, &stats, mask);
     }
     keep_alive.clear();
     return py::make_tuple(used, stats);
@@ -158,7 +200,9 @@ py::tuple GenerateOpticalFlowRecordsPy(const VideoInfo& video_info, py::object f
 py::dict GenerateOpticalFlowShardPy(const VideoInfo& video_info, py::object frame_accessor, py::object callback,
                                     const std::string& database_path, int32_t shard_begin, int32_t shard_end, uintptr_t device_log,
                                     size_t capacity_bytes, int log_buffers, int piece_frames, py::object on_piece, bool host_records,
-                                    const GFTTOptions& detector_options, const OpticalFlowOptions& flow_options) {
+                                    const GFTTOptions& detector_options, const OpticalFlowOptions& flow_options,
+                                    py::object detection_mask) {
+    const DetectionMask mask = DetectionMaskFromPython(detection_mask, video_info);
     std::deque<py::object> keep_alive;
     FrameAccessorFunction accessor;
     if (!frame_accessor.is_none())
@@ -188,7 +232,7 @@ py::dict GenerateOpticalFlowShardPy(const VideoInfo& video_info, py::object fram
     OpticalFlowRunStats stats;
     {
         py::gil_scoped_release release;
-        GenerateOpticalFlowShard(video_info, accessor, cb, database_path, shard, detector_options, flow_options, &stats);
+        GenerateOpticalFlowShard(video_info, accessor, cb, database_path, shard, detector_options, flow_options, &stats, mask);
     }
     keep_alive.clear();
     py::dict out;
@@ -205,7 +249,8 @@ py::dict GenerateOpticalFlowDatabaseMultiGpuPy(const VideoInfo& video_info, py::
                                                const std::string& database_path, int world_size, int rank, const std::string& master_addr,
                                                int master_port, int device, int piece_frames, const std::string& transport,
                                                size_t keypoints_per_frame, const GFTTOptions& detector_options,
-                                               const OpticalFlowOptions& flow_options) {
+                                               const OpticalFlowOptions& flow_options, py::object detection_mask) {
+    const DetectionMask mask = DetectionMaskFromPython(detection_mask, video_info);
     std::deque<py::object> keep_alive;
     FrameAccessorFunction accessor;
     if (!frame_accessor.is_none())
@@ -231,7 +276,7 @@ py::dict GenerateOpticalFlowDatabaseMultiGpuPy(const VideoInfo& video_info, py::
     MultiGpuResult r;
     {
         py::gil_scoped_release release;
-        r = GenerateOpticalFlowDatabaseMultiGpu(video_info, accessor, cb, database_path, cfg, detector_options, flow_options);
+        r = GenerateOpticalFlowDatabaseMultiGpu(video_info, accessor, cb, database_path, cfg, detector_options, flow_options, mask);
     }
     keep_alive.clear();
     py::dict out;
@@ -383,10 +428,15 @@ PYBIND11_MODULE(polychase_core, m) {
         .def_readonly("seconds_writer_wait", &OpticalFlowRunStats::seconds_writer_wait);
 
     py::class_<OpticalFlowThread>(m, "OpticalFlowThread")
-        .def(py::init<VideoInfo, std::string, GFTTOptions, OpticalFlowOptions, bool>(), py::arg("video_info"),
-             py::arg("database_path"), py::arg("detector_options") = GFTTOptions{},
+        .def(py::init([](VideoInfo video_info, std::string database_path, GFTTOptions detector_options, OpticalFlowOptions flow_options,
+                         bool write_images, py::object detection_mask) {
+                 DetectionMask mask = DetectionMaskFromPython(detection_mask, video_info, /*allow_callable=*/false);
+                 return std::make_unique<OpticalFlowThread>(video_info, std::move(database_path), detector_options, flow_options, write_images,
+                                                            std::move(mask));
+             }),
+             py::arg("video_info"), py::arg("database_path"), py::arg("detector_options") = GFTTOptions{},
              py::arg("OpticalFlowOptions") = OpticalFlowOptions{},  // sic: polychase_pybind.cc:186
-             py::arg("write_images") = false)
+             py::arg("write_images") = false, py::arg("detection_mask") = py::none())   // detection_mask: not in the reference
         .def("request_stop", &OpticalFlowThread::RequestStop)
         .def("join", &OpticalFlowThread::Join, py::call_guard<py::gil_scoped_release>())
         .def("try_pop", &OpticalFlowThread::TryPop)
@@ -410,7 +460,8 @@ PYBIND11_MODULE(polychase_core, m) {
     // process per GPU, and all-gathers the record logs over RCCL in between)
     m.def("generate_optical_flow_records", &GenerateOpticalFlowRecordsPy, py::arg("video_info"), py::arg("frame_accessor_function"),
           py::arg("callback"), py::arg("shard_begin"), py::arg("shard_end"), py::arg("device_log"), py::arg("capacity_bytes"),
-          py::arg("detector_options") = GFTTOptions{}, py::arg("flow_options") = OpticalFlowOptions{});
+          py::arg("detector_options") = GFTTOptions{}, py::arg("flow_options") = OpticalFlowOptions{},
+          py::arg("detection_mask") = py::none());
     // not in the reference's module: its SaveImageForDebugging (cpp/opticalflow.cc:80-96) by itself, for the tests
     m.def("_save_image_for_debugging", [](const U8Array& rgb, int32_t frame_id, const std::string& dir, const F32Array& kps) {
         if (rgb.ndim() != 3 || rgb.shape(2) != 3) throw py::value_error("rgb must be (H, W, 3) uint8");
@@ -437,12 +488,13 @@ PYBIND11_MODULE(polychase_core, m) {
     m.def("generate_optical_flow_shard", &GenerateOpticalFlowShardPy, py::arg("video_info"), py::arg("frame_accessor_function"),
           py::arg("callback"), py::arg("database_path"), py::arg("shard_begin"), py::arg("shard_end"), py::arg("device_log") = 0,
           py::arg("capacity_bytes") = 0, py::arg("log_buffers") = 1, py::arg("piece_frames") = 0, py::arg("on_piece") = py::none(),
-          py::arg("host_records") = true, py::arg("detector_options") = GFTTOptions{}, py::arg("flow_options") = OpticalFlowOptions{});
+          py::arg("host_records") = true, py::arg("detector_options") = GFTTOptions{}, py::arg("flow_options") = OpticalFlowOptions{},
+          py::arg("detection_mask") = py::none());
     m.def("generate_optical_flow_database_multi_gpu", &GenerateOpticalFlowDatabaseMultiGpuPy, py::arg("video_info"),
           py::arg("frame_accessor_function"), py::arg("callback"), py::arg("database_path"), py::arg("world_size"), py::arg("rank"),
           py::arg("master_addr") = "127.0.0.1", py::arg("master_port") = 29611, py::arg("device") = -1, py::arg("piece_frames") = 16,
           py::arg("transport") = "rccl", py::arg("keypoints_per_frame") = 0, py::arg("detector_options") = GFTTOptions{},
-          py::arg("flow_options") = OpticalFlowOptions{});
+          py::arg("flow_options") = OpticalFlowOptions{}, py::arg("detection_mask") = py::none());
     // Testing aid (not in the reference): GenerateOpticalFlowDatabaseMultiGpu's protocol -- credits, headers, ordered pieces, failure
     // propagation, the cancelled flag -- with the rank's shard given as ready-made record logs instead of an analysis
     // (MultiGpuConfig::synthetic_shard, transport "tcp"): runs on a box without a GPU (tests/test_distributed_cpu.py).
@@ -508,7 +560,7 @@ PYBIND11_MODULE(polychase_core, m) {
     m.def("generate_optical_flow_database", &GenerateOpticalFlowDatabasePy, py::arg("video_info"),
           py::arg("frame_accessor_function"), py::arg("callback"), py::arg("database_path"),
           py::arg("detector_options") = GFTTOptions{}, py::arg("flow_options") = OpticalFlowOptions{},
-          py::arg("write_images") = false);
+          py::arg("write_images") = false, py::arg("detection_mask") = py::none());   // detection_mask: not in the reference
 
 #ifdef PC_WITH_TRACKER
     BindTracker(m);

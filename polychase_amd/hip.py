@@ -27,13 +27,13 @@ SYMBOLS = [
     "pc_host_buffer_alloc", "pc_host_buffer_free",
     "pc_frame_num_levels", "pc_frame_level_size", "pc_frame_download_gray", "pc_frame_download_level",
     "pc_frame_download_deriv", "pc_frame_detect", "pc_frame_download_min_eig", "pc_frame_num_candidates",
-    "pc_frame_num_keypoints", "pc_frame_download_keypoints", "pc_frame_set_keypoints",
+    "pc_frame_num_keypoints", "pc_frame_download_keypoints", "pc_frame_set_keypoints", "pc_frame_set_mask",
     "pc_lk_track", "pc_lk_track_filtered", "pc_lk_track_fb", "pc_lk_track_filtered_fb",
     "pc_analyzer_create", "pc_analyzer_destroy", "pc_analyzer_reset", "pc_analyzer_put_frame", "pc_analyzer_put_frame_f32",
     "pc_analyzer_has_frame", "pc_analyzer_frame_ingested",
     "pc_analyzer_set_keypoints", "pc_analyzer_submit", "pc_analyzer_pending", "pc_analyzer_collect",
     "pc_analyzer_set_device_log", "pc_analyzer_device_log_used", "pc_analyzer_redirect_device_log",
-    "pc_analyzer_set_host_records", "pc_analyzer_set_fb_threshold",
+    "pc_analyzer_set_host_records", "pc_analyzer_set_fb_threshold", "pc_analyzer_set_mask",
     "pc_peer_buffer_alloc", "pc_peer_buffer_free", "pc_peer_buffer_export", "pc_peer_buffer_open", "pc_peer_buffer_close",
     "pc_peer_copy_async", "pc_peer_buffer_download",
     "pc_comm_unique_id", "pc_comm_create", "pc_comm_destroy", "pc_comm_world_size", "pc_comm_rank", "pc_comm_all_gather_log",
@@ -134,6 +134,7 @@ def load():
     L.pc_frame_download_level.argtypes = [vp, vp, C.c_int, vp]
     L.pc_frame_download_deriv.argtypes = [vp, vp, C.c_int, vp]
     L.pc_frame_detect.argtypes = [vp, vp, C.POINTER(GfttOptions)]
+    L.pc_frame_set_mask.argtypes = [vp, vp, vp, C.c_size_t, C.c_int]
     L.pc_frame_download_min_eig.argtypes = [vp, vp, vp]
     L.pc_frame_num_candidates.argtypes = [vp, vp, ip]
     L.pc_frame_num_keypoints.argtypes = [vp, vp, ip]
@@ -161,6 +162,7 @@ def load():
     L.pc_analyzer_redirect_device_log.argtypes = [vp, vp, C.c_size_t]
     L.pc_analyzer_set_host_records.argtypes = [vp, C.c_int]
     L.pc_analyzer_set_fb_threshold.argtypes = [vp, C.c_double]
+    L.pc_analyzer_set_mask.argtypes = [vp, vp, C.c_size_t, C.c_int]
     L.pc_peer_buffer_alloc.argtypes = [C.c_int, C.c_size_t, C.POINTER(vp)]
     L.pc_peer_buffer_free.argtypes = [C.c_int, vp]
     L.pc_peer_buffer_export.argtypes = [C.c_int, vp, C.c_char_p]
@@ -297,6 +299,27 @@ def _ptr(a):
     return a.data_ptr(), 1 if a.is_cuda else 0, a.stride(0) * a.element_size()
 
 
+def _mask_ptr(mask, w: int, h: int):
+    """detection mask -> (address, is_device, row_pitch_bytes): uint8 (H, W), numpy (rows may be strided: a view of a wider
+    array) or a torch tensor, host or device, whose rows are contiguous (they too may lie a pitch >= W apart).  ValueError for
+    anything else (the reference CHECKs CV_8UC1 and the image's size)."""
+    if str(mask.dtype) not in ("uint8", "torch.uint8"):
+        raise ValueError(f"detection mask must be uint8, got {mask.dtype}")
+    if tuple(mask.shape) != (h, w):
+        raise ValueError(f"detection mask must have shape {(h, w)}, got {tuple(mask.shape)}")
+    if isinstance(mask, np.ndarray):
+        if w > 1 and mask.strides[1] != 1 or (h > 1 and mask.strides[0] < w):
+            mask = np.ascontiguousarray(mask)
+        return mask, mask.ctypes.data, 0, (mask.strides[0] if h > 1 else w)
+    if (w > 1 and mask.stride(1) != 1) or (h > 1 and mask.stride(0) < w):
+        raise ValueError(f"detection mask tensor must have contiguous rows at least {w} bytes apart, got strides {tuple(mask.stride())}")
+    if mask.is_cuda:
+        # the library enqueues on its own HIP stream: the tensor must be complete before it is read
+        import torch
+        torch.cuda.current_stream(mask.device).synchronize()
+    return mask, mask.data_ptr(), 1 if mask.is_cuda else 0, (mask.stride(0) if h > 1 else w)
+
+
 def _is_float32(a) -> bool:
     return str(a.dtype) in ("float32", "torch.float32")
 
@@ -362,6 +385,16 @@ class Frame:
         out = np.empty((h + 2 * self.win, w + 2 * self.win, 2), np.int16)
         _check(load().pc_frame_download_deriv(self.ctx._h, self._h, l, out.ctypes.data))
         return out
+
+    def set_mask(self, mask):
+        """Detection mask of the next detect() (pc_frame_set_mask): uint8 (H, W), non-zero = detect here; None clears it."""
+        if mask is None:
+            _check(load().pc_frame_set_mask(self.ctx._h, self._h, None, 0, 0))
+            self._keep_mask = None
+            return
+        keep, p, dev, pitch = _mask_ptr(mask, self.w, self.h)
+        _check(load().pc_frame_set_mask(self.ctx._h, self._h, p, pitch, dev))
+        self._keep_mask = keep if dev else None   # a device mask is read stream-ordered
 
     def detect(self, opt: GfttOptions | None = None):
         opt = opt or gftt_options()
@@ -472,6 +505,7 @@ class Analyzer:
         self.flow = flow or flow_options()
         self._h = C.c_void_p()
         self._keep = {}
+        self._keep_mask, self._keep_masks = None, {}   # the device mask in force / per ring slot, of the frame put under it
         _check(load().pc_analyzer_create(ctx._h, width, height, C.byref(self.gftt), C.byref(self.flow), ring_frames,
                                          max_jobs, C.byref(self._h)))
         self.ring = ring_frames
@@ -481,6 +515,7 @@ class Analyzer:
             load().pc_analyzer_destroy(self._h)
         self._h = C.c_void_p()
         self._keep = {}
+        self._keep_mask, self._keep_masks = None, {}
 
     def __del__(self):
         try:
@@ -489,9 +524,10 @@ class Analyzer:
             pass
 
     def reset(self):
-        """No resident frame, no job, no log; allocations kept (pc_analyzer_reset)."""
+        """No resident frame, no job, no log, no mask; allocations kept (pc_analyzer_reset)."""
         _check(load().pc_analyzer_reset(self._h))
         self._keep = {}
+        self._keep_mask, self._keep_masks = None, {}
 
     def put_frame(self, frame_id: int, rgb, will_detect: bool = True):
         p, dev, pitch = _ptr(rgb)
@@ -504,6 +540,9 @@ class Analyzer:
             _check(load().pc_analyzer_put_frame(self._h, frame_id, p, pitch, dev, 1 if will_detect else 0))
         if dev:
             self._keep[frame_id % self.ring] = rgb  # device sources must outlive the async kernels
+        # ... and so must the device mask this frame's detection copies: until the slot takes its next frame, whatever
+        # set_mask is given in between
+        self._keep_masks[frame_id % self.ring] = self._keep_mask if will_detect else None
 
     def has_frame(self, frame_id: int) -> bool:
         return bool(load().pc_analyzer_has_frame(self._h, frame_id))
@@ -543,6 +582,18 @@ class Analyzer:
     def set_fb_threshold(self, fb_threshold: float):
         """forward-backward check for the jobs submitted from now on; 0 = off (pc_analyzer_set_fb_threshold)"""
         _check(load().pc_analyzer_set_fb_threshold(self._h, float(fb_threshold)))
+
+    def set_mask(self, mask):
+        """Detection mask of the frames put from now on with will_detect (pc_analyzer_set_mask): uint8 (H, W), non-zero =
+        detect here; None = no mask.  A device tensor is held here until the ring slots of the frames put under it are reused;
+        the caller must leave its contents unmodified until frame_ingested() for those frames."""
+        if mask is None:
+            _check(load().pc_analyzer_set_mask(self._h, None, 0, 0))
+            self._keep_mask = None
+            return
+        keep, p, dev, pitch = _mask_ptr(mask, self.w, self.h)
+        _check(load().pc_analyzer_set_mask(self._h, p, pitch, dev))
+        self._keep_mask = keep if dev else None
 
     @property
     def device_log_used(self) -> int:

@@ -2,10 +2,15 @@
 """End-to-end rates of GenerateOpticalFlowDatabase through the polychase_core module (what the Blender
 addon experiences), next to bench.py's HBM-resident number.  Not the headline metric.
 
-  python tools/e2e_bench.py [--config c2|c3] [--frames 60]
+  python tools/e2e_bench.py [--config c2|c3] [--frames 60] [--mask-fraction F]
 
 Modes: frames as torch CUDA tensors / host numpy arrays (PCIe upload included), with and without the
-SQLite insert."""
+SQLite insert.  --mask-fraction F: every run takes detection_mask = a centred rectangle of the frame's aspect covering F of
+its area (1.0: an all-on mask, the masked kernels with nothing masked out); the SQLite modes then also report the mean number
+of keypoints per frame.  "gpu_ms_per_step": per-class GPU time, launches and keypoints of a step (pc_context_get_timing: HIP
+events around every launch) from a pass of this tool's own context and analyzer over the same frames under the same mask --
+the driver's context cannot be read from here, and events around every launch slow the step, so the rates above come from
+untimed runs."""
 import argparse
 import json
 import os
@@ -17,10 +22,34 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
+def per_class_ms(w, h, ml, frames, mask, steps=40):
+    """one pipelined pass (polychase_amd.pipeline.ClipAnalyzer) with every kernel class timed: 20 untimed steps, then `steps`"""
+    from polychase_amd import hip
+    from polychase_amd.pipeline import ClipAnalyzer
+
+    ctx = hip.Context(0)
+    an = ClipAnalyzer(ctx, w, h, 1, len(frames), lambda f: frames[f - 1], hip.gftt_options(), hip.flow_options(max_level=ml))
+    an.an.set_mask(mask)
+    steps = min(steps, len(frames) - 9 - 29)
+    an.run(range(9, 29), None)
+    ctx.synchronize()
+    ctx.enable_timing(True)
+    ctx.reset_timing()
+    kps = []
+    an.run(range(29, 29 + steps), lambda f1, k, det, flows: kps.append(len(k)), copy=False)
+    t = ctx.timing()
+    ctx.enable_timing(False)
+    an.close()
+    ctx.close()
+    return {"steps": steps, "mean_keypoints_per_frame": sum(kps) / len(kps),
+            "ms": {k: round(v[1] / steps, 4) for k, v in t.items()}, "launches": {k: v[0] for k, v in t.items()}}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", default="c2")
     ap.add_argument("--frames", type=int, default=300)
+    ap.add_argument("--mask-fraction", type=float, default=None)
     a = ap.parse_args()
     import torch
     from polychase_amd import synth
@@ -36,14 +65,26 @@ def main():
     fo.max_level = ml
     vi = core.VideoInfo(w, h, 1, a.frames)
     out = {}
+    mask = None
+    if a.mask_fraction is not None:
+        import numpy as np
+        assert 0.0 < a.mask_fraction <= 1.0
+        mw, mh = int(round(w * a.mask_fraction ** 0.5)), int(round(h * a.mask_fraction ** 0.5))
+        mask = np.zeros((h, w), np.uint8)
+        mask[(h - mh) // 2:(h - mh) // 2 + mh, (w - mw) // 2:(w - mw) // 2 + mw] = 255
+        out["mask_fraction"] = float(mask.mean() / 255.0)
+    if a.frames >= 39:
+        out["gpu_ms_per_step"] = per_class_ms(w, h, ml, dev, mask)
+    else:
+        out["gpu_ms_per_step"] = {"skipped": "the per-class pass needs --frames 39 or more (20 untimed steps, then at least one)"}
     with tempfile.TemporaryDirectory() as td:
         for name, frames, db in [("device_frames_no_db", dev, ""), ("host_frames_no_db", host, ""),
                                  ("host_frames_sqlite", host, os.path.join(td, "a.db")),
                                  ("device_frames_sqlite", dev, os.path.join(td, "b.db"))]:
-            core.generate_optical_flow_database(core.VideoInfo(w, h, 1, 12), lambda f: frames[f - 1], None, "", core.GFTTOptions(), fo)
+            core.generate_optical_flow_database(core.VideoInfo(w, h, 1, 12), lambda f: frames[f - 1], None, "", core.GFTTOptions(), fo, detection_mask=mask)
             c0 = core._async_write_counters()
             t0 = time.perf_counter()
-            st = core.generate_optical_flow_database(vi, lambda f: frames[f - 1], None, db, core.GFTTOptions(), fo)
+            st = core.generate_optical_flow_database(vi, lambda f: frames[f - 1], None, db, core.GFTTOptions(), fo, detection_mask=mask)
             dt = time.perf_counter() - t0
             c1 = core._async_write_counters()
             out[name] = {"fps": a.frames / dt, "fps_without_setup": a.frames / (dt - st.seconds_setup), "seconds_db": st.seconds_db,
@@ -54,6 +95,11 @@ def main():
                          "setup_ms": round(1e3 * st.seconds_setup, 1),
                          # page writes of the database file: handed to the worker threads / carried out by SQLite's own thread
                          "db_page_writes": {k: c1[k] - c0[k] for k in c1}}
+            if db:
+                import sqlite3
+                con = sqlite3.connect(db)
+                out[name]["mean_keypoints_per_frame"] = con.execute("select avg(rows) from keypoints").fetchone()[0]
+                con.close()
     print(json.dumps({"config": a.config, "frames": a.frames, **out}))
 
 
