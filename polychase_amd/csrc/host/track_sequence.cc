@@ -574,39 +574,10 @@ class FrameSolver {
                 break;
             }
         }
-        const BundleOptions& bo = opts_.bundle_opts;
-        const CameraIntrinsics::Bounds bounds = guess_.intrinsics.GetBounds();
-        pc_pnp_camera init;
-        init.q_xyzw[0] = guess_.pose.q.x;
-        init.q_xyzw[1] = guess_.pose.q.y;
-        init.q_xyzw[2] = guess_.pose.q.z;
-        init.q_xyzw[3] = guess_.pose.q.w;
-        for (int i = 0; i < 3; i++) init.t[i] = guess_.pose.t[i];
-        init.fx = guess_.intrinsics.fx;
-        init.fy = guess_.intrinsics.fy;
-        init.cx = guess_.intrinsics.cx;
-        init.cy = guess_.intrinsics.cy;
-        init.aspect_ratio = guess_.intrinsics.aspect_ratio;
-        init.convention_opencv = guess_.intrinsics.convention == CameraConvention::OpenCV ? 1 : 0;
-        pc_pnp_solve_options so;
-        so.max_iterations = static_cast<int>(bo.max_iterations);
-        so.initial_lambda = bo.initial_lambda;
-        so.min_lambda = bo.min_lambda;
-        so.max_lambda = bo.max_lambda;
-        so.gradient_tol = bo.gradient_tol;
-        so.step_tol = bo.step_tol;
-        so.loss_type = static_cast<int>(bo.loss_type);
-        so.loss_scale = bo.loss_scale;
-        so.optimize_focal_length = opts_.optimize_focal_length ? 1 : 0;        // "with more than 3 points" is decided on the device
-        so.optimize_principal_point = opts_.optimize_principal_point ? 1 : 0;
-        so.f_low = bounds.f_low;
-        so.f_high = bounds.f_high;
-        so.cx_low = bounds.cx_low;
-        so.cx_high = bounds.cx_high;
-        so.cy_low = bounds.cy_low;
-        so.cy_high = bounds.cy_high;
-        so.max_inlier_error = opts_.max_inlier_error;
-        so.rounds_hint = 0;
+        const pc_pnp_camera init = ToPnpCamera(guess_);
+        // "with more than 3 points" is decided on the device
+        const pc_pnp_solve_options so = ToPnpSolveOptions(opts_.bundle_opts, guess_.intrinsics.GetBounds(), opts_.optimize_focal_length,
+                                                          opts_.optimize_principal_point, opts_.max_inlier_error);
         GpuSection section;
         mesh_.SyncMask();   // the mask can be edited between frames through inner_mut(): the current bits (sent when they changed)
         if (pc_track_frame_launch_chained(s_.ctx, s_.set, mesh_.Gpu(), model_.data(), /*check_mask=*/1, sources_, n_sources_, chained_source,
@@ -648,25 +619,8 @@ class FrameSolver {
         if (sr.n_correspondences < 3) return std::nullopt;  // :95-97
         PnPResult result;
         result.camera = guess_;
-        CameraState& c = result.camera;
-        c.pose.q.x = sr.pnp.camera.q_xyzw[0];
-        c.pose.q.y = sr.pnp.camera.q_xyzw[1];
-        c.pose.q.z = sr.pnp.camera.q_xyzw[2];
-        c.pose.q.w = sr.pnp.camera.q_xyzw[3];
-        for (int i = 0; i < 3; i++) c.pose.t[i] = sr.pnp.camera.t[i];
-        c.intrinsics.fx = sr.pnp.camera.fx;
-        c.intrinsics.fy = sr.pnp.camera.fy;
-        c.intrinsics.cx = sr.pnp.camera.cx;
-        c.intrinsics.cy = sr.pnp.camera.cy;
-        BundleStats st;
-        st.iterations = static_cast<size_t>(sr.pnp.iterations);
-        st.invalid_steps = static_cast<size_t>(sr.pnp.invalid_steps);
-        st.initial_cost = sr.pnp.initial_cost;
-        st.cost = sr.pnp.cost;
-        st.lambda = sr.pnp.lambda;
-        st.step_norm = sr.pnp.step_norm;
-        st.grad_norm = sr.pnp.grad_norm;
-        result.bundle_stats = st;
+        FromPnpCamera(sr.pnp.camera, result.camera);
+        result.bundle_stats = ToBundleStats(sr.pnp);
         result.inlier_ratio = static_cast<Float>(sr.pnp.inliers) / static_cast<Float>(sr.n_correspondences);
         return result;
     }

@@ -1,8 +1,8 @@
 // trajectory_refiner.cc -- host side of "Refine Sequence".
 //   segment loading   : CachedDatabase (cpp/refiner.cc:18-197) flattened into the CSR arrays the GPU
 //                       problem wants (keypoints per frame, residuals per edge)
-//   LM driver         : LevMarqSparseSolver::Solve (cpp/pnp/lev_marq.h:503-601), Step
-//                       (cpp/refiner.cc:508-540, :659-690)
+//   LM driver         : LevMarqSparseSolver::Solve (cpp/pnp/lev_marq.h:503-601) = lm_loop.h over BandedProblem,
+//                       Step (cpp/refiner.cc:508-540, :659-690)
 //   linear algebra    : the frames of a segment only connect to frames at most `max |i-j|` apart, so
 //                       J^T J is block-banded; a banded Cholesky (fp64) replaces Eigen::SimplicialLLT
 //   residual sweeps   : on the GPU through pc_refine_* (kernels_refiner.hip), one workgroup per edge
@@ -27,6 +27,7 @@
 #include "band_matrix.h"
 #include "flow_database.h"
 #include "gpu_context.h"
+#include "lm_loop.h"
 #include "numa_pin.h"
 
 namespace {
@@ -321,22 +322,6 @@ void PackCameras(const CameraTrajectory& traj, std::vector<pc_refine_camera>& ou
     }
 }
 
-// RefinementProblemBase::Step (refiner.cc:508-540)
-void StepCamera(CameraState& state, const float* dp, bool opt_f, bool opt_pp, const CameraIntrinsics::Bounds& b) {
-    state.pose.q = QuatStepPost(state.pose.q, Vec3f{dp[0], dp[1], dp[2]});
-    state.pose.t = state.pose.t + Vec3f{dp[3], dp[4], dp[5]};
-    if (opt_f) {
-        state.intrinsics.fy = state.intrinsics.fy + dp[6];
-        state.intrinsics.fx = state.intrinsics.fy * state.intrinsics.aspect_ratio;
-        state.intrinsics.fy = std::clamp(state.intrinsics.fy, b.f_low, b.f_high);
-        state.intrinsics.fx = std::clamp(state.intrinsics.fx, b.f_low, b.f_high);
-    }
-    if (opt_pp) {
-        state.intrinsics.cx = std::clamp(state.intrinsics.cx + dp[7], b.cx_low, b.cx_high);
-        state.intrinsics.cy = std::clamp(state.intrinsics.cy + dp[8], b.cy_low, b.cy_high);
-    }
-}
-
 // The GPU-resident problem of one segment plus the host-side normal equations.
 class RefineSession {
    public:
@@ -482,6 +467,63 @@ class RefineSession {
     std::vector<double> edge_blocks_;
 };
 
+// LevMarqSparseSolver over GlobalRefinementProblem, as lm_loop.h wants it.  The reference runs its loop in fp32 (Float); costs,
+// the system and the step are fp64 here and rounded into BundleStats, the camera update itself stays fp32.
+template <class ReportFn>
+struct BandedProblem {
+    using Scalar = double;
+
+    RefineSession& session;
+    CameraTrajectory& traj;
+    const bool opt_f, opt_pp;
+    const CameraIntrinsics::Bounds bounds;
+    ReportFn report;  // callback_wrapper, refiner.cc:673-681
+    CameraTrajectory traj_new = traj;
+    BandMatrix damped = session.JtJ;
+    std::vector<double> step, JtJ_step;
+    std::vector<float> step_f;   // what the cameras are stepped by
+
+    double InitialCost() { return session.TotalCost(traj); }
+    double Linearize() {
+        session.BuildNormalEquations(traj);
+        return Norm(session.Jtr);
+    }
+    bool Factorize(Float lambda) {  // ComputeStep (:826-842): damp the clamped diagonal, factorise
+        damped = session.JtJ;
+        for (int i = 0; i < session.NumParams(); i++) {
+            damped.At(i, i) = session.diag[i] * (1.0 + lambda);
+            session.JtJ.At(i, i) = session.diag[i];
+        }
+        StageClock::Scope sc("refine/banded Cholesky");
+        return damped.Factorize();
+    }
+    double Solve() {
+        damped.Solve(session.Jtr, step);
+        for (double& x : step) x = -x;
+        step_f.assign(step.begin(), step.end());
+        return Norm(step);
+    }
+    double EvaluateCandidate() {
+        // GlobalRefinementProblem::Step (refiner.cc:618-646): the first and the last camera are constant
+        for (int32_t frame = traj.FirstFrame() + 1; frame <= traj.LastFrame() - 1; frame++) {
+            CameraState camera = *traj.Get(frame);
+            StepCamera(camera, &step_f[static_cast<size_t>(session.BlockLength()) * (frame - traj.FirstFrame())], opt_f, opt_pp, bounds);
+            traj_new.Set(frame, camera);
+        }
+        return session.TotalCost(traj_new);
+    }
+    double ExpectedChange() {
+        session.JtJ.Multiply(step, JtJ_step);
+        double expected = 0;
+        for (size_t i = 0; i < step.size(); i++) expected += step[i] * (2.0 * session.Jtr[i] + JtJ_step[i]);
+        return expected;
+    }
+    void Accept() {
+        for (int32_t frame = traj.FirstFrame() + 1; frame <= traj.LastFrame() - 1; frame++) traj.Set(frame, *traj_new.Get(frame));
+    }
+    bool Report(const BundleStats& stats) { return report(stats); }
+};
+
 }  // namespace
 
 void RefineTrajectory(const std::string& database_path, CameraTrajectory& traj, const Mat4f& model_matrix,
@@ -490,13 +532,7 @@ void RefineTrajectory(const std::string& database_path, CameraTrajectory& traj, 
     StageClock::Begin();
     numa::ScopedPin near_gpu(SharedGpuContext(), "refinement: calling thread");   // numa_pin.h
     RefineSession session(database_path, traj, model_matrix, mesh, optimize_focal_length, optimize_principal_point, opts);
-    const int B = session.BlockLength(), n_params = session.NumParams();
     const CameraIntrinsics::Bounds bounds = traj.Get(traj.FirstFrame())->intrinsics.GetBounds();  // refiner.cc:690
-    BandMatrix& JtJ = session.JtJ;
-    BandMatrix damped = JtJ;
-    std::vector<double>&Jtr = session.Jtr, &diag = session.diag;
-    std::vector<double> step(n_params), JtJ_step(n_params);
-    std::vector<float> step_f(n_params);
 
     RefineTrajectoryUpdate update;
     auto report = [&](const BundleStats& stats) {  // callback_wrapper, refiner.cc:673-681
@@ -509,89 +545,8 @@ void RefineTrajectory(const std::string& database_path, CameraTrajectory& traj, 
         return callback ? callback(update) : true;
     };
 
-    // ---- LevMarqSparseSolver::Solve (lev_marq.h:503-601) ----
-    // The reference runs this loop in fp32 (Float); costs, the system and the step are fp64 here and rounded into
-    // BundleStats, the camera update itself stays fp32.
-    BundleStats stats;
-    double cost = session.TotalCost(traj);
-    stats.cost = static_cast<Float>(cost);
-    stats.initial_cost = stats.cost;
-    stats.grad_norm = -1;
-    stats.step_norm = -1;
-    stats.invalid_steps = 0;
-    stats.lambda = opts.initial_lambda;
-
-    CameraTrajectory traj_new = traj;
-    Float v = 2.0f;
-    bool rebuild = true;
-    for (stats.iterations = 0; stats.iterations < opts.max_iterations; ++stats.iterations) {
-        if (rebuild) {
-            session.BuildNormalEquations(traj);
-            stats.grad_norm = static_cast<Float>(Norm(Jtr));
-            if (stats.grad_norm < opts.gradient_tol) break;
-        }
-        // ComputeStep (:826-842): damp the clamped diagonal, factorise, solve
-        damped = JtJ;
-        for (int i = 0; i < n_params; i++) {
-            damped.At(i, i) = diag[i] * (1.0 + stats.lambda);
-            JtJ.At(i, i) = diag[i];
-        }
-        bool factorized;
-        {
-            StageClock::Scope sc("refine/banded Cholesky");
-            factorized = damped.Factorize();
-        }
-        if (!factorized) {
-            stats.invalid_steps++;
-            if (stats.lambda == opts.max_lambda) break;
-            stats.lambda = std::min(opts.max_lambda, stats.lambda * v);
-            v = 2 * v;
-            rebuild = false;
-            continue;
-        }
-        damped.Solve(Jtr, step);
-        for (int i = 0; i < n_params; i++) {
-            step[i] = -step[i];
-            step_f[i] = static_cast<float>(step[i]);
-        }
-        stats.step_norm = static_cast<Float>(Norm(step));
-        if (stats.step_norm < opts.step_tol) break;
-
-        // GlobalRefinementProblem::Step (refiner.cc:618-646): the first and the last camera are constant
-        for (int32_t frame = traj.FirstFrame() + 1; frame <= traj.LastFrame() - 1; frame++) {
-            CameraState camera = *traj.Get(frame);
-            StepCamera(camera, &step_f[static_cast<size_t>(B) * (frame - traj.FirstFrame())], optimize_focal_length,
-                       optimize_principal_point, bounds);
-            traj_new.Set(frame, camera);
-        }
-        const double cost_new = session.TotalCost(traj_new);
-
-        if (cost_new < cost) {
-            const double actual = cost_new - cost;
-            JtJ.Multiply(step, JtJ_step);
-            double expected = 0;
-            for (int i = 0; i < n_params; i++) expected += step[i] * (2.0 * Jtr[i] + JtJ_step[i]);
-            const double rho = actual / expected;
-            if (rho > 0) {
-                const double factor = std::max(1.0 / 3.0, 1.0 - std::pow(2.0 * rho - 1.0, 3));
-                stats.lambda = std::clamp(static_cast<Float>(stats.lambda * factor), opts.min_lambda, opts.max_lambda);
-            }
-            for (int32_t frame = traj.FirstFrame() + 1; frame <= traj.LastFrame() - 1; frame++)
-                traj.Set(frame, *traj_new.Get(frame));
-            cost = cost_new;
-            stats.cost = static_cast<Float>(cost_new);
-            v = 2;
-            rebuild = true;
-        } else {
-            stats.invalid_steps++;
-            if (stats.lambda == opts.max_lambda) break;
-            stats.lambda = std::min(opts.max_lambda, stats.lambda * v);
-            v = 2 * v;
-            rebuild = false;
-        }
-        if (!report(stats)) break;
-    }
-    report(stats);
+    BandedProblem<decltype(report)&> banded{session, traj, optimize_focal_length, optimize_principal_point, bounds, report};
+    LevMarqLoop(opts, banded);  // LevMarqSparseSolver::Solve (lev_marq.h:503-601)
     session.ReportGpuTimes();
     StageClock::Report("RefineTrajectory");
 }

@@ -76,6 +76,23 @@ struct CameraState {
     Pose pose;
 };
 
+// PnPProblem::Step (pnp/pnp_problem.h:101-131) and RefinementProblemBase::Step (refiner.cc:508-540): one camera's
+// 9 (or 6: dp[6..8] are not read then) parameters forward by `dp`
+inline void StepCamera(CameraState& state, const float* dp, bool opt_f, bool opt_pp, const CameraIntrinsics::Bounds& b) {
+    state.pose.q = QuatStepPost(state.pose.q, Vec3f{dp[0], dp[1], dp[2]});
+    state.pose.t = state.pose.t + Vec3f{dp[3], dp[4], dp[5]};
+    if (opt_f) {
+        state.intrinsics.fy = state.intrinsics.fy + dp[6];
+        state.intrinsics.fx = state.intrinsics.fy * state.intrinsics.aspect_ratio;
+        state.intrinsics.fy = std::clamp(state.intrinsics.fy, b.f_low, b.f_high);
+        state.intrinsics.fx = std::clamp(state.intrinsics.fx, b.f_low, b.f_high);
+    }
+    if (opt_pp) {
+        state.intrinsics.cx = std::clamp(state.intrinsics.cx + dp[7], b.cx_low, b.cx_high);
+        state.intrinsics.cy = std::clamp(state.intrinsics.cy + dp[8], b.cy_low, b.cy_high);
+    }
+}
+
 struct BundleOptions {  // pnp/types.h:200-215
     size_t max_iterations = 100;
     size_t max_allowed_parallelism = 8;  // unused: the accumulation runs on the GPU

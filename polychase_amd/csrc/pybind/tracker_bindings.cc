@@ -5,6 +5,7 @@
 #include <pybind11/stl.h>
 
 #include "../host/band_matrix.h"
+#include "../host/lm_loop.h"
 #include "../host/pnp.h"
 #include "../host/ray_casting.h"
 #include "../host/refining_thread.h"
@@ -35,6 +36,59 @@ enum class TransformationType { Camera, Model };
 [[noreturn]] void NotInThisBuild(const char* what) {
     throw std::runtime_error(std::string(what) +
                              " is not part of the MI355X hot-path build (see DESIGN.md, out of scope / next)");
+}
+
+// A problem for LevMarqLoop (lm_loop.h) that computes nothing: every operation records its name and answers with the next value
+// of its script.  A script that runs out is an error, not a default.
+template <class T>
+struct ScriptedProblem {
+    using Scalar = T;
+    std::vector<double> costs, grad_norms, step_norms, expected_changes;
+    std::vector<bool> factorize_ok;
+    std::optional<size_t> stop_at;   // Report returns false at this iteration
+    size_t cost_i = 0, grad_i = 0, step_i = 0, expected_i = 0, factorize_i = 0;
+    std::vector<std::string> ops;
+    std::vector<Float> lambdas;      // what Factorize was called with
+    std::vector<size_t> reports;     // stats.iterations of every Report
+
+    template <class V>
+    static auto Next(const V& script, size_t& i, const char* what) {
+        if (i >= script.size()) throw std::runtime_error(std::string("the script ran out of ") + what);
+        return script[i++];
+    }
+    T InitialCost() { return ops.push_back("cost"), static_cast<T>(Next(costs, cost_i, "costs")); }
+    T Linearize() { return ops.push_back("linearize"), static_cast<T>(Next(grad_norms, grad_i, "gradient norms")); }
+    bool Factorize(Float lambda) {
+        ops.push_back("factorize");
+        lambdas.push_back(lambda);
+        return Next(factorize_ok, factorize_i, "factorisations");
+    }
+    T Solve() { return ops.push_back("solve"), static_cast<T>(Next(step_norms, step_i, "step norms")); }
+    T EvaluateCandidate() { return ops.push_back("evaluate"), static_cast<T>(Next(costs, cost_i, "costs")); }
+    T ExpectedChange() { return ops.push_back("expected"), static_cast<T>(Next(expected_changes, expected_i, "expected changes")); }
+    void Accept() { ops.push_back("accept"); }
+    bool Report(const BundleStats& stats) {
+        ops.push_back("report");
+        reports.push_back(stats.iterations);
+        return !(stop_at && stats.iterations == *stop_at);
+    }
+};
+
+template <class T>
+py::dict RunScriptedLoop(ScriptedProblem<T> problem, const BundleOptions& opts) {
+    const BundleStats st = LevMarqLoop(opts, problem);
+    py::dict d;
+    d["iterations"] = st.iterations;
+    d["invalid_steps"] = st.invalid_steps;
+    d["initial_cost"] = st.initial_cost;
+    d["cost"] = st.cost;
+    d["lambda"] = st.lambda;
+    d["step_norm"] = st.step_norm;
+    d["grad_norm"] = st.grad_norm;
+    d["ops"] = problem.ops;
+    d["lambdas"] = problem.lambdas;
+    d["reports"] = problem.reports;
+    return d;
 }
 
 }  // namespace
@@ -393,6 +447,22 @@ void BindTracker(py::module_& m) {
             return py::make_tuple(w, x);
         },
         py::arg("database_path"), py::arg("trajectory"), py::arg("model_matrix"), py::arg("frame"), py::arg("accel_mesh"));
+
+    // The host solvers' LM loop (lm_loop.h) over a scripted problem, in the scalar type of the dense ("float") or the
+    // banded ("double") solver: its control flow without a GPU (tests).
+    m.def(
+        "_lm_loop_script",
+        [](const std::string& scalar, std::vector<double> costs, std::vector<bool> factorize_ok, std::vector<double> grad_norms,
+           std::vector<double> step_norms, std::vector<double> expected_changes, std::optional<size_t> stop_at,
+           const BundleOptions& opts) {
+            if (scalar == "float")
+                return RunScriptedLoop(ScriptedProblem<float>{costs, grad_norms, step_norms, expected_changes, factorize_ok, stop_at}, opts);
+            if (scalar == "double")
+                return RunScriptedLoop(ScriptedProblem<double>{costs, grad_norms, step_norms, expected_changes, factorize_ok, stop_at}, opts);
+            throw py::value_error("scalar must be \"float\" or \"double\"");
+        },
+        py::arg("scalar"), py::arg("costs"), py::arg("factorize_ok"), py::arg("grad_norms"), py::arg("step_norms"),
+        py::arg("expected_changes"), py::arg("stop_at") = py::none(), py::arg("bundle_opts") = BundleOptions());
 
     // 9x9 lower Cholesky solve used by the LM step (known-answer test of
     // cpp/examples/levmarq_ill_conditioned_float32_issue.cpp)
