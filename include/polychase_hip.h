@@ -220,6 +220,29 @@ int pc_frame_detect(pc_context* ctx, pc_frame* f, const pc_gftt_options* opt);
  * frame until it is replaced or cleared (mask = NULL); a frame that never had one allocates nothing and runs the unmasked
  * kernels.  Null context or frame, or row_pitch < W: PC_E_INVALID. */
 int pc_frame_set_mask(pc_context* ctx, pc_frame* f, const uint8_t* mask, size_t row_pitch, int on_device);
+/* The same mask given as outlines and rasterised on the GPU (kernels_mask.hip), so that no plane crosses the bus: a list of
+ * n_polygons closed polygons (0..PC_MASK_MAX_POLYGONS), polygon k with counts[k] >= 3 vertices, PC_MASK_MAX_VERTICES in all;
+ * xy holds them one after another, (x, y) float32 in pixel coordinates: pixel (px, py) has its centre at (px, py).  A polygon
+ * closes from its last vertex to its first; it may lie partly or wholly outside the frame.  The fill rule is exact, in integers:
+ *   1. every coordinate is snapped to X = rint(x * PC_MASK_SUBPIXEL), round-half-to-even (on the host);
+ *   2. with P = (16 px, 16 py), an edge A -> B is crossed when (Ay <= Py) != (By <= Py); a crossed edge lies to the right of P
+ *      when d = (Bx - Ax)(Py - Ay) - (Px - Ax)(By - Ay) is > 0 for By > Ay, < 0 for By < Ay (64-bit integers);
+ *   3. a pixel is inside a polygon when an odd number of that polygon's edges are crossed to its right (even-odd), on when it
+ *      is inside at least one polygon (union), and `invert` flips the result.
+ * So an integer-cornered rectangle (x0, y0)-(x1, y1) turns on x0 <= px < x1, y0 <= py < y1; polygons that share an edge share
+ * no pixel; orientation does not matter; horizontal and zero-length edges never cross.  Holes are not expressible (a polygon
+ * inside another adds nothing to the union): pass a keyhole outline.  0 polygons: everything off (on with invert).
+ * The effect on the next pc_frame_detect is that of pc_frame_set_mask with the plane the rule gives; pc_frame_set_mask(NULL)
+ * clears it.  xy and counts are host memory, consumed before the call returns.  PC_E_INVALID, with the previous mask left in
+ * force: a null handle or array, n_polygons outside 0..PC_MASK_MAX_POLYGONS, a count below 3, more than PC_MASK_MAX_VERTICES
+ * vertices, a coordinate that is not finite or has |x| > 32768. */
+#define PC_MASK_MAX_POLYGONS 32
+#define PC_MASK_MAX_VERTICES 4096
+#define PC_MASK_SUBPIXEL     16
+int pc_frame_set_mask_polygons(pc_context* ctx, pc_frame* f, const float* xy, const int32_t* counts, int n_polygons, int invert);
+/* tests, debugging: the frame's current mask plane, w*h bytes (255 / 0 for a polygon mask, the caller's bytes for a byte
+ * mask); PC_E_STATE when the frame has no mask on */
+int pc_frame_download_mask(pc_context* ctx, const pc_frame* f, uint8_t* out);
 /* cv::cornerMinEigenVal map of the last pc_frame_detect (gftt.cc:35), w*h floats (tests). */
 int pc_frame_download_min_eig(pc_context* ctx, const pc_frame* f, float* out_eig);
 /* Number of local-maximum candidates of the last pc_frame_detect (gftt.cc:76-86) (tests). */
@@ -353,6 +376,12 @@ int pc_analyzer_set_fb_threshold(pc_analyzer* a, double fb_threshold);
  * take the mask.  The planes are allocated by the first call with a mask; an analyzer that never sees one allocates nothing
  * and enqueues what it always did.  pc_analyzer_reset clears the mask.  Null analyzer, or row_pitch < width: PC_E_INVALID. */
 int pc_analyzer_set_mask(pc_analyzer* a, const uint8_t* mask, size_t row_pitch, int on_device);
+/* As pc_analyzer_set_mask, the mask of the frames put from now on with will_detect != 0, given as polygons
+ * (pc_frame_set_mask_polygons: arguments, fill rule, refusals).  The snapped vertices go through a small page-locked ring to
+ * the device; each frame's plane is rasterised into its slot on the preparation stream when the frame is put, so the mask may
+ * change with every frame and nothing of the size of a plane crosses the bus.  The first call allocates the slots' planes and
+ * the vertex ring; later calls allocate nothing.  pc_analyzer_set_mask(a, NULL, ..) and pc_analyzer_reset clear it. */
+int pc_analyzer_set_mask_polygons(pc_analyzer* a, const float* xy, const int32_t* counts, int n_polygons, int invert);
 /* Wait for the oldest submitted job.  Pointers stay valid until the job slot is reused, i.e. for
  * the next max_jobs-1 submits. */
 int pc_analyzer_collect(pc_analyzer* a, pc_frame_result* out);

@@ -767,6 +767,8 @@ void pc_context_destroy(pc_context* c) {
         c->detect = nullptr;
     }
     c->sort_temp.release();
+    c->poly_host.release();
+    c->poly_dev.release();
     c->lk_rec[0].release();
     c->lk_rec[1].release();
     c->lk_cxy.release();
@@ -983,6 +985,45 @@ int pc_api::upload_mask(pc_frame* f, const uint8_t* mask, size_t row_pitch, int 
     return PC_OK;
 }
 
+static_assert(pc::kPolyMaxPolygons == PC_MASK_MAX_POLYGONS && pc::kPolyMaxVertices == PC_MASK_MAX_VERTICES, "kernels.hpp holds the header's limits");
+static_assert(pc::kPolyVertsAt > PC_MASK_MAX_POLYGONS, "the polygons' first vertices lie in front of the vertices");
+
+int pc_api::check_polygons(const float* xy, const int32_t* counts, int n_polygons, int* n_vertices) {
+    if (n_polygons < 0 || n_polygons > PC_MASK_MAX_POLYGONS) return fail(PC_E_INVALID, "%d polygons, 0..%d allowed", n_polygons, PC_MASK_MAX_POLYGONS);
+    if (n_polygons > 0 && (!xy || !counts)) return fail(PC_E_INVALID, "null argument");
+    int nv = 0;
+    for (int k = 0; k < n_polygons; k++) {
+        if (counts[k] < 3) return fail(PC_E_INVALID, "polygon %d has %d vertices, 3 needed", k, (int)counts[k]);
+        if (counts[k] > PC_MASK_MAX_VERTICES - nv) return fail(PC_E_INVALID, "more than %d vertices", PC_MASK_MAX_VERTICES);
+        nv += counts[k];
+    }
+    for (int i = 0; i < 2 * nv; i++)
+        if (!(std::fabs(xy[i]) <= 32768.0f)) return fail(PC_E_INVALID, "vertex %d: coordinate %g is not finite or beyond +-32768", i / 2, (double)xy[i]);
+    *n_vertices = nv;
+    return PC_OK;
+}
+
+size_t pc_api::snap_polygons(const float* xy, const int32_t* counts, int n_polygons, int32_t* out) {
+    int nv = 0;
+    for (int k = 0; k < n_polygons; k++) {
+        out[k] = nv;
+        nv += counts[k];
+    }
+    out[n_polygons] = nv;
+    // x * 16 is exact in float32; nearbyintf rounds halves to even (the default rounding mode)
+    for (int i = 0; i < 2 * nv; i++) out[pc::kPolyVertsAt + i] = (int32_t)std::nearbyintf(xy[i] * (float)PC_MASK_SUBPIXEL);
+    return (size_t)pc::kPolyVertsAt + 2 * (size_t)nv;
+}
+
+int pc_api::fill_mask_polygons(pc_frame* f, const int32_t* d_poly, int n_vertices, int n_polygons, int invert, hipStream_t s) {
+    int rc = ensure_mask_plane(f);
+    if (rc != PC_OK) return rc;
+    pc::launch_polygon_mask(d_poly, n_vertices, n_polygons, invert ? 1 : 0, f->d_mask, f->w, f->h, s);
+    PC_HIP(hipGetLastError());
+    f->mask_on = true;
+    return PC_OK;
+}
+
 // channels: 1 / 3 = u8 gray / RGB; elem_size 4 = float32 RGB(A) with `channels` floats per pixel
 int pc_api::detect_counter_words(const DetectScratch& d) { return d.counter_words; }
 
@@ -1109,6 +1150,32 @@ int pc_frame_set_mask(pc_context* ctx, pc_frame* f, const uint8_t* mask, size_t 
     int rc = upload_mask(f, mask, row_pitch, on_device, ctx->stream);
     if (rc != PC_OK) return rc;
     if (on_device != 1) PC_HIP(hipStreamSynchronize(ctx->stream));   // the caller may reuse its host buffer
+    return PC_OK;
+}
+
+int pc_frame_set_mask_polygons(pc_context* ctx, pc_frame* f, const float* xy, const int32_t* counts, int n_polygons, int invert) {
+    int nv = 0;
+    if (int rc = check_polygons(xy, counts, n_polygons, &nv)) return rc;   // first: the polygons are refused whatever the handles
+    if (!ctx || !f) return fail(PC_E_INVALID, "null argument");
+    if (f->ctx != ctx) return fail(PC_E_INVALID, "frame belongs to another context");
+    PC_HIP(hipSetDevice(ctx->device));
+    if (int jrc = join_prep(ctx)) return jrc;
+    PC_HIP(ctx->poly_host.ensure((size_t)pc::kPolyWords));
+    PC_HIP(ctx->poly_dev.ensure((size_t)pc::kPolyWords, true));
+    const size_t words = snap_polygons(xy, counts, n_polygons, ctx->poly_host.p);
+    PC_HIP(hipMemcpyAsync(ctx->poly_dev.p, ctx->poly_host.p, words * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    int rc = fill_mask_polygons(f, ctx->poly_dev.p, nv, n_polygons, invert, ctx->stream);
+    if (rc != PC_OK) return rc;
+    PC_HIP(hipStreamSynchronize(ctx->stream));   // the one staging buffer is free again
+    return PC_OK;
+}
+
+int pc_frame_download_mask(pc_context* ctx, const pc_frame* f, uint8_t* out) {
+    if (!ctx || !f || !out) return fail(PC_E_INVALID, "null argument");
+    if (!f->mask_on) return fail(PC_E_STATE, "the frame has no mask on");
+    if (int jrc = join_prep(ctx)) return jrc;
+    PC_HIP(hipMemcpyAsync(out, f->d_mask, (size_t)f->w * f->h, hipMemcpyDeviceToHost, ctx->stream));
+    PC_HIP(hipStreamSynchronize(ctx->stream));
     return PC_OK;
 }
 

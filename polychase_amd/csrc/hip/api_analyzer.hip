@@ -109,12 +109,20 @@ struct pc_analyzer {
     // the mask it was enqueued with.  A host mask is copied at once into one of kMaskGens pinned buffers, used in turn, so that
     // the per-frame copies into the slots never wait for the host; mask_copied[g]: the latest copy out of buffer g is complete.
     static constexpr int kMaskGens = 4;
-    int mask_kind = 0;                   // 0 none, 1 host (mask_host[mask_gen]), 2 device (mask_dev, mask_dev_pitch)
+    int mask_kind = 0;                   // 0 none, 1 host (mask_host[mask_gen]), 2 device (mask_dev, mask_dev_pitch), 3 polygons (poly_dev[poly_gen])
     int mask_gen = 0;
     PinBuf<uint8_t> mask_host[kMaskGens];
     hipEvent_t mask_copied[kMaskGens] = {};
     const uint8_t* mask_dev = nullptr;
     size_t mask_dev_pitch = 0;
+    // Polygon masks (pc_analyzer_set_mask_polygons): the snapped vertices are written into one of kMaskGens pinned buffers, used
+    // in turn, and copied on the preparation stream into that buffer's device twin, which the frames' rasteriser launches read
+    // on the same stream.  poly_read[g]: the latest copy out of poly_host[g] and the latest launch that read poly_dev[g] are
+    // complete -- the host waits for it before it writes poly_host[g] again, kMaskGens masks later.
+    int poly_gen = 0, poly_vertices = 0, poly_polygons = 0, poly_invert = 0;
+    PinBuf<int32_t> poly_host[kMaskGens];
+    DevBuf<int32_t> poly_dev[kMaskGens];
+    hipEvent_t poly_read[kMaskGens] = {};
     uint8_t* d_log = nullptr;            // optional device-resident record log
     size_t log_cap = 0, log_used = 0;
     std::vector<PinBuf<long long>> log_hdr;  // one pinned header per job slot
@@ -273,6 +281,10 @@ void pc_analyzer_destroy(pc_analyzer* a) {
     for (auto& m : a->mask_host) m.release();
     for (hipEvent_t e : a->mask_copied)
         if (e) (void)hipEventDestroy(e);
+    for (auto& m : a->poly_host) m.release();
+    for (auto& m : a->poly_dev) m.release();
+    for (hipEvent_t e : a->poly_read)
+        if (e) (void)hipEventDestroy(e);
     for (auto& j : a->jobs) {
         j.h_pack.release();
         if (j.done) (void)hipEventDestroy(j.done);
@@ -349,6 +361,11 @@ static int analyzer_put(pc_analyzer* a, int32_t frame_id, const uint8_t* rgb, si
         PC_HIP(hipEventRecord(a->mask_copied[g], a->ctx->prep_stream));
     } else if (will_detect && a->mask_kind == 2) {
         if ((rc = upload_mask(s.frame, a->mask_dev, a->mask_dev_pitch, 1, a->ctx->prep_stream)) != PC_OK) return rc;
+    } else if (will_detect && a->mask_kind == 3) {
+        const int g = a->poly_gen;
+        if ((rc = fill_mask_polygons(s.frame, a->poly_dev[g].p, a->poly_vertices, a->poly_polygons, a->poly_invert, a->ctx->prep_stream)) != PC_OK)
+            return rc;
+        PC_HIP(hipEventRecord(a->poly_read[g], a->ctx->prep_stream));
     }
     PC_HIP(hipEventRecord(s.img_ready, a->ctx->prep_stream));
     s.frame_id = frame_id;
@@ -613,6 +630,36 @@ int pc_analyzer_set_mask(pc_analyzer* a, const uint8_t* mask, size_t row_pitch, 
     for (int y = 0; y < a->h; y++) std::memcpy(a->mask_host[g].p + (size_t)y * a->w, mask + (size_t)y * row_pitch, (size_t)a->w);
     a->mask_gen = g;
     a->mask_kind = 1;
+    a->mask_dev = nullptr;
+    return PC_OK;
+}
+
+int pc_analyzer_set_mask_polygons(pc_analyzer* a, const float* xy, const int32_t* counts, int n_polygons, int invert) {
+    int nv = 0;
+    if (int rc = check_polygons(xy, counts, n_polygons, &nv)) return rc;   // first: the polygons are refused whatever the handle
+    if (!a) return fail(PC_E_INVALID, "null analyzer");
+    PC_HIP(hipSetDevice(a->ctx->device));
+    // every slot's plane and the whole vertex ring now: an allocation inside the running pipeline would stall it
+    for (auto& s : a->slots)
+        if (int rc = ensure_mask_plane(s.frame)) return rc;
+    for (int k = 0; k < pc_analyzer::kMaskGens; k++) {
+        PC_HIP(a->poly_host[k].ensure((size_t)pc::kPolyWords));
+        PC_HIP(a->poly_dev[k].ensure((size_t)pc::kPolyWords, true));
+        if (!a->poly_read[k]) PC_HIP(hipEventCreateWithFlags(&a->poly_read[k], hipEventDisableTiming));
+    }
+    const int g = (a->poly_gen + 1) % pc_analyzer::kMaskGens;
+    PC_HIP(hipEventSynchronize(a->poly_read[g]));   // what read this buffer, kMaskGens masks ago (a fresh event is complete)
+    const size_t words = snap_polygons(xy, counts, n_polygons, a->poly_host[g].p);
+    {
+        PrepScope prep(a->ctx);
+        PC_HIP(hipMemcpyAsync(a->poly_dev[g].p, a->poly_host[g].p, words * sizeof(int32_t), hipMemcpyHostToDevice, a->ctx->prep_stream));
+        PC_HIP(hipEventRecord(a->poly_read[g], a->ctx->prep_stream));
+    }
+    a->poly_gen = g;
+    a->poly_vertices = nv;
+    a->poly_polygons = n_polygons;
+    a->poly_invert = invert ? 1 : 0;
+    a->mask_kind = 3;
     a->mask_dev = nullptr;
     return PC_OK;
 }

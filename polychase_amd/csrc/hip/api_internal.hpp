@@ -91,5 +91,11 @@ int detect_counter_words(const DetectScratch& d);   // words of DetectScratch::c
 // (host or device memory, rows row_pitch apart) into it on stream `s`, stream-ordered, and switches the mask on
 int ensure_mask_plane(pc_frame* f);
 int upload_mask(pc_frame* f, const uint8_t* mask, size_t row_pitch, int on_device, hipStream_t s);
+// polygon mask (pc_frame_set_mask_polygons): check_polygons refuses what the header lists and returns the vertex count;
+// snap_polygons writes the checked polygons in the layout of pc::launch_polygon_mask (kernels.hpp) and returns the words used;
+// fill_mask_polygons rasterises that layout, now in device memory, into the frame's plane on stream `s` and switches the mask on
+int check_polygons(const float* xy, const int32_t* counts, int n_polygons, int* n_vertices);
+size_t snap_polygons(const float* xy, const int32_t* counts, int n_polygons, int32_t* out);
+int fill_mask_polygons(pc_frame* f, const int32_t* d_poly, int n_vertices, int n_polygons, int invert, hipStream_t s);
 
 }  // namespace pc_api

@@ -202,6 +202,9 @@ struct pc_context {
     struct DetectScratch* detect = nullptr;  // scratch of the stage-level pc_frame_detect
     DevBuf<uint8_t> sort_temp;
     const pc_frame* eig_owner = nullptr;
+    // pc_frame_set_mask_polygons: the snapped vertices on their way to the device (the call waits for the launch that reads them)
+    PinBuf<int32_t> poly_host;
+    DevBuf<int32_t> poly_dev;
     // LK scratch
     // raw LK outputs, compaction scratch and packed records: one set per job lane of the analyzer (set 0: stage-level calls)
     DevBuf<float4> lk_rec[2];              // raw records in visiting order (kernels.hpp LKParams::out_rec)

@@ -130,6 +130,17 @@ int suppress_large_grid_words(int w, int h, double min_distance);
 hipError_t sort_keys_desc(void* temp, size_t& temp_bytes, unsigned long long* keys_in,
                           unsigned long long* keys_out, uint32_t n, hipStream_t s);
 
+// ---- kernels_mask.hip ----
+// The detection mask's plane from polygon outlines (pc_frame_set_mask_polygons has the fill rule): `mask`, w x h packed bytes,
+// is written whole, 255 = on.  `poly` is one snapped polygon mask in device memory, kPolyWords words at most:
+// [0 .. n_polygons] the first vertex of each polygon and n_vertices at the end; from kPolyVertsAt on the vertices, (X, Y) in
+// sixteenths of a pixel, polygon after polygon.  n_polygons <= kPolyMaxPolygons (== PC_MASK_MAX_POLYGONS), every polygon
+// non-empty, n_vertices <= kPolyMaxVertices; 0 polygons: all off (all on with invert).
+constexpr int kPolyMaxPolygons = 32, kPolyMaxVertices = 4096;
+constexpr int kPolyVertsAt = 64;
+constexpr int kPolyWords = kPolyVertsAt + 2 * kPolyMaxVertices;
+void launch_polygon_mask(const int32_t* poly, int n_vertices, int n_polygons, int invert, uint8_t* mask, int w, int h, hipStream_t s);
+
 // ---- kernels_lk.hip ----
 constexpr int kMaxLevels = 16;   // == PC_MAX_LEVELS (internal.hpp asserts it)
 struct LKParams {

@@ -11,6 +11,7 @@
 #include <memory>
 #include <optional>
 #include <string>
+#include <vector>
 
 // ---- options -----------------------------------------------------------------------------------
 
@@ -68,7 +69,16 @@ struct FrameView {
 // rows x cols uint8, non-zero = keypoints may be detected here; the semantics are the reference's `mask` argument
 // (include/polychase_hip.h: pc_frame_set_mask), not a filter on the unmasked keypoints.  `data` is host memory (consumed when
 // the mask is handed to the engine) or HIP device memory of the GPU in use (on_device; `owner` keeps it alive while it is read).
+// Or outlines instead of bytes (`polygons` set; the other fields unused): closed polygons in pixel coordinates, rasterised on the
+// GPU by the exact fill rule of include/polychase_hip.h: pc_frame_set_mask_polygons -- a few hundred bytes per frame instead of a
+// plane, so a mask that moves with every frame keeps pace.  Holes are not expressible.
+struct PolygonMaskData {
+    std::vector<float> xy;          // x, y of every vertex, polygon after polygon
+    std::vector<int32_t> counts;    // vertices per polygon
+    bool invert = false;
+};
 struct MaskView {
+    std::shared_ptr<const PolygonMaskData> polygons;
     const uint8_t* data = nullptr;
     int rows = 0;
     int cols = 0;

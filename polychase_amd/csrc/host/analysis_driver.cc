@@ -351,6 +351,7 @@ static void RunAnalysis(const VideoInfo& video_info, FrameAccessorFunction frame
                         OpticalFlowRunStats* stats, OpticalFlowShard* shard, bool write_images, const DetectionMask& detection_mask) {
     CHECK(frame_accessor);
     auto check_mask = [&](const MaskView& m) {
+        if (m.polygons) return;   // any size of frame; the engine refuses bad polygons
         if (!m.data || m.rows != static_cast<int>(video_info.height) || m.cols != static_cast<int>(video_info.width) ||
             m.row_pitch < static_cast<size_t>(m.cols))
             throw std::invalid_argument("detection mask must be " + std::to_string(video_info.height) + " x " + std::to_string(video_info.width) +
@@ -432,6 +433,12 @@ static void RunAnalysis(const VideoInfo& video_info, FrameAccessorFunction frame
     // ... and so is the detection mask: the run's one mask, or none until the first frame's is asked for
     auto set_mask = [&](const std::optional<MaskView>& m) {
         if (m) check_mask(*m);
+        if (m && m->polygons) {
+            const PolygonMaskData& p = *m->polygons;
+            if (pc_analyzer_set_mask_polygons(eng.an, p.xy.data(), p.counts.data(), static_cast<int>(p.counts.size()), p.invert ? 1 : 0) != PC_OK)
+                ThrowHip("pc_analyzer_set_mask_polygons");
+            return;
+        }
         if (pc_analyzer_set_mask(eng.an, m ? m->data : nullptr, m ? m->row_pitch : 0, m && m->on_device ? 1 : 0) != PC_OK) ThrowHip("pc_analyzer_set_mask");
     };
     set_mask(detection_mask.fixed);

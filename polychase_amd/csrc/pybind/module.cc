@@ -5,7 +5,9 @@
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
 
+#include <cmath>
 #include <deque>
+#include <map>
 
 #include "../../../include/polychase_hip.h"
 #include "../host/debug_images.h"
@@ -116,22 +118,94 @@ MaskView MaskFromPython(const py::object& obj, const VideoInfo& video_info) {
     return v;
 }
 
-// detection_mask=None | array | callable(frame_id) -> array | None.  `obj` must outlive the run (the callable is called with
-// the GIL from the driver's thread).  allow_callable = false: OpticalFlowThread, whose protocol has no mask request.
+// polychase_core.PolygonMask(polygons, invert=False): a detection mask as closed polygons (csrc/host/analysis.h PolygonMaskData;
+// the fill rule: include/polychase_hip.h pc_frame_set_mask_polygons).  Everything the engine would refuse is a ValueError here,
+// at construction, before any GPU work.
+struct PolygonMaskPy {
+    std::shared_ptr<const PolygonMaskData> data;
+    py::tuple polygons;   // the float32 (K, 2) copies, read-only
+};
+
+PolygonMaskPy MakePolygonMask(const py::object& polygons, bool invert) {
+    if (polygons.is_none() || py::isinstance<py::str>(polygons) || !py::isinstance<py::sequence>(polygons))
+        throw py::value_error("PolygonMask takes a sequence of polygons, each an array of shape (K, 2)");
+    auto data = std::make_shared<PolygonMaskData>();
+    data->invert = invert;
+    py::list kept;
+    for (const py::handle& item : py::reinterpret_borrow<py::sequence>(polygons)) {
+        py::array raw;
+        try {
+            raw = py::array::ensure(item);
+        } catch (const py::error_already_set&) {
+            raw = py::array();
+        }
+        if (!raw || raw.ndim() != 2 || raw.shape(1) != 2) throw py::value_error("a polygon must be an array of shape (K, 2)");
+        const char kind = raw.dtype().kind();
+        if (kind != 'f' && kind != 'i' && kind != 'u') throw py::value_error("a polygon must hold numbers");
+        // a copy of our own, converted to float32 in C order
+        F32Array p = F32Array::ensure(py::module_::import("numpy").attr("array")(raw, py::arg("dtype") = "float32", py::arg("order") = "C"));
+        if (!p) throw py::value_error("a polygon must be convertible to float32");
+        if (p.shape(0) < 3) throw py::value_error("a polygon needs at least 3 vertices, got " + std::to_string(p.shape(0)));
+        if (data->counts.size() >= static_cast<size_t>(PC_MASK_MAX_POLYGONS))
+            throw py::value_error("more than " + std::to_string(PC_MASK_MAX_POLYGONS) + " polygons");
+        if (data->xy.size() / 2 + static_cast<size_t>(p.shape(0)) > static_cast<size_t>(PC_MASK_MAX_VERTICES))
+            throw py::value_error("more than " + std::to_string(PC_MASK_MAX_VERTICES) + " vertices");
+        const float* v = p.data();
+        for (py::ssize_t i = 0; i < p.size(); i++)
+            if (!(std::fabs(v[i]) <= 32768.0f)) throw py::value_error("a polygon's coordinates must be finite and within +-32768");
+        data->xy.insert(data->xy.end(), v, v + p.size());
+        data->counts.push_back(static_cast<int32_t>(p.shape(0)));
+        p.attr("setflags")(py::arg("write") = false);
+        kept.append(p);
+    }
+    return PolygonMaskPy{std::move(data), py::tuple(kept)};
+}
+
+// array | PolygonMask -> MaskView
+MaskView AnyMaskFromPython(const py::object& obj, const VideoInfo& video_info) {
+    if (py::isinstance<PolygonMaskPy>(obj)) {
+        MaskView v;
+        v.polygons = obj.cast<const PolygonMaskPy&>().data;
+        return v;
+    }
+    return MaskFromPython(obj, video_info);
+}
+
+// detection_mask=None | array | PolygonMask | callable(frame_id) -> array | PolygonMask | None | dict {frame_id: PolygonMask |
+// None} (copied here; a missing key = no mask for that frame; an array as a value is refused: a clip of planes does not belong
+// in a dictionary).  `obj` must outlive the run (the callable is called with the GIL from the driver's thread).
+// allow_callable = false: OpticalFlowThread, whose protocol has no mask request -- its per-frame masks come as a dict.
 DetectionMask DetectionMaskFromPython(const py::object& obj, const VideoInfo& video_info, bool allow_callable = true) {
     DetectionMask m;
     if (obj.is_none()) return m;
-    if (PyCallable_Check(obj.ptr())) {
-        if (!allow_callable) throw py::value_error("detection_mask must be a uint8 array of shape (H, W) or None");
+    if (py::isinstance<py::dict>(obj)) {
+        auto table = std::make_shared<std::map<int32_t, std::shared_ptr<const PolygonMaskData>>>();
+        for (const auto& kv : py::reinterpret_borrow<py::dict>(obj)) {
+            if (!py::isinstance<py::int_>(kv.first)) throw py::value_error("detection_mask: the keys of a dict are frame ids");
+            if (kv.second.is_none()) continue;
+            if (!py::isinstance<PolygonMaskPy>(kv.second)) throw py::value_error("detection_mask: the values of a dict are PolygonMask or None");
+            (*table)[kv.first.cast<int32_t>()] = kv.second.cast<const PolygonMaskPy&>().data;
+        }
+        m.per_frame = [table](int32_t frame_id) -> std::optional<MaskView> {
+            const auto it = table->find(frame_id);
+            if (it == table->end()) return std::nullopt;
+            MaskView v;
+            v.polygons = it->second;
+            return v;
+        };
+        return m;
+    }
+    if (!py::isinstance<PolygonMaskPy>(obj) && PyCallable_Check(obj.ptr())) {
+        if (!allow_callable) throw py::value_error("detection_mask must be a uint8 array of shape (H, W), a PolygonMask, a dict of them or None");
         m.per_frame = [&obj, video_info](int32_t frame_id) -> std::optional<MaskView> {
             py::gil_scoped_acquire gil;
             const py::object r = obj(frame_id);
             if (r.is_none()) return std::nullopt;
-            return MaskFromPython(r, video_info);
+            return AnyMaskFromPython(r, video_info);
         };
         return m;
     }
-    m.fixed = MaskFromPython(obj, video_info);
+    m.fixed = AnyMaskFromPython(obj, video_info);
     return m;
 }
 
@@ -426,6 +500,11 @@ PYBIND11_MODULE(polychase_core, m) {
         .def_readonly("seconds_submit", &OpticalFlowRunStats::seconds_submit)
         .def_readonly("seconds_collect", &OpticalFlowRunStats::seconds_collect)
         .def_readonly("seconds_writer_wait", &OpticalFlowRunStats::seconds_writer_wait);
+
+    py::class_<PolygonMaskPy>(m, "PolygonMask")   // not in the reference
+        .def(py::init(&MakePolygonMask), py::arg("polygons"), py::arg("invert") = false)
+        .def_property_readonly("polygons", [](const PolygonMaskPy& p) { return p.polygons; })
+        .def_property_readonly("invert", [](const PolygonMaskPy& p) { return p.data->invert; });
 
     py::class_<OpticalFlowThread>(m, "OpticalFlowThread")
         .def(py::init([](VideoInfo video_info, std::string database_path, GFTTOptions detector_options, OpticalFlowOptions flow_options,

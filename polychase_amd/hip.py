@@ -28,6 +28,7 @@ SYMBOLS = [
     "pc_frame_num_levels", "pc_frame_level_size", "pc_frame_download_gray", "pc_frame_download_level",
     "pc_frame_download_deriv", "pc_frame_detect", "pc_frame_download_min_eig", "pc_frame_num_candidates",
     "pc_frame_num_keypoints", "pc_frame_download_keypoints", "pc_frame_set_keypoints", "pc_frame_set_mask",
+    "pc_frame_set_mask_polygons", "pc_frame_download_mask", "pc_analyzer_set_mask_polygons",
     "pc_lk_track", "pc_lk_track_filtered", "pc_lk_track_fb", "pc_lk_track_filtered_fb",
     "pc_analyzer_create", "pc_analyzer_destroy", "pc_analyzer_reset", "pc_analyzer_put_frame", "pc_analyzer_put_frame_f32",
     "pc_analyzer_has_frame", "pc_analyzer_frame_ingested",
@@ -135,6 +136,8 @@ def load():
     L.pc_frame_download_deriv.argtypes = [vp, vp, C.c_int, vp]
     L.pc_frame_detect.argtypes = [vp, vp, C.POINTER(GfttOptions)]
     L.pc_frame_set_mask.argtypes = [vp, vp, vp, C.c_size_t, C.c_int]
+    L.pc_frame_set_mask_polygons.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int]
+    L.pc_frame_download_mask.argtypes = [vp, vp, vp]
     L.pc_frame_download_min_eig.argtypes = [vp, vp, vp]
     L.pc_frame_num_candidates.argtypes = [vp, vp, ip]
     L.pc_frame_num_keypoints.argtypes = [vp, vp, ip]
@@ -163,6 +166,7 @@ def load():
     L.pc_analyzer_set_host_records.argtypes = [vp, C.c_int]
     L.pc_analyzer_set_fb_threshold.argtypes = [vp, C.c_double]
     L.pc_analyzer_set_mask.argtypes = [vp, vp, C.c_size_t, C.c_int]
+    L.pc_analyzer_set_mask_polygons.argtypes = [vp, vp, vp, C.c_int, C.c_int]
     L.pc_peer_buffer_alloc.argtypes = [C.c_int, C.c_size_t, C.POINTER(vp)]
     L.pc_peer_buffer_free.argtypes = [C.c_int, vp]
     L.pc_peer_buffer_export.argtypes = [C.c_int, vp, C.c_char_p]
@@ -320,6 +324,20 @@ def _mask_ptr(mask, w: int, h: int):
     return mask, mask.data_ptr(), 1 if mask.is_cuda else 0, (mask.stride(0) if h > 1 else w)
 
 
+MASK_MAX_POLYGONS, MASK_MAX_VERTICES, MASK_SUBPIXEL = 32, 4096, 16   # PC_MASK_* of include/polychase_hip.h
+
+
+def _polygon_arrays(polys):
+    """polygons (a sequence of (K, 2) array-likes) -> (xy float32 (sum K, 2), counts int32): the arguments of
+    pc_frame_set_mask_polygons.  ValueError for a wrong shape; everything else is the library's to refuse."""
+    polys = [np.asarray(p, dtype=np.float32) for p in polys]
+    for p in polys:
+        if p.ndim != 2 or p.shape[1] != 2:
+            raise ValueError(f"a polygon must have shape (K, 2), got {p.shape}")
+    xy = np.ascontiguousarray(np.concatenate(polys, axis=0) if polys else np.zeros((0, 2), np.float32))
+    return xy, np.array([len(p) for p in polys], np.int32)
+
+
 def _is_float32(a) -> bool:
     return str(a.dtype) in ("float32", "torch.float32")
 
@@ -395,6 +413,19 @@ class Frame:
         keep, p, dev, pitch = _mask_ptr(mask, self.w, self.h)
         _check(load().pc_frame_set_mask(self.ctx._h, self._h, p, pitch, dev))
         self._keep_mask = keep if dev else None   # a device mask is read stream-ordered
+
+    def set_mask_polygons(self, polys, invert: bool = False):
+        """Detection mask of the next detect() as closed polygons, rasterised on the GPU (pc_frame_set_mask_polygons has the
+        fill rule): a sequence of (K, 2) float32 array-likes in pixel coordinates; [] = everything off (on with invert)."""
+        xy, counts = _polygon_arrays(polys)
+        _check(load().pc_frame_set_mask_polygons(self.ctx._h, self._h, xy.ctypes.data, counts.ctypes.data, len(counts), int(bool(invert))))
+        self._keep_mask = None
+
+    def mask(self) -> np.ndarray:
+        """The mask plane in force, uint8 (H, W) (pc_frame_download_mask); an error when the frame has no mask on."""
+        out = np.empty((self.h, self.w), np.uint8)
+        _check(load().pc_frame_download_mask(self.ctx._h, self._h, out.ctypes.data))
+        return out
 
     def detect(self, opt: GfttOptions | None = None):
         opt = opt or gftt_options()
@@ -594,6 +625,13 @@ class Analyzer:
         keep, p, dev, pitch = _mask_ptr(mask, self.w, self.h)
         _check(load().pc_analyzer_set_mask(self._h, p, pitch, dev))
         self._keep_mask = keep if dev else None
+
+    def set_mask_polygons(self, polys, invert: bool = False):
+        """The same as closed polygons, rasterised on the GPU when a frame is put (pc_analyzer_set_mask_polygons; arguments
+        as Frame.set_mask_polygons).  The vertices are consumed before the call returns."""
+        xy, counts = _polygon_arrays(polys)
+        _check(load().pc_analyzer_set_mask_polygons(self._h, xy.ctypes.data, counts.ctypes.data, len(counts), int(bool(invert))))
+        self._keep_mask = None
 
     @property
     def device_log_used(self) -> int:

@@ -2,12 +2,17 @@
 """End-to-end rates of GenerateOpticalFlowDatabase through the polychase_core module (what the Blender
 addon experiences), next to bench.py's HBM-resident number.  Not the headline metric.
 
-  python tools/e2e_bench.py [--config c2|c3] [--frames 60] [--mask-fraction F]
+  python tools/e2e_bench.py [--config c2|c3] [--frames 60] [--mask-fraction F [--mask-polygon] [--mask-outline N]]
 
 Modes: frames as torch CUDA tensors / host numpy arrays (PCIe upload included), with and without the
 SQLite insert.  --mask-fraction F: every run takes detection_mask = a centred rectangle of the frame's aspect covering F of
 its area (1.0: an all-on mask, the masked kernels with nothing masked out); the SQLite modes then also report the mean number
-of keypoints per frame.  "gpu_ms_per_step": per-class GPU time, launches and keypoints of a step (pc_context_get_timing: HIP
+of keypoints per frame.  --mask-polygon: the same rectangle as a 4-vertex PolygonMask with integer corners -- by the fill rule
+(include/polychase_hip.h: pc_frame_set_mask_polygons) the identical mask, so the keypoint counts must match the byte-mask run --
+rasterised on the GPU instead of uploaded.  --mask-outline N: instead of the rectangle an N-vertex ellipse of that area, as
+polygons with --mask-polygon and otherwise as the plane the rasteriser gives for it.  "mask_fill_ms_per_call": wall-clock of
+Frame.set_mask_polygons (vertex copy, rasteriser launch, wait), mean of 200 calls: an upper bound of the launch, which belongs
+to no timed kernel class.  "gpu_ms_per_step": per-class GPU time, launches and keypoints of a step (pc_context_get_timing: HIP
 events around every launch) from a pass of this tool's own context and analyzer over the same frames under the same mask --
 the driver's context cannot be read from here, and events around every launch slow the step, so the rates above come from
 untimed runs."""
@@ -22,14 +27,17 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
-def per_class_ms(w, h, ml, frames, mask, steps=40):
+def per_class_ms(w, h, ml, frames, mask, steps=40, polygons=None):
     """one pipelined pass (polychase_amd.pipeline.ClipAnalyzer) with every kernel class timed: 20 untimed steps, then `steps`"""
     from polychase_amd import hip
     from polychase_amd.pipeline import ClipAnalyzer
 
     ctx = hip.Context(0)
     an = ClipAnalyzer(ctx, w, h, 1, len(frames), lambda f: frames[f - 1], hip.gftt_options(), hip.flow_options(max_level=ml))
-    an.an.set_mask(mask)
+    if polygons is not None:
+        an.an.set_mask_polygons(polygons)
+    else:
+        an.an.set_mask(mask)
     steps = min(steps, len(frames) - 9 - 29)
     an.run(range(9, 29), None)
     ctx.synchronize()
@@ -50,6 +58,8 @@ def main():
     ap.add_argument("--config", default="c2")
     ap.add_argument("--frames", type=int, default=300)
     ap.add_argument("--mask-fraction", type=float, default=None)
+    ap.add_argument("--mask-polygon", action="store_true")
+    ap.add_argument("--mask-outline", type=int, default=0)
     a = ap.parse_args()
     import torch
     from polychase_amd import synth
@@ -70,11 +80,35 @@ def main():
         import numpy as np
         assert 0.0 < a.mask_fraction <= 1.0
         mw, mh = int(round(w * a.mask_fraction ** 0.5)), int(round(h * a.mask_fraction ** 0.5))
-        mask = np.zeros((h, w), np.uint8)
-        mask[(h - mh) // 2:(h - mh) // 2 + mh, (w - mw) // 2:(w - mw) // 2 + mw] = 255
+        from polychase_amd import hip
+        x0, y0 = (w - mw) // 2, (h - mh) // 2
+        polygons = [np.array([(x0, y0), (x0 + mw, y0), (x0 + mw, y0 + mh), (x0, y0 + mh)], np.float32)]
+        if a.mask_outline:
+            ang = 2 * np.pi * np.arange(a.mask_outline) / a.mask_outline
+            r = (a.mask_fraction / np.pi) ** 0.5       # an ellipse of the frame's aspect: pi (r w)(r h) = F w h
+            polygons = [np.stack([w / 2 + r * w * np.cos(ang), h / 2 + r * h * np.sin(ang)], axis=1).astype(np.float32)]
+        ctx = hip.Context(0)
+        fr = hip.Frame(ctx, w, h)
+        fr.set_mask_polygons(polygons)
+        mask = fr.mask()
+        t0 = time.perf_counter()
+        for _ in range(200):
+            fr.set_mask_polygons(polygons)
+        out["mask_fill_ms_per_call"] = 1e3 * (time.perf_counter() - t0) / 200
+        fr.close()
+        ctx.close()
+        if not a.mask_outline:
+            rect = np.zeros((h, w), np.uint8)
+            rect[y0:y0 + mh, x0:x0 + mw] = 255
+            assert np.array_equal(mask, rect), "the rasterised rectangle is the byte mask"
         out["mask_fraction"] = float(mask.mean() / 255.0)
+        out["mask_vertices"] = int(len(polygons[0]))
+        out["mask_polygon"] = bool(a.mask_polygon)
+        if a.mask_polygon:
+            mask = core.PolygonMask(polygons)
+    polygons = polygons if a.mask_polygon and a.mask_fraction is not None else None
     if a.frames >= 39:
-        out["gpu_ms_per_step"] = per_class_ms(w, h, ml, dev, mask)
+        out["gpu_ms_per_step"] = per_class_ms(w, h, ml, dev, mask, polygons=polygons)
     else:
         out["gpu_ms_per_step"] = {"skipped": "the per-class pass needs --frames 39 or more (20 untimed steps, then at least one)"}
     with tempfile.TemporaryDirectory() as td:
