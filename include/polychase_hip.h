@@ -95,9 +95,9 @@ int pc_context_pci_bus_id(pc_context* ctx, char* buf, int len);
  *   PC_ARITH_LK_X86_ORDER   the LK sums in fp32 in the order of LKTrackerInvoker's CV_SIMD128 path on x86 (four vector lanes
  *                           over the first (win / 8) * 8 columns, a scalar accumulator over the rest; calcOpticalFlowPyrLK,
  *                           cpp/opticalflow.cc:119-125): differs from the canonical order only where a window's partial
- *                           sums exceed 2^24 (step edges), by <= ~2e-3 px.  Windows 4-11 run the canonical integer data
+ *                           sums exceed 2^24 (step edges), by <= ~2e-3 px.  The kernels run the canonical integer data
  *                           path plus a proof that the fp32 sums are exact, and the x86 order itself where the proof fails
- *                           (+10-18 % on the LK launch); other windows run the generic kernel
+ *                           (+10-18 % on the LK launch at windows 4-10)
  *   PC_ARITH_SOBEL_FMA      the fused multiply-add of the AVX2-dispatched symmetric column filter of Sobel inside
  *                           cornerMinEigenVal (cpp/feature_detection/gftt.cc:35): same corners, the (value, address)
  *                           order of near-ties -- i.e. keypoint indices -- as a stock x86 build produces them; with

@@ -141,7 +141,7 @@ constexpr int kPolyVertsAt = 64;
 constexpr int kPolyWords = kPolyVertsAt + 2 * kPolyMaxVertices;
 void launch_polygon_mask(const int32_t* poly, int n_vertices, int n_polygons, int invert, uint8_t* mask, int w, int h, hipStream_t s);
 
-// ---- kernels_lk.hip ----
+// ---- kernels_lk.hip (launch_lk, the plain cross-check kernel, binning, gate, compaction), kernels_lk3.hip, kernels_lk4{a,b,c}.hip ----
 constexpr int kMaxLevels = 16;   // == PC_MAX_LEVELS (internal.hpp asserts it)
 struct LKParams {
     Level src[kMaxLevels];             // frame1 levels
@@ -152,7 +152,7 @@ struct LKParams {
     int n;                    // number of keypoints
     const float2* pts;
     const uint32_t* perm;     // visiting order (spatially binned keypoint indices) or null
-    int blocks_per_xcd;       // filled in by launch_lk
+    int blocks_per_xcd;       // filled in by launch_lk3 / launch_lk4*
     int max_iters;
     double eps_sq;
     float min_eig_thr;
@@ -169,7 +169,7 @@ struct LKParams {
     // the next launch fills the tail of this one -- and no more than the tail.  May be null.
     uint32_t* gate;
     uint32_t gate_value;
-    int x86_order;            // PC_ARITH_LK_X86_ORDER: fp32 lane sums in the order of OpenCV's SSE path (X86 = true in both kernels)
+    int x86_order;            // PC_ARITH_LK_X86_ORDER: fp32 lane sums in the order of OpenCV's SSE path (X86 = true in every kernel)
     // lk3, x86_order, diagnostics (or null): [0] iterations decided by the exactness proof, [1] iterations evaluated in the
     // x86 order, [2] (keypoint, level) pairs, [3] of those with the structure tensor evaluated in the x86 order
     unsigned long long* x86_stats;
@@ -182,10 +182,11 @@ __device__ __forceinline__ void lk_signal_dispatched(const LKParams& p) {
         __hip_atomic_store(p.gate, p.gate_value, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 constexpr int kRecStride = 8;   // records per slot (= PC_MAX_TARGETS)
-// K8-K10: pyramidal LK, one 16-lane DPP row per (keypoint, target).  Returns false if the window
-// size is unsupported.
+// K8-K10: pyramidal LK of every (keypoint, target) pair, windows 3 .. PC_MAX_WINDOW: launch_lk3 for windows 4..10, launch_lk4* for
+// the others; under POLYCHASE_LK_VARIANT=1 the plain kernel (lk_plain.hpp) for every window.  Returns false if the window size is
+// unsupported.
 bool launch_lk(const LKParams& p, int win, hipStream_t s);
-// two keypoints per wavefront on the uint16 planes, dword-per-position LDS regions (kernels_lk3.hip); windows 4..11 (launch_lk sends 11 to lk4)
+// two keypoints per wavefront on the uint16 planes, dword-per-position LDS regions (kernels_lk3.hip); windows 4..10
 bool launch_lk3(const LKParams& p, int win, hipStream_t s);
 // one keypoint per wavefront, 8 lanes per target, on the uint16 planes (lk4_kernel.hpp); windows 3 and 11..31, spread over
 // three translation units (kernels_lk4{a,b,c}.hip)

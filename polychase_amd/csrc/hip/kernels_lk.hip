@@ -1,397 +1,51 @@
-// kernels_lk.hip -- pyramidal Lucas-Kanade on gfx950 (K8-K10) + status compaction.
+// kernels_lk.hip -- what surrounds the pyramidal Lucas-Kanade launch (K8-K10) on gfx950: the dispatch to the LK kernels, the
+// plain cross-check kernel, the spatial binning of the keypoints, the gate between job lanes, status compaction and unpacking.
 //
-// Replaces cv::calcOpticalFlowPyrLK as called at reference cpp/opticalflow.cc:119-125 and the
-// status==1 filter of cpp/opticalflow.cc:130-147.  Arithmetic follows oracle/pc_oracle.c (which
-// restates OpenCV's LKTrackerInvoker): 14-bit fixed-point bilinear weights, int16 patches,
-// structure tensor / mismatch vector accumulated EXACTLY in integers, one rounding to fp32, 2x2
-// solve in fp32 without FMA contraction.
-//
-// Mapping (v3): one wavefront per keypoint, one group of 8 lanes per target (<= 8 targets).  The
-// I side (window patch, Scharr patch, structure tensor) does not depend on the target: the whole
-// wave stages and evaluates it ONCE per level and hands every group its pixels through LDS.  A
-// group owns the WIN x WIN window of its target (pixel p = lane + 8k).
-//   * Every gather goes through LDS: per pyramid level the group stages (a) the I window as
-//     "byte pairs" P[c] = (I[c], I[c+1]) and the raw Scharr window, (b) a (WIN+7) x (WIN+7..) search
-//     region of the target image J in the same pair format.  A lane owns a window COLUMN, so one
-//     pixel of one LK iteration is ONE aligned ds_read_u16 (the row below; the row above is the
-//     previous pixel's) -> the 4 bilinear taps in one dword, and two
-//     v_dot4_u32_u8 (the 14-bit weights are split w = 128*wh + wl so they fit u8 lanes).  The region
-//     is re-staged only when the window leaves it.
-//   * Window sums are all-reduced inside the group with DPP adds (quad_perm xor1/xor2 +
-//     row_half_mirror): no LDS traffic, no cross-group traffic, so every lane holds the same A, b,
-//     delta and the convergence branches are group-uniform.
-#include <algorithm>
+// The LK launch replaces cv::calcOpticalFlowPyrLK as called at reference cpp/opticalflow.cc:119-125 and the status==1 filter of
+// cpp/opticalflow.cc:130-147.  Arithmetic follows oracle/pc_oracle.c (which restates OpenCV's LKTrackerInvoker): 14-bit
+// fixed-point bilinear weights, int16 patches, structure tensor / mismatch vector accumulated EXACTLY in integers (or, under
+// PC_ARITH_LK_X86_ORDER, in the fp32 lane order of an x86 OpenCV build), one rounding to fp32, 2x2 solve in fp32 without FMA
+// contraction.  The product kernels are kernels_lk3.hip (windows 4..10) and lk4_kernel.hpp (window 3, windows 11..31).
 #include <cstdlib>
 
-#include "lk_common.hpp"
+#include "lk_plain.hpp"
 
 namespace pc {
 
-// One wavefront per keypoint; group g = lane / 8 tracks it into target g (v3).
-//
-// X86 = true: the sums of the structure tensor and of the mismatch vector in the ORDER an x86 OpenCV build executes them
-// (LKTrackerInvoker's CV_SIMD128 path: four fp32 lane accumulators over the first (WIN / 8) * 8 columns, a scalar fp32
-// accumulator over the rest, combined at the end) instead of exactly in integers -- PC_ARITH_LK_X86_ORDER, bit for bit
-// oracle/pc_oracle.c under PCO_EMU_LK_SIMD.  Where every partial sum stays below 2^24 the two orders agree; on step
-// edges they differ by up to ~2e-3 px.  The fp32 accumulations are sequential by definition,
-// so this mode runs on the generic kernel only and costs about 3x its iteration.
-template <int WIN, bool X86>
-__global__ __launch_bounds__(256) void lk_kernel(const LKParams p) {
-    using G = LKGeo<WIN>;
-    constexpr int GL = 8;
-    constexpr int NPX = WIN * WIN;
-    constexpr int K = (NPX + GL - 1) / GL;
-    constexpr int KW = (NPX + 63) / 64;  // pixels per lane in the cooperative (wave-wide) I-side pass
-    constexpr int SIMD_W = (WIN / 8) * 8;                      // columns the x86 path handles with vector lanes
-    constexpr int DIF_DW = X86 ? 8 * NPX : 0;                  // X86: every group's per-pixel differences of one iteration
-    __shared__ __attribute__((aligned(16))) uint32_t s_buf[4][G::WAVE_DW + DIF_DW];
-
+// The independent cross-check of the product kernels, every window 3 .. PC_MAX_WINDOW: one wavefront per keypoint (visiting order
+// p.perm), group g = lane / 8 tracks it into target g with plain_lk_pair (lk_plain.hpp) -- the template is evaluated per group,
+// nothing is shared across the wavefront, the target is gathered byte by byte.  A diagnostic, not a fast path.
+template <bool X86>
+__global__ __launch_bounds__(256) void lk_plain_kernel(const LKParams p, const int win) {
+    extern __shared__ __attribute__((aligned(16))) uint2 s_tmpl[];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int grp = lane >> 3, lg = lane & 7;
-    // Workgroup b runs on XCD b % 8 (observed dispatch order; speed only).  Keypoints are visited in
-    // spatially binned order (p.perm) and each XCD gets one contiguous eighth of that order, so the
-    // windows a private L2 sees belong to one image region.
     lk_signal_dispatched(p);
-    const int lb = (int)(blockIdx.x & 7u) * p.blocks_per_xcd + (int)(blockIdx.x >> 3);
-    const int slot = lb * 4 + wave;
-    if ((int)(blockIdx.x >> 3) >= p.blocks_per_xcd || slot >= p.n) return;  // whole waves exit together
-    const int feat = p.perm ? (int)p.perm[slot] : slot;
-    const bool tgt_active = grp < p.n_targets;
-    const int tgt = tgt_active ? grp : 0;
-
-    uint32_t* const wbase = &s_buf[wave][0];
-    uint8_t* const ibuf = reinterpret_cast<uint8_t*>(wbase);                       // I window, pair format
-    uint8_t* const dbuf = reinterpret_cast<uint8_t*>(wbase + G::I_DW);             // raw Scharr window
-    uint32_t* const xbuf = wbase + G::I_DW + G::D_DW;                              // (Ival, Dxy) exchange
-    uint8_t* const jbuf = reinterpret_cast<uint8_t*>(wbase + G::I_DW + G::D_DW + G::X_DW + grp * G::J_DW);
-    int32_t* const dif = reinterpret_cast<int32_t*>(wbase + G::WAVE_DW) + grp * NPX;   // X86 only
-
-    // Window pixels owned by this lane.  Main part: lane lg < WIN owns COLUMN lg (rows 0..WIN-1), so
-    // the bottom taps of row y are the top taps of row y+1 and one LDS read per pixel suffices.
-    // Extra part (WIN > 8): the remaining (WIN-8) columns are dealt out pixel by pixel.
-    constexpr int KM = WIN;                                            // main slots
-    constexpr int NEXTRA = (WIN > GL) ? (WIN - GL) * WIN : 0;          // pixels outside the first 8 columns
-    constexpr int KE = (NEXTRA + GL - 1) / GL;                         // extra slots per lane
-    static_assert(KM + KE == K || WIN < GL, "slot count");
-    const bool main_valid = lg < WIN;
-    int offE[KE > 0 ? KE : 1], qE[KE > 0 ? KE : 1];
-#pragma unroll
-    for (int e = 0; e < KE; e++) {
-        const int r = lg + GL * e;
-        const int col = GL + r / WIN, row = r - (r / WIN) * WIN;
-        const bool ok = r < NEXTRA;
-        offE[e] = ok ? row * G::PAIR_PITCH + 2 * col : 0;   // slots past the window read pixel 0, contribute 0
-        qE[e] = ok ? row * WIN + col : -1;
-    }
-
-    const float2 pt = p.pts[feat];
-    const float half_win = (float)(WIN - 1) * 0.5f;
-    const float FLT_SCALE = 1.f / (float)(1 << 20);
-    float nx = 0.f, ny = 0.f;
-    bool status = true;
-    float err = 0.f;
-
-    for (int level = p.max_level; level >= 0; --level) {
+    const int slot = (int)blockIdx.x * (int)(blockDim.x >> 6) + wave;
+    if (slot >= p.n || grp >= p.n_targets) return;   // whole groups
+    const float2 pt = p.pts[p.perm ? (int)p.perm[slot] : slot];
+    const auto level_of = [&](int level) {
         const Level L = p.src[level];
-        const uint8_t* __restrict__ J = p.tgt[tgt][level];
-        const int pitch = L.pitch;
-        const float lscale = 1.f / (float)(1 << level);
-        float px = pt.x * lscale, py = pt.y * lscale;
-        float qx, qy;
-        if (level == p.max_level) {
-            qx = px;
-            qy = py;
-        } else {
-            qx = nx * 2.f;
-            qy = ny * 2.f;
-        }
-        nx = qx;
-        ny = qy;
-
-        // ---- I side: identical for all targets -> computed once by the whole wave ----
-        px -= half_win;
-        py -= half_win;
-        const int ipx = (int)floorf(px), ipy = (int)floorf(py);
-        if (ipx < -WIN || ipx >= L.w || ipy < -WIN || ipy >= L.h) {   // wave-uniform
-            if (level == 0) {
-                status = false;
-                err = 0.f;
-            }
-            continue;
-        }
-        const Weights wI = bilinear_weights(px - (float)ipx, py - (float)ipy);
-        // signed 16-bit weight pairs for the derivative taps: (w00, w01) and (w10, w11)
-        const uint32_t wrow0 = wI.r0, wrow1 = wI.r1;
-
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        {
-            DerivWindow<WIN, 64> dw;
-            dw.load(L.der + (ptrdiff_t)(ipy * pitch + ipx), pitch, lane);
-            stage_pairs_auto<WIN, 64, WIN + 1>(L.img, pitch, L.h, ipx & ~3, ipy, ibuf, lane);
-            dw.store(reinterpret_cast<int32_t*>(dbuf), lane);
-        }
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        int sA11 = 0, sA12 = 0, sA22 = 0;
-        {
-            const uint8_t* ib = ibuf + 2 * (ipx & 3);
-#pragma unroll
-            for (int m = 0; m < KW; m++) {
-                const int q = lane + 64 * m;
-                if (q < NPX) {
-                    const int y = q / WIN, x = q - y * WIN;
-                    const uint16_t* qp = reinterpret_cast<const uint16_t*>(ib + y * G::PAIR_PITCH + 2 * x);
-                    const int ival = interp_pairs(widen_pair(qp[0]), widen_pair(qp[G::RWB]), wI);
-                    const uint32_t* d = reinterpret_cast<const uint32_t*>(dbuf) + y * G::D_PITCH + x;
-                    const uint32_t d00 = d[0], d01 = d[1], d10 = d[G::D_PITCH], d11 = d[G::D_PITCH + 1];
-                    // (dx00, dx01), (dx10, dx11), (dy00, dy01), (dy10, dy11)
-                    const uint32_t dx0 = __builtin_amdgcn_perm(d01, d00, 0x05040100u);
-                    const uint32_t dx1 = __builtin_amdgcn_perm(d11, d10, 0x05040100u);
-                    const uint32_t dy0 = __builtin_amdgcn_perm(d01, d00, 0x07060302u);
-                    const uint32_t dy1 = __builtin_amdgcn_perm(d11, d10, 0x07060302u);
-                    const int ix = sdot2(dx1, wrow1, sdot2(dx0, wrow0, 1 << (W_BITS - 1))) >> W_BITS;
-                    const int iy = sdot2(dy1, wrow1, sdot2(dy0, wrow0, 1 << (W_BITS - 1))) >> W_BITS;
-                    xbuf[2 * q] = (uint32_t)ival;
-                    xbuf[2 * q + 1] = (uint32_t)(ix & 0xffff) | ((uint32_t)iy << 16);
-                    sA11 += __mul24(ix, ix);   // |ix|, |iy| <= 4080
-                    sA12 += __mul24(ix, iy);
-                    sA22 += __mul24(iy, iy);
-                }
-            }
-        }
-        float A11, A12, A22;
-        if constexpr (X86) {
-            // lane j < 4: the vector lane that takes columns j, j + 4, ... < SIMD_W of every row, in row order;
-            // lane 4: the scalar accumulator over the remaining columns; then fA += q0 + q1 + q2 + q3
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-            float q11 = 0.f, q12 = 0.f, q22 = 0.f;
-            for (int y = 0; y < WIN; y++) {
-                if (lane < 4) {
-                    for (int x = lane; x < SIMD_W; x += 4) {
-                        const uint32_t d = xbuf[2 * (y * WIN + x) + 1];
-                        const float fx = (float)(int)(int16_t)(d & 0xffffu), fy = (float)((int)d >> 16);
-                        q22 = fy * fy + q22;
-                        q12 = fx * fy + q12;
-                        q11 = fx * fx + q11;
-                    }
-                } else if (lane == 4) {
-                    for (int x = SIMD_W; x < WIN; x++) {
-                        const uint32_t d = xbuf[2 * (y * WIN + x) + 1];
-                        const int ix = (int)(int16_t)(d & 0xffffu), iy = (int)d >> 16;
-                        q11 += (float)(ix * ix);
-                        q12 += (float)(ix * iy);
-                        q22 += (float)(iy * iy);
-                    }
-                }
-            }
-            auto combine = [](float q) {
-                const float s = ((__shfl(q, 0) + __shfl(q, 1)) + __shfl(q, 2)) + __shfl(q, 3);
-                return __shfl(q, 4) + s;
-            };
-            A11 = combine(q11) * FLT_SCALE;
-            A12 = combine(q12) * FLT_SCALE;
-            A22 = combine(q22) * FLT_SCALE;
-        } else {
-            // |ix|,|iy| <= 4080: per-lane partials fit int32; totals reduced as exact (hi, lo) halves
-            A11 = wave_exact_sum(sA11) * FLT_SCALE;
-            A12 = wave_exact_sum(sA12) * FLT_SCALE;
-            A22 = wave_exact_sum(sA22) * FLT_SCALE;
-        }
-        float D = A11 * A22 - A12 * A12;
-        const float tdiff = A11 - A22;
-        const float min_eig = (A22 + A11 - sqrtf(tdiff * tdiff + 4.f * A12 * A12)) / (float)(2 * WIN * WIN);
-        if (min_eig < p.min_eig_thr || D < 1.1920928955078125e-07f /* FLT_EPSILON */) {   // wave-uniform
-            if (level == 0) status = false;
-            continue;
-        }
-        D = 1.f / D;
-        if (!tgt_active) continue;  // idle groups only help with the I side
-
-        // every group picks up the pixels it owns
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        int Ival[KM + KE];  // ival_bias(I patch value): the accumulator init of interp_diff
-        int Dxy[KM + KE];  // (int16 ix) | (int16 iy << 16); 0 for slots without a pixel
-#pragma unroll
-        for (int k = 0; k < KM; k++) {
-            const uint2 v = main_valid ? *reinterpret_cast<const uint2*>(xbuf + 2 * (k * WIN + lg)) : make_uint2(0u, 0u);
-            Ival[k] = ival_bias((int)v.x);
-            Dxy[k] = (int)v.y;
-        }
-#pragma unroll
-        for (int e = 0; e < KE; e++) {
-            const uint2 v = (qE[e] >= 0) ? *reinterpret_cast<const uint2*>(xbuf + 2 * qE[e]) : make_uint2(0u, 0u);
-            Ival[KM + e] = ival_bias((int)v.x);
-            Dxy[KM + e] = (int)v.y;
-        }
-
-        // ---- iterations on the staged J region ----
-        qx -= half_win;
-        qy -= half_win;
-        float pdx = 0.f, pdy = 0.f;
-        int rx0 = 0, ry0 = 0;
-        bool staged = false;
-        for (int j = 0; j < p.max_iters; j++) {
-            const int iqx = (int)floorf(qx), iqy = (int)floorf(qy);
-            if (iqx < -WIN || iqx >= L.w || iqy < -WIN || iqy >= L.h) {
-                if (level == 0) status = false;
-                break;
-            }
-            if (!staged || iqx < rx0 || iqx + WIN > rx0 + G::RWB || iqy < ry0 || iqy + WIN + 1 > ry0 + G::RH) {
-                rx0 = (iqx - G::MX) & ~3;
-                ry0 = iqy - G::MY;
-                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-                stage_pairs_auto<WIN, GL, G::RH>(J, pitch, L.h, rx0, ry0, jbuf, lg);
-                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-                staged = true;
-            }
-            const Weights wJ = bilinear_weights(qx - (float)iqx, qy - (float)iqy);
-            const uint8_t* jb = jbuf + (iqy - ry0) * G::PAIR_PITCH + 2 * (iqx - rx0);
-            int sb1 = 0, sb2 = 0;  // per-lane partials: <= K * 8160 * 4080
-            // b1 += diff * ix, b2 += diff * iy: |diff| <= 8160 fits int16, (ix, iy) are the halves of Dxy
-            // (slots without a pixel have Dxy == 0)
-            {
-                const uint8_t* cb = jb + 2 * lg;
-                uint32_t top = widen_pair(*reinterpret_cast<const uint16_t*>(cb));
-#pragma unroll
-                for (int k = 0; k < KM; k++) {
-                    const uint32_t bot = widen_pair(*reinterpret_cast<const uint16_t*>(cb + (k + 1) * G::PAIR_PITCH));
-                    const int diff = interp_diff(top, bot, wJ, Ival[k]);
-                    top = bot;
-                    if constexpr (X86) {
-                        if (main_valid) dif[k * WIN + lg] = diff;
-                    } else {
-                        sb1 = mad16_lo(diff, (uint32_t)Dxy[k], sb1);
-                        sb2 = mad16_hi(diff, (uint32_t)Dxy[k], sb2);
-                    }
-                }
-#pragma unroll
-                for (int e = 0; e < KE; e++) {
-                    const uint16_t* q = reinterpret_cast<const uint16_t*>(jb + offE[e]);
-                    const int diff = interp_diff(widen_pair(q[0]), widen_pair(q[G::RWB]), wJ, Ival[KM + e]);
-                    if constexpr (X86) {
-                        if (qE[e] >= 0) dif[qE[e]] = diff;
-                    } else {
-                        sb1 = mad16_lo(diff, (uint32_t)Dxy[KM + e], sb1);
-                        sb2 = mad16_hi(diff, (uint32_t)Dxy[KM + e], sb2);
-                    }
-                }
-            }
-            float b1, b2;
-            if constexpr (X86) {
-                // per 8 columns the products of columns (c, c + 4) are added as int32 pairs (v_dotprod), converted to
-                // fp32 and accumulated row by row in vector lane c (lanes 0-3 of the group); the scalar accumulator
-                // (lane 4) takes the remaining columns; b = scalar + ((q[c=0] + q[c=2]) + (q[c=1] + q[c=3]))
-                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-                float q1 = 0.f, q2 = 0.f;
-                for (int y = 0; y < WIN; y++) {
-                    if (lg < 4) {
-                        for (int x0 = 0; x0 < SIMD_W; x0 += 8) {
-                            const int qa = y * WIN + x0 + lg, qb = qa + 4;
-                            const int da = dif[qa], db = dif[qb];
-                            const uint32_t ea = xbuf[2 * qa + 1], eb = xbuf[2 * qb + 1];
-                            const int p1 = da * (int)(int16_t)(ea & 0xffffu) + db * (int)(int16_t)(eb & 0xffffu);
-                            const int p2 = da * ((int)ea >> 16) + db * ((int)eb >> 16);
-                            q1 += (float)p1;
-                            q2 += (float)p2;
-                        }
-                    } else if (lg == 4) {
-                        for (int x = SIMD_W; x < WIN; x++) {
-                            const int qq = y * WIN + x;
-                            const int d = dif[qq];
-                            const uint32_t e2 = xbuf[2 * qq + 1];
-                            q1 += (float)(d * (int)(int16_t)(e2 & 0xffffu));
-                            q2 += (float)(d * ((int)e2 >> 16));
-                        }
-                    }
-                }
-                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");   // the differences are consumed: the next iteration may overwrite them
-                auto combine = [](float q) {
-                    const float v = (__shfl(q, 0, 8) + __shfl(q, 2, 8)) + (__shfl(q, 1, 8) + __shfl(q, 3, 8));
-                    return __shfl(q, 4, 8) + v;
-                };
-                b1 = combine(q1) * FLT_SCALE;
-                b2 = combine(q2) * FLT_SCALE;
-            } else if constexpr ((long long)K * 8160 * 4080 < (1ll << 29)) {
-                b1 = group8_exact_sum_small(sb1) * FLT_SCALE;
-                b2 = group8_exact_sum_small(sb2) * FLT_SCALE;
-            } else {
-                b1 = group_exact_sum<GL>(sb1) * FLT_SCALE;
-                b2 = group_exact_sum<GL>(sb2) * FLT_SCALE;
-            }
-            const float dx = (A12 * b2 - A22 * b1) * D;
-            const float dy = (A12 * b1 - A11 * b2) * D;
-            qx += dx;
-            qy += dy;
-            nx = qx + half_win;
-            ny = qy + half_win;
-            if ((double)dx * (double)dx + (double)dy * (double)dy <= p.eps_sq) break;
-            if (j > 0 && fabs((double)(dx + pdx)) < 0.01 && fabs((double)(dy + pdy)) < 0.01) {
-                nx -= dx * 0.5f;
-                ny -= dy * 0.5f;
-                break;
-            }
-            pdx = dx;
-            pdy = dy;
-        }
-
-        // ---- L1 patch error at level 0 ----
-        if (status && level == 0) {
-            const float ex = nx - half_win, ey = ny - half_win;
-            const int iex = (int)floorf(ex), iey = (int)floorf(ey);
-            if (iex < -WIN || iex >= L.w || iey < -WIN || iey >= L.h) {
-                status = false;
-                continue;
-            }
-            if (!staged || iex < rx0 || iex + WIN > rx0 + G::RWB || iey < ry0 || iey + WIN + 1 > ry0 + G::RH) {
-                rx0 = (iex - G::MX) & ~3;
-                ry0 = iey - G::MY;
-                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-                stage_pairs_auto<WIN, GL, G::RH>(J, pitch, L.h, rx0, ry0, jbuf, lg);
-                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-                staged = true;
-            }
-            const Weights wE = bilinear_weights(ex - (float)iex, ey - (float)iey);
-            const uint8_t* jb = jbuf + (iey - ry0) * G::PAIR_PITCH + 2 * (iex - rx0);
-            int se = 0;
-            {
-                const uint8_t* cb = jb + 2 * lg;
-                uint32_t top = widen_pair(*reinterpret_cast<const uint16_t*>(cb));
-#pragma unroll
-                for (int k = 0; k < KM; k++) {
-                    const uint32_t bot = widen_pair(*reinterpret_cast<const uint16_t*>(cb + (k + 1) * G::PAIR_PITCH));
-                    const int diff = interp_diff(top, bot, wE, Ival[k]);
-                    top = bot;
-                    se += main_valid ? (diff < 0 ? -diff : diff) : 0;
-                }
-#pragma unroll
-                for (int e = 0; e < KE; e++) {
-                    const uint16_t* q = reinterpret_cast<const uint16_t*>(jb + offE[e]);
-                    const int diff = interp_diff(widen_pair(q[0]), widen_pair(q[G::RWB]), wE, Ival[KM + e]);
-                    se += (qE[e] >= 0) ? (diff < 0 ? -diff : diff) : 0;
-                }
-            }
-            se = group_allreduce_add<GL>(se);  // <= 256 * 8160 < 2^24: exact in fp32 too
-            err = ((float)se * 1.f) / (float)(32 * WIN * WIN);
-        }
-    }
-
+        return PlainLKLevel{L.w, L.h, L.pitch, L.img, L.der, p.tgt[grp][level]};
+    };
+    const PlainLKResult r = plain_lk_pair<X86, true>(level_of, pt.x, pt.y, win, lg, p.max_level, p.max_iters, p.eps_sq, p.min_eig_thr,
+                                                     s_tmpl + (size_t)(wave * 8 + grp) * (win * win));
     // one 16-byte record per (slot, target): the wavefront's results are contiguous
-    if (lg == 0 && tgt_active)
-        p.out_rec[(size_t)slot * kRecStride + tgt] = make_float4(nx, ny, status ? err : 0.f, __uint_as_float(status ? 1u : 0u));
+    if (lg == 0) p.out_rec[(size_t)slot * kRecStride + grp] = make_float4(r.nx, r.ny, r.err, __uint_as_float(r.status ? 1u : 0u));
 }
 
-template <int WIN>
-static void launch_lk_t(const LKParams& p0, hipStream_t s) {
-    LKParams p = p0;
-    const int blocks = (p.n + 3) / 4;   // one wavefront per keypoint, 4 per workgroup
-    if (blocks == 0) return;
-    p.blocks_per_xcd = (blocks + 7) / 8;
-    if (p.x86_order) hipLaunchKernelGGL((lk_kernel<WIN, true>), dim3((unsigned)p.blocks_per_xcd * 8u), dim3(256), 0, s, p);
-    else hipLaunchKernelGGL((lk_kernel<WIN, false>), dim3((unsigned)p.blocks_per_xcd * 8u), dim3(256), 0, s, p);
+static bool launch_lk_plain(const LKParams& p, int win, hipStream_t s) {
+    if (win < 3 || win > PC_MAX_WINDOW) return false;
+    if (p.n <= 0) return true;
+    const PlainLKLaunch g = plain_lk_launch(p.n, win);
+    if (p.x86_order) hipLaunchKernelGGL((lk_plain_kernel<true>), dim3(g.blocks), dim3(64 * g.waves), g.lds_bytes, s, p, win);
+    else hipLaunchKernelGGL((lk_plain_kernel<false>), dim3(g.blocks), dim3(64 * g.waves), g.lds_bytes, s, p, win);
+    return true;
 }
 
-// POLYCHASE_LK_VARIANT=1 forces the generic one-keypoint-per-wavefront kernel of this file (windows up to 16: the cross-check of
-// the two product kernels; round 1's two-keypoint kernel on the u8 planes, kernels_lk2.hip, was removed in round 3 after its last
-// measurement: profiles/r03_c2_lk_variants.jsonl);
+// POLYCHASE_LK_VARIANT=1 sends every window to the plain kernel above (the cross-check of the two product kernels; round 1's
+// two-keypoint kernel on the u8 planes, kernels_lk2.hip, was removed in round 3 after its last measurement:
+// profiles/r03_c2_lk_variants.jsonl);
 // default: the two-keypoint kernel on the uint16 planes (kernels_lk3.hip) for windows 4..10, the eight-lanes-per-target kernel
 // (lk4_kernel.hpp) for window 3 and windows 11..31
 static int lk_variant() {
@@ -403,19 +57,8 @@ static int lk_variant() {
 }
 
 bool launch_lk(const LKParams& p, int win, hipStream_t s) {
-    const int v = lk_variant();
-    // window 11: the eight-lanes-per-target kernel (0.43 ms per C2 launch against 0.62 on the two-keypoint kernel, whose 11-px
-    // instance has no registers left for its unrolled ordered tensor and read-ahead; POLYCHASE_LK_VARIANT=3 keeps it reachable)
-    if (v == 0 && win == 11 && launch_lk4a(p, win, s)) return true;
-    if ((v == 0 || v == 3) && launch_lk3(p, win, s)) return true;
-    if ((v != 1 || win > 16) && (launch_lk4a(p, win, s) || launch_lk4b(p, win, s) || launch_lk4c(p, win, s))) return true;
-    switch (win) {
-#define PC_LK_CASE(W) case W: launch_lk_t<W>(p, s); return true;
-        PC_LK_CASE(3) PC_LK_CASE(4) PC_LK_CASE(5) PC_LK_CASE(6) PC_LK_CASE(7) PC_LK_CASE(8) PC_LK_CASE(9)
-        PC_LK_CASE(10) PC_LK_CASE(11) PC_LK_CASE(12) PC_LK_CASE(13) PC_LK_CASE(14) PC_LK_CASE(15) PC_LK_CASE(16)
-#undef PC_LK_CASE
-        default: return false;
-    }
+    if (lk_variant() == 1) return launch_lk_plain(p, win, s);
+    return launch_lk3(p, win, s) || launch_lk4a(p, win, s) || launch_lk4b(p, win, s) || launch_lk4c(p, win, s);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -1,6 +1,6 @@
 // kernels_lk3.hip -- pyramidal Lucas-Kanade (K8-K10), two keypoints per wavefront, on the uint16 planes.
 //
-// Same arithmetic and results as kernels_lk.hip (bit for bit; both follow oracle/pc_oracle.c,
+// Same arithmetic and results as the plain kernel (lk_plain.hpp; bit for bit: both follow oracle/pc_oracle.c,
 // which restates cv::calcOpticalFlowPyrLK as called at reference cpp/opticalflow.cc:119-125), same mapping as
 // round 1's lk2 kernel -- lanes 0-31 track keypoint A, lanes 32-63 keypoint B, group g = 4 lanes tracks the keypoint into target
 // g, the I side is evaluated once per keypoint by its half-wave -- but another data path for the inner loop:
@@ -495,10 +495,8 @@ __device__ __forceinline__ void x86_structure_tensor(uint32_t* wbase, const uint
         const float* src = pa + k * NPX + c * X::CL;
         float acc = 0.f;
         // all LDS reads of the chain in flight, then the additions (unrolled by four the loop sat out an LDS latency per batch:
-        // ~0.7 iteration-equivalents per ordered tensor); the 11-px window has no registers for that (it would drop to two
-        // wavefronts per SIMD)
-        constexpr int kUnroll = WIN <= 10 ? MAXL : 4;
-#pragma unroll kUnroll
+        // ~0.7 iteration-equivalents per ordered tensor)
+#pragma unroll
         for (int i = 0; i < MAXL; i++) {
             const float v = src[i < len ? i : 0];
             acc = i < len ? v + acc : acc;
@@ -546,13 +544,12 @@ __global__ __launch_bounds__(64) void lk3_kernel(const LKParams p) {
     const int tgt = grp < p.n_targets ? grp : 0;
 
     uint32_t* const wbase = &s_buf[wave][0];
-    uint32_t* const ibuf = wbase + half * G::HALF_I_DW;                          // I window, position dwords
-    int32_t* const dbuf = reinterpret_cast<int32_t*>(ibuf + G::I_DW);            // raw Scharr window
-    uint32_t* const xbuf = ibuf + G::I_DW + G::D_DW;                             // (bias, Dxy) exchange
+    // wbase + half * G::HALF_I_DW: this half's I window (position dwords), behind it the raw Scharr window (+ G::I_DW) and the
+    // (bias, Dxy) exchange (+ G::I_DW + G::D_DW); they are addressed through the evaluating lane's pointers (ibuf_o ... below)
     uint32_t* const jbuf = wbase + (half * 8 + grp) * G::J_DW;                   // aliases the above
 
     // the lane's run of the columns that do not fill a chain (column-major order of those pixels)
-    int e_off = 0, e_len = 0, e_q0 = 0;          // RUNS: first top position (dwords from the window origin), length, pixel index
+    int e_off = 0, e_len = 0;                    // RUNS: first top position (dwords from the window origin), length
     int offE[KE > 0 ? KE : 1], qE[KE > 0 ? KE : 1];
     if constexpr (KE > 0) {
         if constexpr (G::RUNS) {
@@ -560,7 +557,6 @@ __global__ __launch_bounds__(64) void lk3_kernel(const LKParams p) {
             e_len = max(0, min(KE, G::NEXTRA - e0));
             const int col = G::WM + (e_len > 0 ? e0 / WIN : 0), row0 = e_len > 0 ? e0 % WIN : 0;
             e_off = row0 * G::PITCH + col;
-            e_q0 = row0 * WIN + col;
         } else {
 #pragma unroll
             for (int e = 0; e < KE; e++) {
@@ -1125,7 +1121,7 @@ bool launch_lk3(const LKParams& p, int win, hipStream_t s) {
     if (!p.src[0].img16) return false;
     switch (win) {
 #define PC_LK_CASE(W) case W: launch_lk3_t<W>(p, s); return true;
-        PC_LK_CASE(4) PC_LK_CASE(5) PC_LK_CASE(6) PC_LK_CASE(7) PC_LK_CASE(8) PC_LK_CASE(9) PC_LK_CASE(10) PC_LK_CASE(11)
+        PC_LK_CASE(4) PC_LK_CASE(5) PC_LK_CASE(6) PC_LK_CASE(7) PC_LK_CASE(8) PC_LK_CASE(9) PC_LK_CASE(10)
 #undef PC_LK_CASE
         default: return false;
     }

@@ -1,7 +1,7 @@
 // lk4_kernel.hpp -- pyramidal Lucas-Kanade (K8-K10) for the windows the two-keypoint kernel does not take: one keypoint per
 // wavefront, EIGHT lanes per target, on the uint16 planes.  Windows 3 and 11 .. PC_MAX_WINDOW (31).
 //
-// Same arithmetic and results as kernels_lk.hip / kernels_lk3.hip (bit for bit; all follow oracle/pc_oracle.c, which restates
+// Same arithmetic and results as lk_plain.hpp / kernels_lk3.hip (bit for bit; all follow oracle/pc_oracle.c, which restates
 // cv::calcOpticalFlowPyrLK as called at reference cpp/opticalflow.cc:119-125 -- OpticalFlowOptions.window_size is a free
 // read-write attribute there, cpp/opticalflow.h:27-33, and OpenCV's own default is 21).
 //

@@ -1,6 +1,6 @@
 """GPU: every execution-strategy knob of the library must leave the flow database unchanged.
 
-The knobs select kernels (LK variants 1/2/3, fused / unfused pyramid), the detection path (device-count bucket sort / the
+The knobs select kernels (LK variant 1: the plain cross-check kernel; fused / unfused pyramid), the detection path (device-count bucket sort / the
 synchronous slow path with the rocPRIM sort) and the stream layout of the analyzer (gate between the job lanes, detection
 on its own stream(s), the helper kernels' issue priority, the copy stream of host frames, one job lane, the parked engine).  They are read when the library or a context is created, so each variant runs in its own process
 (tests/_analyze_hash.py: polychase_core.generate_optical_flow_database on a 26-frame clip -> sha256 of all rows)."""

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """pmc_collect.py -- hardware counters of one kernel, averaged per dispatch (run ON the GPU box).
 
-    python tools/pmc_collect.py [--kernel lk_kernel] [--config c2] [--out gpurun_out/pmc.json] GROUP [GROUP ...]
+    python tools/pmc_collect.py [--kernel lk3_kernel] [--config c2] [--out FILE] GROUP [GROUP ...]
 
 Each GROUP is a comma-separated list of counters collected in its own rocprofv3 pass
 (`rocprofv3 --pmc ... --kernel-trace` is NOT combined with any other trace domain).
@@ -21,7 +21,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--kernel", default="lk_kernel")
+    ap.add_argument("--kernel", default="lk3_kernel")
     ap.add_argument("--config", default="c2")
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--out", default=os.path.join(ROOT, "gpurun_out", "pmc.json"))

@@ -3,7 +3,7 @@
 and what ran in between.   usage: timeline_gaps.py <kernel_trace.csv> [kernel-substring]"""
 import csv, sys
 rows = list(csv.DictReader(open(sys.argv[1])))
-key = sys.argv[2] if len(sys.argv) > 2 else "lk_kernel"
+key = sys.argv[2] if len(sys.argv) > 2 else "lk3_kernel"
 rows.sort(key=lambda r: int(r["Start_Timestamp"]))
 lk = [r for r in rows if key in r["Kernel_Name"]]
 lk = lk[len(lk) // 4:]           # skip warm-up
