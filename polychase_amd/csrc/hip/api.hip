@@ -151,30 +151,30 @@ int validate_gftt(const pc_gftt_options* opt, int w, int h, pc::GfttGrid* g) {
     return PC_OK;
 }
 
-// the detector's default response (block 3, Sobel 3, min-eig): the tiled kernel
-static bool tiled_response(const pc_gftt_options& opt) {
-    // POLYCHASE_GFTT_GENERAL=1: the general kernels for the default options too (cross-check of the tiled kernel)
+// the detector's default response (block 3, Sobel 3, min-eig): the fused register kernel
+static bool default_response(const pc_gftt_options& opt) {
+    // POLYCHASE_GFTT_GENERAL=1: the general kernels for the default options too (cross-check of the fused kernel)
     static const bool force_general = getenv("POLYCHASE_GFTT_GENERAL") && atoi(getenv("POLYCHASE_GFTT_GENERAL")) == 1;
     return opt.block_size == 3 && opt.gradient_size == 3 && !opt.use_harris && !force_general;
 }
 
-// The fused chain for the detector's default (tiled response, table-driven suppression): NMS -> rank sort ->
+// The fused chain for the detector's default (default response, table-driven suppression): NMS -> rank sort ->
 // suppression with its own ordered compaction -> visiting order, four launches after the response map where the
 // general chain has six (bucket scatter and compaction folded into their neighbours).
 static bool fused_detection(const pc_gftt_options& opt) {
-    return tiled_response(opt) && opt.min_distance >= 1 && !(opt.min_distance > pc::kSuppressMaxTableRadius);
+    return default_response(opt) && opt.min_distance >= 1 && !(opt.min_distance > pc::kSuppressMaxTableRadius);
 }
 
 // the frame's detection mask plane, or null: the unmasked kernels
 static const uint8_t* frame_mask(const pc_frame* f) { return f->mask_on ? f->d_mask : nullptr; }
 
-// cornerMinEigenVal / cornerHarris of the frame (gftt.cc:31-36) + per-cell maxima: the tiled kernel for the detector's
+// cornerMinEigenVal / cornerHarris of the frame (gftt.cc:31-36) + per-cell maxima: the fused register kernel for the detector's
 // default, the general pair of kernels otherwise (their covariance scratch is allocated on first use: not the addon's path)
 static int corner_response(pc_context* ctx, const pc_frame* f, DetectScratch& d, const pc::GfttGrid& grid, const pc_gftt_options& opt,
                            uint32_t* cell_max) {
     const int fma = ((ctx->arith & PC_ARITH_SOBEL_FMA) ? 1 : 0) | ((ctx->arith & PC_ARITH_SOBEL_ROW_FMA) ? 2 : 0);
     const uint8_t* const mask = frame_mask(f);
-    if (tiled_response(opt)) {
+    if (default_response(opt)) {
         pc::launch_min_eig(f->levels[0], d.eig.p, grid, cell_max, fma, ctx->work, mask);
         return PC_OK;
     }
@@ -390,8 +390,7 @@ int detect_finish(pc_context* ctx, pc_frame* f, const pc::GfttGrid& grid, const 
 // order `stream` after it.
 int join_prep(pc_context* ctx) {
     if (!ctx->prep_dirty) return PC_OK;
-    hipStream_t const side[4] = {ctx->prep_stream, ctx->stream_b, ctx->detect_stream[0], ctx->detect_stream[1]};
-    for (hipStream_t s : side) {
+    for (hipStream_t s : {ctx->prep_stream, ctx->stream_b}) {
         if (!s) continue;
         PC_HIP(hipEventRecord(ctx->prep_fence, s));
         PC_HIP(hipStreamWaitEvent(ctx->stream, ctx->prep_fence, 0));
@@ -406,14 +405,7 @@ int order_keypoints_spatially(pc_context* ctx, pc_frame* f, DevBuf<uint32_t>& hi
     const int n = f->n_kps;
     f->perm_valid = false;
     if (n <= 0) return PC_OK;
-    if (f->perm_cap < n) {
-        const int cap = std::max(n + n / 2, 1024);
-        if (f->d_perm) PC_HIP(hipFree(f->d_perm));
-        f->d_perm = nullptr;
-        f->perm_cap = 0;
-        PC_HIP(hipMalloc(&f->d_perm, (size_t)cap * 2 * sizeof(uint32_t)));   // order + inverse
-        f->perm_cap = cap;
-    }
+    if (int rc = ensure_perm_capacity(f, n)) return rc;
     PC_HIP(hist.ensure((size_t)pc::bin_num_tiles(f->w, f->h) + 1));
     pc::launch_spatial_bins(f->d_kps, n, nullptr, f->w, f->h, hist.p, f->d_perm, f->d_perm + f->perm_cap, ctx->work);
     f->perm_valid = true;
@@ -643,12 +635,6 @@ int pc_context_create(int device_index, pc_context** out) {
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&c->stream_b, hipStreamNonBlocking);
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&c->prep_stream, hipStreamNonBlocking);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&c->prep_fence, hipEventDisableTiming);
-    {
-        const char* v = getenv("POLYCHASE_DETECT_STREAMS");
-        c->n_detect = v ? std::max(0, std::min(2, atoi(v))) : 0;
-        for (int k = 0; k < c->n_detect && e == hipSuccess; k++)
-            e = hipStreamCreateWithFlags(&c->detect_stream[k], hipStreamNonBlocking);
-    }
     c->work = c->stream;
     {
         const char* v = getenv("POLYCHASE_COPY_STREAM");
@@ -792,8 +778,6 @@ void pc_context_destroy(pc_context* c) {
         (void)hipStreamDestroy(c->stream_b);
     }
     if (c->prep_stream) (void)hipStreamDestroy(c->prep_stream);
-    for (hipStream_t s : c->detect_stream)
-        if (s) (void)hipStreamDestroy(s);
     if (c->prep_fence) (void)hipEventDestroy(c->prep_fence);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;

@@ -139,12 +139,10 @@ Slot* find_slot(pc_analyzer* a, int32_t frame_id) {
 // detection of the slot's frame, enqueued on the prep stream in one go; `kps_ready` fires when keypoints and visiting
 // order are complete
 int detect_dense(pc_analyzer* a, Slot& s) {
-    hipStream_t const ds = a->ctx->detect_stream_for(s.frame_id);
-    PrepScope prep(a->ctx, ds);
-    if (ds != a->ctx->prep_stream) PC_HIP(hipStreamWaitEvent(ds, s.img_ready, 0));
+    PrepScope prep(a->ctx);
     int rc = detect_enqueue(a->ctx, s.frame, a->grid, a->gopt, s.scratch, s.scratch.bin_hist);
     if (rc != PC_OK) return rc;
-    PC_HIP(hipEventRecord(s.kps_ready, ds));
+    PC_HIP(hipEventRecord(s.kps_ready, a->ctx->prep_stream));
     s.det = DET_ENQUEUED;
     s.supplied = false;
     return PC_OK;
@@ -155,14 +153,13 @@ int detect_finish_slot(pc_analyzer* a, Slot& s) {
     int rc;
     if (s.det == DET_NONE && (rc = detect_dense(a, s)) != PC_OK) return rc;
     {
-        hipStream_t const ds = a->ctx->detect_stream_for(s.frame_id);
-        PrepScope prep(a->ctx, ds);
+        PrepScope prep(a->ctx);
         bool redone = false;
         if ((rc = detect_finish(a->ctx, s.frame, a->grid, a->gopt, s.scratch, s.scratch.bin_hist, &redone)) != PC_OK) return rc;
         // Only then: recorded unconditionally the event would sit behind the detection of the frame that was made
         // resident a moment ago, and the LK launch of THIS frame1 would wait for it (rounds 1-2 did exactly that: the
         // "preparation chain" that bounded the step was this false dependency)
-        if (redone) PC_HIP(hipEventRecord(s.kps_ready, ds));
+        if (redone) PC_HIP(hipEventRecord(s.kps_ready, a->ctx->prep_stream));
     }
     s.det = DET_DONE;
     return PC_OK;
@@ -339,13 +336,11 @@ static int analyzer_put(pc_analyzer* a, int32_t frame_id, const uint8_t* rgb, si
         if (e) PC_HIP(hipStreamWaitEvent(a->ctx->prep_stream, e, 0));
         e = nullptr;
     }
-    // ... and so may the detection of a frame that was never submitted as frame1
-    if (s.valid && s.det == DET_ENQUEUED && a->ctx->n_detect > 0) PC_HIP(hipStreamWaitEvent(a->ctx->prep_stream, s.kps_ready, 0));
+    // (the detection of a frame that was never submitted as frame1 is in front of this on prep_stream)
     // the detection that follows expects its counters zeroed: the frame's first kernel does it on the way
-    const bool clear_here = will_detect && a->ctx->n_detect == 0;
-    int rc = set_image(a->ctx, s.frame, rgb, row_pitch, on_device, channels, elem_size, clear_here ? s.scratch.counters.p : nullptr,
+    int rc = set_image(a->ctx, s.frame, rgb, row_pitch, on_device, channels, elem_size, will_detect ? s.scratch.counters.p : nullptr,
                        detect_counter_words(s.scratch));
-    s.scratch.cleared = rc == PC_OK && clear_here;
+    s.scratch.cleared = rc == PC_OK && will_detect;
     if (rc != PC_OK) {
         s.valid = false;
         return rc;
@@ -407,17 +402,16 @@ int pc_analyzer_set_keypoints(pc_analyzer* a, int32_t frame_id, const float* xy,
     if (rc != PC_OK) return rc;
     if (n > 0) {
         // resume path (keypoints from the database): pageable source, so the copy is synchronous
-        hipStream_t const ds = a->ctx->detect_stream_for(frame_id);
+        hipStream_t const ds = a->ctx->prep_stream;
         PC_HIP(hipStreamSynchronize(ds));   // a detection of this frame in flight would write the same buffer
         PC_HIP(hipMemcpyAsync(s->frame->d_kps, xy, (size_t)n * sizeof(float2), hipMemcpyHostToDevice, ds));
         PC_HIP(hipStreamSynchronize(ds));
     }
     s->frame->n_kps = n;
     {
-        hipStream_t const ds = a->ctx->detect_stream_for(frame_id);
-        PrepScope prep(a->ctx, ds);
+        PrepScope prep(a->ctx);
         if ((rc = order_keypoints_spatially(a->ctx, s->frame, s->scratch.bin_hist)) != PC_OK) return rc;
-        PC_HIP(hipEventRecord(s->kps_ready, ds));
+        PC_HIP(hipEventRecord(s->kps_ready, a->ctx->prep_stream));
     }
     s->det = DET_DONE;
     s->supplied = true;
@@ -678,21 +672,13 @@ int pc_analyzer_collect(pc_analyzer* a, pc_frame_result* out) {
     // is the preparation stream keeping up?  (HelperPriorityControl)
     if (a->puts >= 2) {
         Slot* const sp = find_slot(a, a->put_previous);
-        bool lagging = sp && sp->img_ready && hipEventQuery(sp->img_ready) == hipErrorNotReady;
-        if (a->ctx->n_detect > 0 && !lagging) {
-            // detection on its own stream(s): the pyramid no longer queues behind it, so its lag shows where it is
-            // needed -- the keypoints of the frame1 after the next submit (one frame of slack) are not complete yet
-            Slot* const sd = find_slot(a, j.frame1 + (int32_t)a->job_count + 1);
-            lagging = sd && sd->det == DET_ENQUEUED && sd->kps_ready && hipEventQuery(sd->kps_ready) == hipErrorNotReady;
-        }
-        a->prio.observe(lagging);
+        a->prio.observe(sp && sp->img_ready && hipEventQuery(sp->img_ready) == hipErrorNotReady);
     }
     // let the runtime retire the finished commands of the other streams now, a few at a time: left alone it does
     // so in one batch of several milliseconds every couple of hundred frames, inside some later launch
     (void)hipStreamQuery(a->ctx->stream);
     if (a->ctx->stream_b) (void)hipStreamQuery(a->ctx->stream_b);
     (void)hipStreamQuery(a->ctx->prep_stream);
-    for (int k = 0; k < a->ctx->n_detect; k++) (void)hipStreamQuery(a->ctx->detect_stream[k]);
     out->frame1 = j.frame1;
     out->n_keypoints = j.n_kps;
     out->keypoints_detected = j.detected ? 1 : 0;

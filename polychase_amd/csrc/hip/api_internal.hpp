@@ -40,8 +40,8 @@ struct ScopedTimer {
 // image / detection helpers enqueue on prep_stream while one of these is alive
 struct PrepScope {
     pc_context* c;
-    explicit PrepScope(pc_context* ctx, hipStream_t s = nullptr) : c(ctx) {
-        c->work = s ? s : c->prep_stream;
+    explicit PrepScope(pc_context* ctx) : c(ctx) {
+        c->work = c->prep_stream;
         c->prep_dirty = true;
     }
     ~PrepScope() { c->work = c->stream; }

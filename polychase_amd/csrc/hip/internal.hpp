@@ -163,20 +163,11 @@ struct pc_context {
     // stream so that it overlaps the LK launch of the previous frame1 on `stream`.  `work` is the stream
     // the image / detection helpers enqueue on: `stream` by default, `prep_stream` inside the analyzer.
     hipStream_t prep_stream = nullptr;
-    // Detection of a resident frame is needed only when the frame becomes frame1, nine steps after it was put, while its
-    // pyramid is read by the very next launch: the analyzer enqueues detections on their own streams (frames alternate
-    // over n_detect of them) so that the image path never queues behind a suppression kernel and the latency-bound
-    // detection kernels of neighbouring frames overlap.  n_detect = 0: detection follows the image path on prep_stream.
-    hipStream_t detect_stream[2] = {nullptr, nullptr};
-    int n_detect = 0;
-    hipStream_t detect_stream_for(int32_t frame_id) const {
-        return n_detect > 0 ? detect_stream[(unsigned)frame_id % (unsigned)n_detect] : prep_stream;
-    }
+    // Detection follows the image path on prep_stream.
     hipError_t sync_side_streams() const {
         hipError_t e = copy_stream ? hipStreamSynchronize(copy_stream) : hipSuccess;
         if (e == hipSuccess) e = hipStreamSynchronize(prep_stream);
         if (stream_b && e == hipSuccess) e = hipStreamSynchronize(stream_b);
-        for (int k = 0; k < n_detect && e == hipSuccess; k++) e = hipStreamSynchronize(detect_stream[k]);
         return e;
     }
     hipStream_t work = nullptr;

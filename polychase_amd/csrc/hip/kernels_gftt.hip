@@ -24,195 +24,50 @@
 namespace pc {
 
 // ------------------------------------------------------------------------------------------------
-// K2  min-eigenvalue map.  Tile 64 x 16 outputs per 256-lane workgroup.
-//   LDS stage 1: gray tile with a 2-px ring, read straight from the level-0 plane (its REFLECT_101 padding is the
-//                reflection cornerMinEigenVal's Sobel wants), as aligned dwords.
-//   LDS stage 2: covariance products (Dx^2, DxDy, Dy^2) on the tile + 1-px ring; a lane walks 6 rows of one column
-//                and keeps the row filters of the 3 x 3 Sobel in registers.  Positions outside the image take the
-//                value AT THE REFLECTED POSITION (boxFilter's BORDER_REFLECT_101 applies to the covariance image,
-//                not to the gray image: DxDy changes sign when evaluated on mirrored pixels).
-//   Stage 3: 3 x 3 box sums in fp64 (exact, so separable: three-term row sums first), min eigenvalue,
-//                per-cell max via LDS, then one global atomicMax per cell and workgroup.
+// Tiles of the detection kernels: 64 x 16 pixels per 256-lane workgroup, + a 1-px ring where a 3 x 3 stencil reads one
 // ------------------------------------------------------------------------------------------------
 constexpr int TW = 64, TH = 16;
-constexpr int GH = TH + 4, G_PITCH = 72;  // gray tile: columns x0 - 4 .. x0 + 67 (18 aligned dwords), rows y0 - 2 .. y0 + 17
-constexpr int CW = TW + 2, CH = TH + 2;   // covariance tile: x0 - 1 .. x0 + 64, y0 - 1 .. y0 + 16
-
-// Dy's row pass: the smoothing taps [1, 2, 1] * scale over (a, b, c).  Canonical: the generic row filter's t = f1 a; t += f0 b;
-// t += f1 c.  ROW_FMA (PC_ARITH_SOBEL_ROW_FMA): the same chain fused -- what the 8u -> 32f vector row filter of an
-// AVX2-dispatched build computes (v_muladd from a zero accumulator: the first term is a plain product)
-template <bool ROW_FMA>
-__device__ __forceinline__ float smooth_row(float a, float b, float c, float f1, float f0) {
-    float t = f1 * a;
-    if (ROW_FMA) {
-        t = __fmaf_rn(f0, b, t);
-        t = __fmaf_rn(f1, c, t);
-    } else {
-        t += f0 * b;
-        t += f1 * c;
-    }
-    return t;
-}
-
-// SOBEL_FMA (PC_ARITH_SOBEL_FMA) is a template parameter, not a launch argument: the extra code of that mode took the
-// kernel from 64 to 106 VGPRs, and a helper wavefront with more than 104 does not fit beside three LK wavefronts per SIMD
-// (512 - 3 x 136): the detection then only ran in the gaps of the LK launches -- 4K pipeline 710 -> 537 frames/s, caught by
-// the round's last profile run.  tests/test_kernel_resources_cpu.py now holds every helper kernel to its budget.
-// SOBEL: bit 0 = the fused column pass of Dx (PC_ARITH_SOBEL_FMA), bit 1 = the fused row pass of Dy (PC_ARITH_SOBEL_ROW_FMA)
-// MASKED (detection mask, gftt.cc:58-63): `mask` is a w x h plane of bytes; a pixel whose byte is 0 is left out of its cell's
-// maximum (minMaxLoc with a mask) -- its key becomes 0, which no atomicMax takes.  The map itself is the same with and without.
-// A compile-time variant: the unmasked instantiations never look at `mask`.
-template <int SOBEL, bool MASKED>
-__global__ __launch_bounds__(256) void min_eig_kernel(const uint8_t* __restrict__ img, int pitch, int w, int h,
-                                                      float* __restrict__ eig, GfttGrid g,
-                                                      uint32_t* __restrict__ cell_max, float f1, float f0, int hi_prio,
-                                                      const uint8_t* __restrict__ mask) {
-    constexpr bool sobel_fma = (SOBEL & 1) != 0, row_fma = (SOBEL & 2) != 0;
-    helper_priority(hi_prio);
-    __shared__ __attribute__((aligned(16))) uint8_t s_gray[GH][G_PITCH];
-    __shared__ float s_cxx[CH][CW + 1];
-    __shared__ float s_cxy[CH][CW + 1];
-    __shared__ float s_cyy[CH][CW + 1];
-    __shared__ uint32_t s_max[4];
-
-    const int tid = threadIdx.x;
-    const int x0 = blockIdx.x * TW, y0 = blockIdx.y * TH;
-    if (tid < 4) s_max[tid] = 0u;
-
-    // stage 1: gray tile.  Rows / columns more than 2 px outside the image are clamped (never consumed).
-    {
-        const int xmax = pitch - kPadX - 4;
-        for (int i = tid; i < GH * (G_PITCH / 4); i += 256) {
-            const int r = i / (G_PITCH / 4), d = i - r * (G_PITCH / 4);
-            const int yy = min(max(y0 - 2 + r, -2), h + 1), xx = min(x0 - 4 + 4 * d, xmax);
-            *reinterpret_cast<uint32_t*>(&s_gray[r][4 * d]) = *reinterpret_cast<const uint32_t*>(img + (ptrdiff_t)yy * pitch + xx);
-        }
-    }
-    __syncthreads();
-
-    // stage 2: lane = (column cx, band of 6 covariance rows); gray rows of covariance row cy are cy .. cy + 2,
-    // gray columns of covariance column cx are cx + 2 .. cx + 4 (tile column 0 is x0 - 4)
-    if (tid < 3 * CW) {
-        const int cx = tid % CW, band = tid / CW;
-        const int ax = x0 - 1 + cx;
-        float rx[3], ry[3];   // row filters of gray rows cy, cy + 1 (the two carried over), cy + 2
-#pragma unroll
-        for (int k = 0; k < 2; k++) {
-            const uint8_t* gp = &s_gray[6 * band + k][cx + 2];
-            const float a = gp[0], b = gp[1], c = gp[2];
-            rx[k] = c - a;
-            ry[k] = smooth_row<row_fma>(a, b, c, f1, f0);
-        }
-#pragma unroll
-        for (int k = 0; k < 6; k++) {
-            const int cy = 6 * band + k;
-            const uint8_t* gp = &s_gray[cy + 2][cx + 2];
-            const float a = gp[0], b = gp[1], c = gp[2];
-            rx[2] = c - a;
-            ry[2] = smooth_row<row_fma>(a, b, c, f1, f0);
-            // Dx: row [-1,0,1] then column (S0 + S2)*f1 + S1*f0;  Dy: row [1,2,1]*scale then column S2 - S0
-            // PC_ARITH_SOBEL_FMA: v_muladd(S0 + S2, k1, S1 * k0) fused, as the AVX2 build of the filter executes it
-            const float dx = sobel_fma ? __fmaf_rn(rx[0] + rx[2], f1, rx[1] * f0) : (rx[0] + rx[2]) * f1 + rx[1] * f0;
-            const float dy = ry[2] - ry[0];
-            const int ay = y0 - 1 + cy;
-            const bool in = ax >= 0 && ax < w && ay >= 0 && ay < h;
-            s_cxx[cy][cx] = in ? dx * dx : 0.f;
-            s_cxy[cy][cx] = in ? dx * dy : 0.f;
-            s_cyy[cy][cx] = in ? dy * dy : 0.f;
-            rx[0] = rx[1]; rx[1] = rx[2];
-            ry[0] = ry[1]; ry[1] = ry[2];
-        }
-    }
-    __syncthreads();
-    // covariance ring outside the image <- the reflected (in-image) position; only tiles on the image edge have one
-    if (x0 == 0 || y0 == 0 || x0 + TW >= w || y0 + TH >= h) {
-        for (int i = tid; i < CW * CH; i += 256) {
-            const int cy = i / CW, cx = i - cy * CW;
-            const int ax = x0 - 1 + cx, ay = y0 - 1 + cy;
-            if ((ax < 0 || ax >= w || ay < 0 || ay >= h) && ax >= -1 && ax <= w && ay >= -1 && ay <= h) {
-                const int sx = reflect101(ax, w) - (x0 - 1), sy = reflect101(ay, h) - (y0 - 1);
-                if (sx >= 0 && sx < CW && sy >= 0 && sy < CH) {
-                    s_cxx[cy][cx] = s_cxx[sy][sx];
-                    s_cxy[cy][cx] = s_cxy[sy][sx];
-                    s_cyy[cy][cx] = s_cyy[sy][sx];
-                }
-            }
-        }
-        __syncthreads();
-    }
-
-    // stage 3: lane = (column tx, 4 consecutive rows): six three-term row sums per channel, then the column sums
-    const int tx = tid & 63, ty0 = (tid >> 6) * 4;
-    const int x = x0 + tx;
-    const int cell_x0 = x0 / g.cell_w, cell_y0 = y0 / g.cell_h;
-    const bool small_cells = (g.cell_w < TW) || (g.cell_h < TH);
-    const int cell_bx = (cell_x0 + 1) * g.cell_w, cell_by = (cell_y0 + 1) * g.cell_h;   // block-uniform
-    double hxx[6], hxy[6], hyy[6];
-#pragma unroll
-    for (int k = 0; k < 6; k++) {
-        const int cy = ty0 + k;
-        hxx[k] = ((double)s_cxx[cy][tx] + (double)s_cxx[cy][tx + 1]) + (double)s_cxx[cy][tx + 2];
-        hxy[k] = ((double)s_cxy[cy][tx] + (double)s_cxy[cy][tx + 1]) + (double)s_cxy[cy][tx + 2];
-        hyy[k] = ((double)s_cyy[cy][tx] + (double)s_cyy[cy][tx + 1]) + (double)s_cyy[cy][tx + 2];
-    }
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        const int y = y0 + ty0 + k;
-        if (x < w && y < h) {
-            double sxx = (hxx[k] + hxx[k + 1]) + hxx[k + 2];
-            double sxy = (hxy[k] + hxy[k + 1]) + hxy[k + 2];
-            double syy = (hyy[k] + hyy[k + 1]) + hyy[k + 2];
-            // (With the fused column filter a cancelling Dx leaves a residual of ~1e-10 instead of 0, its square is ~1e-19
-            // beside sums of ~1e-3: the fp64 box sums are no longer exact and their ORDER shows in the last bit of one pixel
-            // in ~10^5.  The oracle's order is this one: rows left to right, then the row sums top to bottom -- 0.0 + h[k] is
-            // exact, so (h[k] + h[k + 1]) + h[k + 2] is that order.)
-            const float a = (float)sxx * 0.5f;
-            const float b = (float)sxy;
-            const float c = (float)syy * 0.5f;
-            const float t = a - c;
-            float e = (a + c) - sqrtf(t * t + b * b);
-#ifdef PC_MINEIG_DUMP   // debugging aid: the covariance tile instead of the response (column x - 1 + PC_MINEIG_DUMP, channel xy)
-            e = s_cxy[ty0 + k + 1][tx + PC_MINEIG_DUMP];
-#endif
-            eig[(size_t)y * w + x] = e;
-            uint32_t key = float_to_ordered(e);
-            if (MASKED && mask[(size_t)y * w + x] == 0) key = 0u;
-            if (small_cells) {
-                const int cx = x / g.cell_w, cy = y / g.cell_h;
-                atomicMax(&cell_max[cy * g.cols + cx], key);
-            } else {
-                // a tile spans at most two cells per axis: the cell of a pixel is a comparison with the next cell
-                // boundary, not a division (5 per lane before)
-                atomicMax(&s_max[(y >= cell_by ? 2 : 0) + (x >= cell_bx ? 1 : 0)], key);
-            }
-        }
-    }
-    __syncthreads();
-    if (!small_cells && tid < 4) {
-        const int cx = cell_x0 + (tid & 1), cy = cell_y0 + (tid >> 1);
-        if (cx < g.cols && cy < g.rows && s_max[tid] != 0u) atomicMax(&cell_max[cy * g.cols + cx], s_max[tid]);
-    }
-}
+constexpr int CW = TW + 2, CH = TH + 2;   // tile + ring: x0 - 1 .. x0 + 64, y0 - 1 .. y0 + 16
 
 // ------------------------------------------------------------------------------------------------
-// K2, round 4: the same map without LDS.  A lane owns 2 output columns x ME_R output rows and walks down its band once,
-// everything in registers:
-//   per gray row (2 aligned dword loads = columns x - 2 .. x + 3): the Sobel row filters of the 4 covariance columns
+// K2  min-eigenvalue map of the detector's default (block 3, Sobel 3), without LDS.  A lane owns 2 output columns x ME_R
+// output rows and walks down its band once, everything in registers:
+//   per gray row (2 aligned dword loads = columns x - 2 .. x + 3, read straight from the level-0 plane: its REFLECT_101
+//       padding is the reflection cornerMinEigenVal's Sobel wants): the Sobel row filters of the 4 covariance columns
 //       x - 1 .. x + 2 -- the products f1 * g and f0 * g of a pixel are formed once and shared by the three columns that use it;
 //   per covariance row (the gray rows above / at / below it are the last three walked): Dx, Dy, their three products for the
 //       4 columns, the window rows' sums ((c[j-1] + c[j]) + c[j+1] in fp64) of the 2 output columns;
 //   per output row: the three row sums added top to bottom, the eigenvalue, the running maximum of the lane.
-// Covariance positions outside the image take the value at the REFLECTED position (see the tiled kernel): a column by a
+// Covariance positions outside the image take the value AT THE REFLECTED POSITION (boxFilter's BORDER_REFLECT_101 applies to
+// the covariance image, not to the gray image: DxDy changes sign when evaluated on mirrored pixels): a column by a
 // register copy inside the lane (-1 <- 1; w <- w - 2 lies at most two columns left of it), a row by substituting the
 // other neighbour's row sums in the vertical sum (-1 <- 1, h <- h - 2).  A wavefront covers 64 x (2 * ME_R) pixels; the
 // per-cell maximum is ONE atomic per wavefront when its tile lies in one grid cell (wave-uniform test; else four
 // registers for the <= 2 x 2 cells a tile can touch, or per-pixel atomics for cells smaller than a tile).
-// Measured against the tiled kernel (tools/prep_bench.py, profiles/r04_*_prep.json; SQ_INSTS_VALU per pixel: r04_*_pipeline_by_kernel_pmc.json).
+// Measurements: tools/prep_bench.py, profiles/r04_*_prep.json; SQ_INSTS_VALU per pixel: r04_*_pipeline_by_kernel_pmc.json.
+//
+// Row filters: Dx's row pass is [-1, 0, 1], its column pass (S0 + S2) * f1 + S1 * f0; Dy's row pass ("smooth_row") is the
+// smoothing taps [1, 2, 1] * scale over (a, b, c), its column pass S2 - S0.  Canonical smooth_row: the generic row filter's
+// t = f1 a; t += f0 b; t += f1 c.  ROW_FMA (PC_ARITH_SOBEL_ROW_FMA): the same chain fused -- what the 8u -> 32f vector row
+// filter of an AVX2-dispatched build computes (v_muladd from a zero accumulator: the first term is a plain product).
+// SOBEL_FMA (PC_ARITH_SOBEL_FMA): v_muladd(S0 + S2, k1, S1 * k0) fused, as the AVX2 build of the column filter executes it.
+//
+// Box sums: 3 x 3 in fp64 -- exact in the canonical arithmetic, so separable: three-term row sums first.  With the fused
+// column filter a cancelling Dx leaves a residual of ~1e-10 instead of 0, its square is ~1e-19 beside sums of ~1e-3: the fp64
+// box sums are no longer exact and their ORDER shows in the last bit of one pixel in ~10^5.  The oracle's order is this one:
+// rows left to right, then the row sums top to bottom -- 0.0 + h[k] is exact, so (h[k] + h[k + 1]) + h[k + 2] is that order.
 // ------------------------------------------------------------------------------------------------
 constexpr int ME_R = 8;                       // output rows per lane
 constexpr int ME_TW = 64, ME_TH = 2 * ME_R;   // pixels per wavefront: 32 column pairs x 2 bands
 
-// MASKED: as in the tiled kernel -- the keys of masked-out pixels become 0 before any of the three per-cell paths sees them.
+// SOBEL is a template parameter, not a launch argument: the extra code of PC_ARITH_SOBEL_FMA took the response kernel from 64
+// to 106 VGPRs, and a helper wavefront with more than 104 does not fit beside three LK wavefronts per SIMD (512 - 3 x 136):
+// the detection then only ran in the gaps of the LK launches -- 4K pipeline 710 -> 537 frames/s, caught by that round's last
+// profile run.  tests/test_kernel_resources_cpu.py now holds every helper kernel to its budget.
+// SOBEL: bit 0 = the fused column pass of Dx (PC_ARITH_SOBEL_FMA), bit 1 = the fused row pass of Dy (PC_ARITH_SOBEL_ROW_FMA)
+// MASKED (detection mask, gftt.cc:58-63): `mask` is a w x h plane of bytes; a pixel whose byte is 0 is left out of its cell's
+// maximum (minMaxLoc with a mask) -- its key becomes 0, which no atomicMax takes, before any of the three per-cell paths sees
+// it.  The map itself is the same with and without.  A compile-time variant: the unmasked instantiations never look at `mask`.
 template <int SOBEL, bool MASKED>
 __global__ __launch_bounds__(256) void min_eig_fused_kernel(const uint8_t* __restrict__ img, int pitch, int w, int h,
                                                             float* __restrict__ eig, GfttGrid g,
@@ -420,33 +275,16 @@ __global__ __launch_bounds__(256) void min_eig_fused_kernel(const uint8_t* __res
     }
 }
 
-// POLYCHASE_MINEIG_VARIANT=1: the LDS-tiled kernel of rounds 1-3 (the cross-check of the fused one; tests/test_env_variants_gpu.py)
-static int min_eig_variant() {
-    static const int v = [] {
-        const char* e = getenv("POLYCHASE_MINEIG_VARIANT");
-        return e ? atoi(e) : 0;
-    }();
-    return v;
-}
-
-template <int SOBEL, bool MASKED>
-static void launch_min_eig_masked(const Level& l0, float* eig, const GfttGrid& g, uint32_t* cell_max, float f1, float f0, hipStream_t s,
-                                  const uint8_t* mask) {
-    if (min_eig_variant() == 0) {
-        dim3 grid2((l0.w + 2 * ME_TW - 1) / (2 * ME_TW), (l0.h + 2 * ME_TH - 1) / (2 * ME_TH));
-        hipLaunchKernelGGL((min_eig_fused_kernel<SOBEL, MASKED>), grid2, dim3(256), 0, s, l0.img, l0.pitch, l0.w, l0.h, eig, g, cell_max, f1, f0,
-                           helper_prio_arg(), mask);
-        return;
-    }
-    dim3 grid((l0.w + TW - 1) / TW, (l0.h + TH - 1) / TH);
-    hipLaunchKernelGGL((min_eig_kernel<SOBEL, MASKED>), grid, dim3(256), 0, s, l0.img, l0.pitch, l0.w, l0.h, eig, g, cell_max, f1, f0,
-                       helper_prio_arg(), mask);
-}
 template <int SOBEL>
 static void launch_min_eig_mode(const Level& l0, float* eig, const GfttGrid& g, uint32_t* cell_max, float f1, float f0, hipStream_t s,
                                 const uint8_t* mask) {
-    if (mask) launch_min_eig_masked<SOBEL, true>(l0, eig, g, cell_max, f1, f0, s, mask);
-    else launch_min_eig_masked<SOBEL, false>(l0, eig, g, cell_max, f1, f0, s, nullptr);
+    dim3 grid((l0.w + 2 * ME_TW - 1) / (2 * ME_TW), (l0.h + 2 * ME_TH - 1) / (2 * ME_TH));
+    if (mask)
+        hipLaunchKernelGGL((min_eig_fused_kernel<SOBEL, true>), grid, dim3(256), 0, s, l0.img, l0.pitch, l0.w, l0.h, eig, g, cell_max, f1, f0,
+                           helper_prio_arg(), mask);
+    else
+        hipLaunchKernelGGL((min_eig_fused_kernel<SOBEL, false>), grid, dim3(256), 0, s, l0.img, l0.pitch, l0.w, l0.h, eig, g, cell_max, f1, f0,
+                           helper_prio_arg(), (const uint8_t*)nullptr);
 }
 void launch_min_eig(const Level& l0, float* eig, const GfttGrid& g, uint32_t* cell_max, int sobel_fma, hipStream_t s, const uint8_t* mask) {
     // scale = 1 / (2^(ksize-1) * block_size * 255), folded into the smoothing taps (see oracle)
@@ -570,7 +408,7 @@ __global__ __launch_bounds__(256) void box_rows_kernel(const float* __restrict__
     rows[2 * n + row + x] = ryy;
 }
 
-template <bool MASKED>   // the detection mask, as in min_eig_kernel
+template <bool MASKED>   // the detection mask, as in min_eig_fused_kernel
 __global__ __launch_bounds__(256) void box_response_kernel(const float* __restrict__ cov, const double* __restrict__ rows, int w, int h, int block, int harris, double harris_k,
                                                            float* __restrict__ eig, GfttGrid g, uint32_t* __restrict__ cell_max, int hi_prio,
                                                            const uint8_t* __restrict__ mask) {

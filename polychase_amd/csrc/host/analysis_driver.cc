@@ -60,7 +60,7 @@ struct Engine {
     static std::string EnvKey() {
         std::string k;
         for (const char* name : {"POLYCHASE_ARITH", "POLYCHASE_COPY_STREAM", "POLYCHASE_HELPER_PRIO", "POLYCHASE_LK_GATE", "POLYCHASE_LK_LANES",
-                                 "POLYCHASE_DETECT_STREAMS", "POLYCHASE_GFTT_SLOW_PATH", "POLYCHASE_INGEST_DMA"}) {
+                                 "POLYCHASE_GFTT_SLOW_PATH", "POLYCHASE_INGEST_DMA"}) {
             const char* v = std::getenv(name);
             k += v ? v : "";
             k += '\x1f';

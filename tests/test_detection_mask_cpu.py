@@ -127,8 +127,7 @@ def kernels():
 
 # substring of the mangled name -> number of instantiations; ELb1 / ILb1: MASKED = true
 MASKED_HELPERS = {"min_eig_fused_kernelILi0ELb1": 1, "min_eig_fused_kernelILi1ELb1": 1, "min_eig_fused_kernelILi2ELb1": 1,
-                  "min_eig_fused_kernelILi3ELb1": 1, "min_eig_kernelILi0ELb1": 1, "min_eig_kernelILi1ELb1": 1,
-                  "min_eig_kernelILi2ELb1": 1, "min_eig_kernelILi3ELb1": 1, "nms_kernelILb1": 1, "box_response_kernelILb1": 1}
+                  "min_eig_fused_kernelILi3ELb1": 1, "nms_kernelILb1": 1, "box_response_kernelILb1": 1}
 
 
 @pytest.mark.parametrize("helper", sorted(MASKED_HELPERS))
