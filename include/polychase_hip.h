@@ -205,6 +205,8 @@ int pc_frame_level_size(const pc_frame* f, int level, int* width, int* height);
 int pc_frame_download_gray(pc_context* ctx, const pc_frame* f, uint8_t* out_gray);
 int pc_frame_download_level(pc_context* ctx, const pc_frame* f, int level, uint8_t* out_padded);
 int pc_frame_download_deriv(pc_context* ctx, const pc_frame* f, int level, int16_t* out_padded);
+/* The plane the LK kernels read: (h + 2*win) x (w + 2*win) uint16, every value of the padded image plane << 7. */
+int pc_frame_download_level16(pc_context* ctx, const pc_frame* f, int level, uint16_t* out_padded);
 
 /* GoodFeaturesToTrack (cpp/feature_detection/gftt.cc:14-192, called at opticalflow.cc:160) on the
  * frame's gray image; keypoints stay on the device, in acceptance order. */

@@ -1204,6 +1204,18 @@ int pc_frame_download_deriv(pc_context* ctx, const pc_frame* f, int level, int16
     return PC_OK;
 }
 
+int pc_frame_download_level16(pc_context* ctx, const pc_frame* f, int level, uint16_t* out) {
+    if (!ctx || !f || !out || level < 0 || level >= f->nlevels) return fail(PC_E_INVALID, "bad argument");
+    if (int jrc = join_prep(ctx)) return jrc;
+    const pc::Level& L = f->levels[level];
+    const int win = f->win;
+    const uint16_t* src = L.img16 - (ptrdiff_t)win * L.pitch - win;
+    const size_t row = (size_t)(L.w + 2 * win) * 2;
+    PC_HIP(hipMemcpy2DAsync(out, row, src, (size_t)L.pitch * 2, row, L.h + 2 * win, hipMemcpyDeviceToHost, ctx->stream));
+    PC_HIP(hipStreamSynchronize(ctx->stream));
+    return PC_OK;
+}
+
 // ---------------------------------------------------------------------------------------------
 int pc_frame_detect(pc_context* ctx, pc_frame* f, const pc_gftt_options* opt) {
     if (!ctx || !f || !opt) return fail(PC_E_INVALID, "null argument");

@@ -26,7 +26,7 @@ SYMBOLS = [
     "pc_frame_create", "pc_frame_destroy", "pc_frame_set_rgb", "pc_frame_set_rgb_f32", "pc_frame_set_gray",
     "pc_host_buffer_alloc", "pc_host_buffer_free",
     "pc_frame_num_levels", "pc_frame_level_size", "pc_frame_download_gray", "pc_frame_download_level",
-    "pc_frame_download_deriv", "pc_frame_detect", "pc_frame_download_min_eig", "pc_frame_num_candidates",
+    "pc_frame_download_deriv", "pc_frame_download_level16", "pc_frame_detect", "pc_frame_download_min_eig", "pc_frame_num_candidates",
     "pc_frame_num_keypoints", "pc_frame_download_keypoints", "pc_frame_set_keypoints", "pc_frame_set_mask",
     "pc_frame_set_mask_polygons", "pc_frame_download_mask", "pc_analyzer_set_mask_polygons",
     "pc_lk_track", "pc_lk_track_filtered", "pc_lk_track_fb", "pc_lk_track_filtered_fb",
@@ -134,6 +134,10 @@ def load():
     L.pc_frame_download_gray.argtypes = [vp, vp, vp]
     L.pc_frame_download_level.argtypes = [vp, vp, C.c_int, vp]
     L.pc_frame_download_deriv.argtypes = [vp, vp, C.c_int, vp]
+    L.pc_frame_download_level16.argtypes = [vp, vp, C.c_int, vp]
+    L.pc_host_buffer_alloc.argtypes = [C.c_size_t, C.POINTER(vp)]
+    L.pc_host_buffer_free.argtypes = [vp]
+    L.pc_host_buffer_free.restype = None
     L.pc_frame_detect.argtypes = [vp, vp, C.POINTER(GfttOptions)]
     L.pc_frame_set_mask.argtypes = [vp, vp, vp, C.c_size_t, C.c_int]
     L.pc_frame_set_mask_polygons.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int]
@@ -402,6 +406,13 @@ class Frame:
         w, h = self.level_size(l)
         out = np.empty((h + 2 * self.win, w + 2 * self.win, 2), np.int16)
         _check(load().pc_frame_download_deriv(self.ctx._h, self._h, l, out.ctypes.data))
+        return out
+
+    def level16(self, l: int) -> np.ndarray:
+        """the uint16 plane the LK kernels read (pixel << 7), padded like level()"""
+        w, h = self.level_size(l)
+        out = np.empty((h + 2 * self.win, w + 2 * self.win), np.uint16)
+        _check(load().pc_frame_download_level16(self.ctx._h, self._h, l, out.ctypes.data))
         return out
 
     def set_mask(self, mask):
