@@ -245,6 +245,11 @@ int pc_frame_set_mask_polygons(pc_context* ctx, pc_frame* f, const float* xy, co
 /* tests, debugging: the frame's current mask plane, w*h bytes (255 / 0 for a polygon mask, the caller's bytes for a byte
  * mask); PC_E_STATE when the frame has no mask on */
 int pc_frame_download_mask(pc_context* ctx, const pc_frame* f, uint8_t* out);
+/* tests, debugging: the choked plane C_margin of the frame's current mask (target-side masks below: pc_lk_track_masked), w*h
+ * bytes, 255 / 0; margin 0: the mask read as on/off.  PC_E_STATE when the frame has no mask on, PC_E_INVALID for a margin
+ * outside 0..PC_TARGET_MASK_MAX_MARGIN. */
+#define PC_TARGET_MASK_MAX_MARGIN 31
+int pc_frame_download_choked_mask(pc_context* ctx, const pc_frame* f, int margin, uint8_t* out);
 /* cv::cornerMinEigenVal map of the last pc_frame_detect (gftt.cc:35), w*h floats (tests). */
 int pc_frame_download_min_eig(pc_context* ctx, const pc_frame* f, float* out_eig);
 /* Number of local-maximum candidates of the last pc_frame_detect (gftt.cc:76-86) (tests). */
@@ -285,6 +290,22 @@ int pc_lk_track_fb(pc_context* ctx, const pc_frame* frame1, const pc_frame* cons
 int pc_lk_track_filtered_fb(pc_context* ctx, const pc_frame* frame1, const pc_frame* const* targets,
                             int n_targets, const pc_flow_options* opt, double fb_threshold, uint32_t* src_indices,
                             float* tgt_xy, float* flow_err, int64_t* row_offset);
+
+/* ---- target-side masks (not in the reference, off by default) ----
+ * A detection mask keeps keypoints out of a region of frame1; this keeps ROWS out that END in the masked-out region of their
+ * target (a background keypoint that a matted-out actor covers in the target frame).  on(x, y): the target's mask byte is
+ * non-zero.  Choked plane of margin r, 0 <= r <= PC_TARGET_MASK_MAX_MARGIN: C_r(x, y) = 255 when on(x', y') holds for every
+ * pixel of the frame with |x' - x| <= r and |y' - y| <= r, else 0 -- pixels outside the frame are ignored; C_0 is the mask read
+ * as on/off (kernels_mask.hip: mask_choke_kernel).  A forward record (q, err, status_f == 1) is judged at the pixel
+ *   ix = (int) fminf(fmaxf(floorf(q.x + 0.5f), 0.f), (float)(w - 1)),   iy likewise with q.y and h,
+ * every operation rounded to fp32: an end point outside the frame (OpenCV keeps such rows) by the nearest border pixel, a NaN
+ * by pixel 0.  The row's status becomes 0 when its target has a mask on (pc_frame_set_mask / _polygons) and C_r(ix, iy) == 0;
+ * next_xy and err are untouched, and a target without a mask keeps every row.  With fb_threshold > 0 the final status is the
+ * AND of both checks; the mask test runs first, so the backward launch does no work for the rows it dropped.
+ * pc_lk_track_masked: pc_lk_track_fb without the back outputs, under the margin.  margin == -1: exactly pc_lk_track_fb
+ * (nothing else is enqueued); margin outside -1..PC_TARGET_MASK_MAX_MARGIN: PC_E_INVALID. */
+int pc_lk_track_masked(pc_context* ctx, const pc_frame* frame1, const pc_frame* const* targets, int n_targets,
+                       const pc_flow_options* opt, double fb_threshold, int margin, float* next_xy, uint8_t* status, float* err);
 
 /* ---- analyzer: the pipelined per-clip engine behind GenerateOpticalFlowDatabase ----
  * (cpp/opticalflow.cc:209-321).  Holds a ring of resident frames (the reference's 17-frame
@@ -375,7 +396,8 @@ int pc_analyzer_set_fb_threshold(pc_analyzer* a, double fb_threshold);
  * (on_device = 0) is consumed before the call returns; a device mask (on_device = 1) is read when a frame is put and must
  * stay alive and unmodified until pc_analyzer_frame_ingested says so for the frames put under it.  Frames put with
  * will_detect = 0 (their keypoints come from the caller, or they are detected without a mask when submitted as frame1) never
- * take the mask.  The planes are allocated by the first call with a mask; an analyzer that never sees one allocates nothing
+ * take the mask -- unless a target-side margin is on (pc_analyzer_set_target_mask_margin below), and then as targets only.  The
+ * planes are allocated by the first call with a mask; an analyzer that never sees one allocates nothing
  * and enqueues what it always did.  pc_analyzer_reset clears the mask.  Null analyzer, or row_pitch < width: PC_E_INVALID. */
 int pc_analyzer_set_mask(pc_analyzer* a, const uint8_t* mask, size_t row_pitch, int on_device);
 /* As pc_analyzer_set_mask, the mask of the frames put from now on with will_detect != 0, given as polygons
@@ -384,6 +406,17 @@ int pc_analyzer_set_mask(pc_analyzer* a, const uint8_t* mask, size_t row_pitch, 
  * change with every frame and nothing of the size of a plane crosses the bus.  The first call allocates the slots' planes and
  * the vertex ring; later calls allocate nothing.  pc_analyzer_set_mask(a, NULL, ..) and pc_analyzer_reset clear it. */
 int pc_analyzer_set_mask_polygons(pc_analyzer* a, const float* xy, const int32_t* counts, int n_polygons, int invert);
+/* Target-side masks (pc_lk_track_masked) for the frames put FROM NOW ON: -1 = off (the default), 0..PC_TARGET_MASK_MAX_MARGIN =
+ * the margin.  While it is >= 0 and a mask is in force (pc_analyzer_set_mask / _polygons), every frame put takes the mask into
+ * its slot's plane whatever will_detect is, and with margin > 0 also gets the choked plane, made on the preparation stream in
+ * front of the frame's "image ready" event.  The jobs submitted then drop, between the forward launch and the forward-backward
+ * check, the rows that end where the target's plane is off; the margin a frame was put under is the one applied to the rows
+ * that end in it, and a frame put without a mask in force keeps every row tracked into it.  Whether a frame's DETECTION reads
+ * the mask stays as pc_analyzer_set_mask says: a frame put with will_detect = 0 is never detected under a mask.  The planes are
+ * allocated by the first call that needs them: an analyzer that never sees a margin >= 0 together with a mask allocates and
+ * enqueues what it always did.  pc_analyzer_reset keeps the margin (like the forward-backward threshold) and clears the mask.
+ * Null analyzer, or a margin outside -1..PC_TARGET_MASK_MAX_MARGIN: PC_E_INVALID. */
+int pc_analyzer_set_target_mask_margin(pc_analyzer* a, int margin);
 /* Wait for the oldest submitted job.  Pointers stay valid until the job slot is reused, i.e. for
  * the next max_jobs-1 submits. */
 int pc_analyzer_collect(pc_analyzer* a, pc_frame_result* out);

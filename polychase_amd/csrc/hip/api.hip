@@ -529,6 +529,32 @@ int run_lk_fb(pc_context* ctx, const pc_frame* frame1, const pc_frame* const* ta
     return PC_OK;
 }
 
+int check_target_margin(int margin, bool allow_off) {
+    if (margin < (allow_off ? -1 : 0) || margin > PC_TARGET_MASK_MAX_MARGIN)
+        return fail(PC_E_INVALID, "margin %d, %d..%d allowed", margin, allow_off ? -1 : 0, PC_TARGET_MASK_MAX_MARGIN);
+    return PC_OK;
+}
+
+int run_lk_target_mask(pc_context* ctx, const pc_frame* frame1, const uint8_t* const* plane, int n_targets, int set) {
+    const int n = frame1->n_kps;
+    pc::TargetMaskParams p;
+    std::memset(&p, 0, sizeof(p));
+    bool any = false;
+    for (int t = 0; t < n_targets; t++) {
+        p.plane[t] = plane[t];
+        any = any || plane[t] != nullptr;
+    }
+    if (!any || n <= 0) return PC_OK;
+    p.rec = ctx->lk_rec[set].p;
+    p.n = n;
+    p.n_targets = n_targets;
+    p.w = frame1->w;
+    p.h = frame1->h;
+    pc::launch_lk_target_mask(p, ctx->lane_stream(set));
+    PC_HIP(hipGetLastError());
+    return PC_OK;
+}
+
 }  // namespace pc_api
 
 using namespace pc_api;
@@ -762,6 +788,7 @@ void pc_context_destroy(pc_context* c) {
     c->lk_cerr.release();
     c->lk_back_xy.release();
     c->lk_back_status.release();
+    c->lk_choked.release();
     c->lk_cidx.release();
     for (auto& b : c->lk_block_counts) b.release();
     c->lk_perm.release();
@@ -948,6 +975,7 @@ void pc_frame_destroy(pc_frame* f) {
     if (f->d_kps) (void)hipFree(f->d_kps);
     if (f->d_perm) (void)hipFree(f->d_perm);
     if (f->d_mask) (void)hipFree(f->d_mask);
+    if (f->d_choked) (void)hipFree(f->d_choked);
     delete f;
 }
 
@@ -957,6 +985,12 @@ int pc_api::ensure_mask_plane(pc_frame* f) {
     if (f->d_mask) return PC_OK;
     // + 16: the kernels read a quad's bytes as one aligned dword, never past the plane, but a little room costs nothing
     PC_HIP(hipMalloc(reinterpret_cast<void**>(&f->d_mask), (size_t)f->w * f->h + 16));
+    return PC_OK;
+}
+
+int pc_api::ensure_choked_plane(pc_frame* f) {
+    if (f->d_choked) return PC_OK;
+    PC_HIP(hipMalloc(reinterpret_cast<void**>(&f->d_choked), (size_t)f->w * f->h + 16));
     return PC_OK;
 }
 
@@ -1163,6 +1197,21 @@ int pc_frame_download_mask(pc_context* ctx, const pc_frame* f, uint8_t* out) {
     return PC_OK;
 }
 
+int pc_frame_download_choked_mask(pc_context* ctx, const pc_frame* f, int margin, uint8_t* out) {
+    if (int rc = check_target_margin(margin, false)) return rc;   // first: a margin is refused whatever the handles
+    if (!ctx || !f || !out) return fail(PC_E_INVALID, "null argument");
+    if (!f->mask_on) return fail(PC_E_STATE, "the frame has no mask on");
+    PC_HIP(hipSetDevice(ctx->device));
+    if (int jrc = join_prep(ctx)) return jrc;
+    const size_t bytes = (size_t)f->w * f->h;
+    PC_HIP(ctx->lk_choked.ensure(bytes + 16));
+    pc::launch_mask_choke(f->d_mask, ctx->lk_choked.p, f->w, f->h, margin, ctx->stream);
+    PC_HIP(hipGetLastError());
+    PC_HIP(hipMemcpyAsync(out, ctx->lk_choked.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    PC_HIP(hipStreamSynchronize(ctx->stream));
+    return PC_OK;
+}
+
 int pc_frame_num_levels(const pc_frame* f) { return f ? f->nlevels : 0; }
 
 int pc_frame_level_size(const pc_frame* f, int level, int* width, int* height) {
@@ -1283,10 +1332,11 @@ int pc_frame_set_keypoints(pc_context* ctx, pc_frame* f, const float* xy, int n)
 
 // ---------------------------------------------------------------------------------------------
 static int lk_track_impl(pc_context* ctx, const pc_frame* frame1, const pc_frame* const* targets, int n_targets,
-                         const pc_flow_options* opt, double fb_threshold, float* next_xy, uint8_t* status, float* err,
+                         const pc_flow_options* opt, double fb_threshold, int margin, float* next_xy, uint8_t* status, float* err,
                          float* back_xy, uint8_t* back_status) {
-    int rc = check_lk_args(ctx, frame1, targets, n_targets, opt);
+    int rc = check_target_margin(margin, true);   // first: a margin is refused whatever the handles
     if (rc != PC_OK) return rc;
+    if ((rc = check_lk_args(ctx, frame1, targets, n_targets, opt)) != PC_OK) return rc;
     if (!next_xy || !status || !err) return fail(PC_E_INVALID, "null output");
     if ((rc = check_fb_threshold(fb_threshold)) != PC_OK) return rc;
     PC_HIP(hipSetDevice(ctx->device));
@@ -1294,6 +1344,26 @@ static int lk_track_impl(pc_context* ctx, const pc_frame* frame1, const pc_frame
     rc = run_lk(ctx, frame1, targets, n_targets, opt);
     if (rc != PC_OK) return rc;
     const size_t rows = (size_t)frame1->n_kps * n_targets;
+    if (margin >= 0 && rows > 0) {
+        // target-side masks: each masked target's plane -- choked into the context's scratch when there is a margin -- judges
+        // the rows that end in it, before the backward launch
+        const size_t plane_bytes = ((size_t)frame1->w * frame1->h + 15) & ~(size_t)15;
+        const uint8_t* plane[PC_MAX_TARGETS] = {};
+        int masked = 0;
+        for (int t = 0; t < n_targets; t++) masked += targets[t]->mask_on ? 1 : 0;
+        if (margin > 0 && masked > 0) PC_HIP(ctx->lk_choked.ensure((size_t)masked * plane_bytes + 16));
+        for (int t = 0, k = 0; t < n_targets; t++) {
+            if (!targets[t]->mask_on) continue;
+            plane[t] = targets[t]->d_mask;
+            if (margin > 0) {
+                uint8_t* const choked = ctx->lk_choked.p + (size_t)(k++) * plane_bytes;
+                pc::launch_mask_choke(targets[t]->d_mask, choked, frame1->w, frame1->h, margin, ctx->stream);
+                plane[t] = choked;
+            }
+        }
+        PC_HIP(hipGetLastError());
+        if ((rc = run_lk_target_mask(ctx, frame1, plane, n_targets)) != PC_OK) return rc;
+    }
     const bool fb = fb_threshold > 0.0;
     if (rows > 0 && !fb) {
         if (back_xy) std::memset(back_xy, 0, rows * sizeof(float2));
@@ -1325,13 +1395,18 @@ static int lk_track_impl(pc_context* ctx, const pc_frame* frame1, const pc_frame
 
 int pc_lk_track(pc_context* ctx, const pc_frame* frame1, const pc_frame* const* targets, int n_targets,
                 const pc_flow_options* opt, float* next_xy, uint8_t* status, float* err) {
-    return lk_track_impl(ctx, frame1, targets, n_targets, opt, 0.0, next_xy, status, err, nullptr, nullptr);
+    return lk_track_impl(ctx, frame1, targets, n_targets, opt, 0.0, -1, next_xy, status, err, nullptr, nullptr);
 }
 
 int pc_lk_track_fb(pc_context* ctx, const pc_frame* frame1, const pc_frame* const* targets, int n_targets,
                    const pc_flow_options* opt, double fb_threshold, float* next_xy, uint8_t* status, float* err,
                    float* back_xy, uint8_t* back_status) {
-    return lk_track_impl(ctx, frame1, targets, n_targets, opt, fb_threshold, next_xy, status, err, back_xy, back_status);
+    return lk_track_impl(ctx, frame1, targets, n_targets, opt, fb_threshold, -1, next_xy, status, err, back_xy, back_status);
+}
+
+int pc_lk_track_masked(pc_context* ctx, const pc_frame* frame1, const pc_frame* const* targets, int n_targets,
+                       const pc_flow_options* opt, double fb_threshold, int margin, float* next_xy, uint8_t* status, float* err) {
+    return lk_track_impl(ctx, frame1, targets, n_targets, opt, fb_threshold, margin, next_xy, status, err, nullptr, nullptr);
 }
 
 static int lk_track_filtered_impl(pc_context* ctx, const pc_frame* frame1, const pc_frame* const* targets, int n_targets,

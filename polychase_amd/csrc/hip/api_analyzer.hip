@@ -104,6 +104,10 @@ struct pc_analyzer {
     int puts = 0;
     bool host_records = true;            // download every job's records to pinned host memory
     double fb_threshold = 0.0;           // forward-backward check of the jobs submitted from now on (0: off)
+    // Target-side masks (pc_analyzer_set_target_mask_margin): -1 off, else the margin of the frames put from now on.  While it is
+    // >= 0 and a mask is in force every frame put takes the mask -- pc_frame::target_margin is the frame's role as a target,
+    // beside mask_on, which stays the detection's -- and with a margin > 0 its choked plane too.
+    int target_margin = -1;
     // Detection mask of the frames put from now on with will_detect (pc_analyzer_set_mask).  The mask a detection reads is the
     // plane of its own slot's frame, filled on the preparation stream when the frame is put: a detection already enqueued keeps
     // the mask it was enqueued with.  A host mask is copied at once into one of kMaskGens pinned buffers, used in turn, so that
@@ -305,7 +309,10 @@ int pc_analyzer_reset(pc_analyzer* a) {
         s.frame_id = 0;
         s.last_read[0] = s.last_read[1] = nullptr;
         s.scratch.cleared = false;
-        if (s.frame) s.frame->mask_on = false;
+        if (s.frame) {
+            s.frame->mask_on = false;
+            s.frame->target_margin = -1;
+        }
     }
     a->mask_kind = 0;
     a->mask_dev = nullptr;
@@ -347,20 +354,32 @@ static int analyzer_put(pc_analyzer* a, int32_t frame_id, const uint8_t* rgb, si
     }
     // the mask of this frame's detection, into the slot's own plane, in front of img_ready: pc_analyzer_frame_ingested then
     // also says that a device mask has been read
+    // With a target-side margin every frame takes the mask, as a target; its detection reads the plane as before: iff will_detect.
+    const bool as_target = a->target_margin >= 0 && a->mask_kind != 0;
+    const bool take_mask = will_detect || as_target;
     s.frame->mask_on = false;
-    if (will_detect && a->mask_kind == 1) {
+    s.frame->target_margin = -1;
+    if (take_mask && a->mask_kind == 1) {
         // TODO(mask-upload): a static mask is uploaded again for every detected frame (w * h bytes; measured -16 % on a whole
         // 1080p call for an all-on mask, DESIGN.md section 7 "Open follow-ups"): skip the copy when the slot's plane holds this mask
         const int g = a->mask_gen;
         if ((rc = upload_mask(s.frame, a->mask_host[g].p, (size_t)a->w, PC_FRAME_PINNED_HOST, a->ctx->prep_stream)) != PC_OK) return rc;
         PC_HIP(hipEventRecord(a->mask_copied[g], a->ctx->prep_stream));
-    } else if (will_detect && a->mask_kind == 2) {
+    } else if (take_mask && a->mask_kind == 2) {
         if ((rc = upload_mask(s.frame, a->mask_dev, a->mask_dev_pitch, 1, a->ctx->prep_stream)) != PC_OK) return rc;
-    } else if (will_detect && a->mask_kind == 3) {
+    } else if (take_mask && a->mask_kind == 3) {
         const int g = a->poly_gen;
         if ((rc = fill_mask_polygons(s.frame, a->poly_dev[g].p, a->poly_vertices, a->poly_polygons, a->poly_invert, a->ctx->prep_stream)) != PC_OK)
             return rc;
         PC_HIP(hipEventRecord(a->poly_read[g], a->ctx->prep_stream));
+    }
+    if (as_target) {
+        s.frame->mask_on = will_detect != 0;
+        if (a->target_margin > 0) {   // (the slot's choked plane exists: ensure_target_planes ran when margin and mask met)
+            pc::launch_mask_choke(s.frame->d_mask, s.frame->d_choked, a->w, a->h, a->target_margin, a->ctx->prep_stream);
+            PC_HIP(hipGetLastError());
+        }
+        s.frame->target_margin = a->target_margin;
     }
     PC_HIP(hipEventRecord(s.img_ready, a->ctx->prep_stream));
     s.frame_id = frame_id;
@@ -510,6 +529,13 @@ int pc_analyzer_submit(pc_analyzer* a, int32_t frame1, const int32_t* targets, i
             a->gate_armed = true;
         }
         if ((rc = run_lk(ctx, s1->frame, tg, n_targets, &a->fopt, lane)) != PC_OK) return rc;
+        // target-side masks: rows that end where their target's plane is off are dropped before the backward launch looks at them
+        {
+            const uint8_t* plane[PC_MAX_TARGETS] = {};
+            for (int t = 0; t < n_targets; t++)
+                if (tg[t]->target_margin >= 0) plane[t] = tg[t]->target_margin > 0 ? tg[t]->d_choked : tg[t]->d_mask;
+            if ((rc = run_lk_target_mask(ctx, s1->frame, plane, n_targets, lane)) != PC_OK) return rc;
+        }
         // forward-backward check: the backward launch follows on the same lane and rewrites the status of the records the
         // compaction below filters; the gate is the forward launch's alone
         if (a->fb_threshold > 0.0 && (rc = run_lk_fb(ctx, s1->frame, tg, n_targets, &a->fopt, a->fb_threshold, lane)) != PC_OK) return rc;
@@ -599,6 +625,22 @@ int pc_analyzer_set_fb_threshold(pc_analyzer* a, double fb_threshold) {
     return PC_OK;
 }
 
+// the choked planes of every slot, when frames put from now on will need them: an allocation inside the running pipeline would stall it
+static int ensure_target_planes(pc_analyzer* a) {
+    if (a->target_margin <= 0 || a->mask_kind == 0) return PC_OK;
+    for (auto& s : a->slots)
+        if (int rc = ensure_choked_plane(s.frame)) return rc;
+    return PC_OK;
+}
+
+int pc_analyzer_set_target_mask_margin(pc_analyzer* a, int margin) {
+    if (int rc = check_target_margin(margin, true)) return rc;   // first: a margin is refused whatever the handle
+    if (!a) return fail(PC_E_INVALID, "null analyzer");
+    a->target_margin = margin;
+    if (margin > 0 && a->mask_kind != 0) PC_HIP(hipSetDevice(a->ctx->device));
+    return ensure_target_planes(a);
+}
+
 int pc_analyzer_set_mask(pc_analyzer* a, const uint8_t* mask, size_t row_pitch, int on_device) {
     if (!a) return fail(PC_E_INVALID, "null analyzer");
     if (!mask) {
@@ -615,7 +657,7 @@ int pc_analyzer_set_mask(pc_analyzer* a, const uint8_t* mask, size_t row_pitch, 
         a->mask_kind = 2;
         a->mask_dev = mask;
         a->mask_dev_pitch = row_pitch;
-        return PC_OK;
+        return ensure_target_planes(a);
     }
     const int g = (a->mask_gen + 1) % pc_analyzer::kMaskGens;
     if (!a->mask_copied[g]) PC_HIP(hipEventCreateWithFlags(&a->mask_copied[g], hipEventDisableTiming));
@@ -625,7 +667,7 @@ int pc_analyzer_set_mask(pc_analyzer* a, const uint8_t* mask, size_t row_pitch, 
     a->mask_gen = g;
     a->mask_kind = 1;
     a->mask_dev = nullptr;
-    return PC_OK;
+    return ensure_target_planes(a);
 }
 
 int pc_analyzer_set_mask_polygons(pc_analyzer* a, const float* xy, const int32_t* counts, int n_polygons, int invert) {
@@ -655,7 +697,7 @@ int pc_analyzer_set_mask_polygons(pc_analyzer* a, const float* xy, const int32_t
     a->poly_invert = invert ? 1 : 0;
     a->mask_kind = 3;
     a->mask_dev = nullptr;
-    return PC_OK;
+    return ensure_target_planes(a);
 }
 
 int pc_analyzer_device_log_used(const pc_analyzer* a, size_t* bytes) {

@@ -82,6 +82,13 @@ int run_lk(pc_context* ctx, const pc_frame* frame1, const pc_frame* const* targe
 int check_fb_threshold(double fb_threshold);
 int run_lk_fb(pc_context* ctx, const pc_frame* frame1, const pc_frame* const* targets, int n_targets, const pc_flow_options* opt,
               double fb_threshold, int set = 0, float2* back_xy = nullptr, uint8_t* back_status = nullptr);
+// target-side masks (include/polychase_hip.h: pc_lk_track_masked).  check_target_margin: -1 (only with allow_off) .. 31;
+// ensure_choked_plane allocates pc_frame::d_choked (once); run_lk_target_mask drops, on the lane of set `set`, the records
+// run_lk has just left there that end where the plane of their target is off (plane[t] null: target t keeps its rows; all null:
+// nothing is enqueued)
+int check_target_margin(int margin, bool allow_off);
+int ensure_choked_plane(pc_frame* f);
+int run_lk_target_mask(pc_context* ctx, const pc_frame* frame1, const uint8_t* const* plane, int n_targets, int set = 0);
 // gray (+ pyramid) of a frame from u8 gray / u8 RGB / float32 RGB(A) pixels, host or device, on the work stream
 // `clear` (may be null): clear_words words zeroed in front of the frame's kernels (by the level-0 kernel where there is one)
 int set_image(pc_context* ctx, pc_frame* f, const uint8_t* src, size_t row_pitch, int on_device, int channels, int elem_size = 1,

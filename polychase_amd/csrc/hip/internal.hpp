@@ -205,6 +205,7 @@ struct pc_context {
     DevBuf<float> lk_cerr;
     DevBuf<float2> lk_back_xy;             // pc_lk_track_fb: backward end points / status, [target][n]
     DevBuf<uint8_t> lk_back_status;
+    DevBuf<uint8_t> lk_choked;             // pc_lk_track_masked, pc_frame_download_choked_mask: the targets' choked planes
     DevBuf<uint32_t> lk_cidx, lk_block_counts[2], lk_perm, lk_hist;
     DevBuf<uint32_t> lk_gate;              // LKParams::gate of the analyzer's launches (one word)
     PinBuf<uint32_t> lk_gate_timed_out;    // raised by a gate kernel that gave up (its stream shares a hardware queue with the other lane)
@@ -245,5 +246,10 @@ struct pc_frame {
     // mask_on: the next detection of this frame honours it
     uint8_t* d_mask = nullptr;
     bool mask_on = false;
+    // target-side mask of a frame in an analyzer's ring (pc_analyzer_set_target_mask_margin): the margin the frame was put under
+    // while a mask was in force -- rows that end in this frame are judged by d_mask (0) or by d_choked, its choked plane (> 0) --
+    // or -1: the frame keeps every row.  d_choked is allocated the first time an analyzer needs it.
+    int target_margin = -1;
+    uint8_t* d_choked = nullptr;
 };
 

@@ -140,6 +140,19 @@ constexpr int kPolyMaxPolygons = 32, kPolyMaxVertices = 4096;
 constexpr int kPolyVertsAt = 64;
 constexpr int kPolyWords = kPolyVertsAt + 2 * kPolyMaxVertices;
 void launch_polygon_mask(const int32_t* poly, int n_vertices, int n_polygons, int invert, uint8_t* mask, int w, int h, hipStream_t s);
+// Target-side masks.  launch_mask_choke: `choked` (w x h packed bytes, written whole, 255 / 0) = the mask plane eroded by a
+// (2 margin + 1)-pixel square, pixels outside the frame counting as on; margin 0 .. 31 (0: the on/off image).
+void launch_mask_choke(const uint8_t* mask, uint8_t* choked, int w, int h, int margin, hipStream_t s);
+// launch_lk_target_mask: clears the status of the forward launch's records (LKParams::out_rec, n slots of 8) whose end point's
+// pixel is 0 in the plane of their target; plane[t] null: target t keeps its rows.
+struct TargetMaskParams {
+    const uint8_t* plane[8];
+    float4* rec;
+    int n, n_targets;
+    int w, h;
+    int hi_prio;    // filled in by the launcher
+};
+void launch_lk_target_mask(TargetMaskParams p, hipStream_t s);
 
 // ---- kernels_lk.hip (launch_lk, the plain cross-check kernel, binning, gate, compaction), kernels_lk3.hip, kernels_lk4{a,b,c}.hip ----
 constexpr int kMaxLevels = 16;   // == PC_MAX_LEVELS (internal.hpp asserts it)

@@ -1,6 +1,6 @@
 // kernels_mask.hip -- the detection mask's plane (kernels_gftt.hip: the MASKED variants read it) rasterised on gfx950 from
 // polygon outlines (include/polychase_hip.h: pc_frame_set_mask_polygons states the fill rule; DESIGN.md section 4 "Polygon
-// masks").
+// masks").  Further down: the choked plane of a mask and the test of the forward records against it ("Target-side masks").
 //
 // The rule is integer.  Vertices arrive snapped to sixteenths of a pixel (|X|, |Y| <= 2^19); pixel (px, py) is the point
 // P = (16 px, 16 py).  An edge A -> B is crossed at P when (Ay <= Py) != (By <= Py), and lies to the right of P when
@@ -132,6 +132,117 @@ void launch_polygon_mask(const int32_t* poly, int n_vertices, int n_polygons, in
     const dim3 grid((w + kPolyTileW - 1) / kPolyTileW, (h + kPolyTileH - 1) / kPolyTileH);
     hipLaunchKernelGGL(polygon_mask_kernel, grid, dim3(256), 0, s, poly, reinterpret_cast<const int2*>(poly + kPolyVertsAt), n_vertices, n_polygons,
                        invert, mask, w, h, helper_prio_arg());
+}
+
+// ---- target-side masks (DESIGN.md section 4 "Target-side masks") ----
+//
+// mask_choke_kernel: the choked plane C_r of a mask plane -- out(x, y) = 255 when every pixel of the frame within r of (x, y) in
+// both axes is on (byte != 0), else 0; pixels outside the frame count as on.  The structuring element is a square, so the erosion
+// is a row pass followed by a column pass, and both run on BITS:
+//   row pass     a wavefront takes one row of the tile with its halo, kChokeTileW + 2 r <= 126 pixels.  Two ballots turn the
+//                row's bytes into a 128-bit word X (bit k: column x0 - r + k); Y = AND over k in [0, 2 r] of X >> k, by doubling
+//                (a handful of wave-uniform shifts), has in bit i the answer for column x0 + i.  Its low 64 bits go to LDS, one
+//                word per row: (kChokeTileH + 62) * 8 = 752 bytes.  The zeros a right shift brings in at bit 127 travel 2 r <= 62
+//                bits down and never reach bit 63.
+//   column pass  the lane of output row t and byte octet q ANDs the 2 r + 1 words of rows t .. t + 2 r (eight lanes read one
+//                address: a broadcast) and expands its eight bits to bytes.
+// One launch, every loop bounded by r, no workgroup waits for another, each byte of the output written exactly once.  r = 0 is
+// accepted as well and gives the on/off image of the input.
+constexpr int kChokeTileW = 64, kChokeTileH = 32;   // one ballot wide; 256 lanes x 8 pixels
+constexpr int kChokeMaxMargin = 31;
+static_assert(kChokeTileW == 64, "a row of the tile is one ballot");
+static_assert(kChokeTileW + 2 * kChokeMaxMargin <= 128, "a row of the tile with its halo is two ballots");
+static_assert(kChokeTileH * (kChokeTileW / 8) == 256, "a lane owns eight pixels of one row");
+
+__device__ __forceinline__ void shr128(unsigned long long& hi, unsigned long long& lo, int k) {   // 0 <= k < 64
+    if (k == 0) return;
+    lo = (lo >> k) | (hi << (64 - k));
+    hi >>= k;
+}
+
+__global__ __launch_bounds__(256) void mask_choke_kernel(const uint8_t* __restrict__ in, uint8_t* __restrict__ out, int w, int h, int r,
+                                                         int hi_prio) {
+    helper_priority(hi_prio);
+    __shared__ unsigned long long s_row[kChokeTileH + 2 * kChokeMaxMargin];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int x0 = blockIdx.x * kChokeTileW, y0 = blockIdx.y * kChokeTileH;
+    r = min(max(r, 0), kChokeMaxMargin);
+    const int rows_in = kChokeTileH + 2 * r, window = 2 * r + 1;
+
+    for (int j = wave; j < rows_in; j += 4) {   // whole wavefronts: j is uniform
+        const int y = y0 - r + j;
+        const bool row_in = y >= 0 && y < h;
+        const int c0 = x0 - r + lane, c1 = c0 + 64;
+        bool on0 = true, on1 = true;            // outside the frame: on
+        if (row_in && c0 >= 0 && c0 < w) on0 = in[(size_t)y * w + c0] != 0;
+        if (row_in && lane < 2 * r && c1 < w) on1 = in[(size_t)y * w + c1] != 0;   // c1 >= 64 - r > 0
+        unsigned long long lo = __ballot(on0), hi = __ballot(on1);
+        int len = 1;
+        while (2 * len <= window) {
+            unsigned long long h2 = hi, l2 = lo;
+            shr128(h2, l2, len);
+            hi &= h2;
+            lo &= l2;
+            len *= 2;
+        }
+        if (len < window) {
+            unsigned long long h2 = hi, l2 = lo;
+            shr128(h2, l2, window - len);
+            lo &= l2;
+        }
+        if (lane == 0) s_row[j] = lo;
+    }
+    __syncthreads();
+
+    const int t = tid >> 3, q = tid & 7;
+    const int x = x0 + 8 * q, y = y0 + t;
+    if (x >= w || y >= h) return;
+    unsigned long long z = s_row[t];
+    for (int k = 1; k < window; k++) z &= s_row[t + k];
+    const uint32_t bits8 = (uint32_t)(z >> (8 * q)) & 255u;
+#pragma unroll
+    for (int half = 0; half < 2; half++) {
+        const uint32_t bits = (bits8 >> (4 * half)) & 15u;
+        // bit k -> byte k = 255
+        const uint32_t word = ((bits & 1u) | ((bits & 2u) << 7) | ((bits & 4u) << 14) | ((bits & 8u) << 21)) * 255u;
+        const int xq = x + 4 * half;
+        const size_t at = (size_t)y * w + xq;
+        if (xq + 3 < w && (at & 3) == 0) {
+            *reinterpret_cast<uint32_t*>(out + at) = word;
+        } else {
+            for (int k = 0; k < 4 && xq + k < w; k++) out[at + k] = (uint8_t)(word >> (8 * k));
+        }
+    }
+}
+
+void launch_mask_choke(const uint8_t* mask, uint8_t* choked, int w, int h, int margin, hipStream_t s) {
+    const dim3 grid((w + kChokeTileW - 1) / kChokeTileW, (h + kChokeTileH - 1) / kChokeTileH);
+    hipLaunchKernelGGL(mask_choke_kernel, grid, dim3(256), 0, s, mask, choked, w, h, margin, helper_prio_arg());
+}
+
+// lk_target_mask_kernel: one lane per raw record of the forward launch.  A record with status 1 whose target holds a plane is
+// judged by the plane's byte at its end point's pixel (include/polychase_hip.h: pc_lk_track_masked has the rounding); a zero
+// clears the status word, as lk_fb_kernel does.  End point and error stay.
+__global__ __launch_bounds__(256) void lk_target_mask_kernel(const TargetMaskParams p) {
+    helper_priority(p.hi_prio);
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (size_t)p.n * kRecStride) return;
+    const int tgt = (int)(i & (kRecStride - 1));
+    if (tgt >= p.n_targets) return;
+    const uint8_t* const plane = p.plane[tgt];
+    if (!plane) return;
+    const float4 rec = p.rec[i];
+    if (__float_as_uint(rec.w) != 1u) return;
+    const int ix = (int)fminf(fmaxf(floorf(rec.x + 0.5f), 0.f), (float)(p.w - 1));   // a NaN lands on 0
+    const int iy = (int)fminf(fmaxf(floorf(rec.y + 0.5f), 0.f), (float)(p.h - 1));
+    if (plane[(size_t)iy * p.w + ix] == 0) p.rec[i].w = __uint_as_float(0u);
+}
+
+void launch_lk_target_mask(TargetMaskParams p, hipStream_t s) {
+    if (p.n <= 0 || p.n_targets <= 0) return;
+    p.hi_prio = helper_prio_arg();
+    const size_t lanes = (size_t)p.n * kRecStride;
+    hipLaunchKernelGGL(lk_target_mask_kernel, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, s, p);
 }
 
 }  // namespace pc

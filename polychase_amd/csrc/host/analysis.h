@@ -10,6 +10,7 @@
 #include <functional>
 #include <memory>
 #include <optional>
+#include <stdexcept>
 #include <string>
 #include <vector>
 
@@ -38,7 +39,16 @@ struct OpticalFlowOptions {
     double min_eigen_threshold = 1e-4;
     // not in the reference: forward-backward check (include/polychase_hip.h: pc_lk_track_fb), pixels at level 0; 0 = off
     double forward_backward_threshold = 0.0;
+    // not in the reference: target-side masks (include/polychase_hip.h: pc_lk_track_masked).  -1 = off; 0..31: a flow row is
+    // dropped when its end point lies where the detection mask of its TARGET frame, choked by this many pixels, is off.  Does
+    // nothing without a detection_mask.
+    int target_mask_margin = -1;
 };
+// std::invalid_argument for what no run accepts; every entry point calls it before it asks for a frame
+inline void CheckOpticalFlowOptions(const OpticalFlowOptions& o) {
+    if (o.target_mask_margin < -1 || o.target_mask_margin > 31)
+        throw std::invalid_argument("target_mask_margin must be -1 (off) or 0..31, got " + std::to_string(o.target_mask_margin));
+}
 
 // The clip: frames first_frame .. first_frame + num_frames - 1, all width x height.
 struct VideoInfo {
@@ -89,7 +99,11 @@ struct MaskView {
 // Either one mask for every frame the run detects (`fixed`), or a function asked once per such frame (`per_frame`; nothing =
 // that frame is detected without a mask); empty = no mask.  Asked only for frames that WILL be detected: not for the halo
 // frames of a shard, and not for frames whose `keypoints` row exists -- a resumed run keeps the stored keypoints whatever mask
-// is passed.  The mask is not stored in the database.  A mask of another size than the clip: std::invalid_argument.
+// is passed.  With OpticalFlowOptions::target_mask_margin >= 0 the mask also judges the rows that END in a frame, so per_frame
+// is then asked once for EVERY frame the run puts, in order -- halo frames and frames with stored keypoints included (their
+// detection, if any, still runs without it) -- and nothing = rows into that frame are all kept.  A resumed run keeps the flow
+// rows already stored, whatever margin they were made under.  The mask is not stored in the database.  A mask of another size
+// than the clip: std::invalid_argument.
 struct DetectionMask {
     std::optional<MaskView> fixed;
     std::function<std::optional<MaskView>(int32_t frame_id)> per_frame;

@@ -350,6 +350,7 @@ static void RunAnalysis(const VideoInfo& video_info, FrameAccessorFunction frame
                         const GFTTOptions& detector_options, const OpticalFlowOptions& flow_options,
                         OpticalFlowRunStats* stats, OpticalFlowShard* shard, bool write_images, const DetectionMask& detection_mask) {
     CHECK(frame_accessor);
+    CheckOpticalFlowOptions(flow_options);
     auto check_mask = [&](const MaskView& m) {
         if (m.polygons) return;   // any size of frame; the engine refuses bad polygons
         if (!m.data || m.rows != static_cast<int>(video_info.height) || m.cols != static_cast<int>(video_info.width) ||
@@ -430,6 +431,9 @@ static void RunAnalysis(const VideoInfo& video_info, FrameAccessorFunction frame
     Engine& eng = *engine;
     // set on every run: a parked engine may have served another threshold (the cache is not keyed on it)
     if (pc_analyzer_set_fb_threshold(eng.an, flow_options.forward_backward_threshold) != PC_OK) ThrowHip("pc_analyzer_set_fb_threshold");
+    // ... the target-side margin, off without a mask to choke ...
+    const int target_margin = detection_mask.empty() ? -1 : flow_options.target_mask_margin;
+    if (pc_analyzer_set_target_mask_margin(eng.an, target_margin) != PC_OK) ThrowHip("pc_analyzer_set_target_mask_margin");
     // ... and so is the detection mask: the run's one mask, or none until the first frame's is asked for
     auto set_mask = [&](const std::optional<MaskView>& m) {
         if (m) check_mask(*m);
@@ -631,14 +635,16 @@ static void RunAnalysis(const VideoInfo& video_info, FrameAccessorFunction frame
                 std::lock_guard<std::mutex> lk(db_mtx);
                 will_detect = !db->KeypointsExist(fid);
             }
-            // the mask of this frame's detection (asked only for frames that are detected); a device mask is read when the
-            // frame is put, so its owner waits with the frame's for pc_analyzer_frame_ingested
+            // the mask of this frame's detection (asked only for frames that are detected) and, under a target-side margin, of
+            // the rows that end in it (asked for every frame: the halo of a shard and frames with stored keypoints too); a device
+            // mask is read when the frame is put, so its owner waits with the frame's for pc_analyzer_frame_ingested
             std::shared_ptr<void> mask_owner;
-            if (will_detect && detection_mask.per_frame) {
+            const bool takes_mask = will_detect || target_margin >= 0;
+            if (takes_mask && detection_mask.per_frame) {
                 std::optional<MaskView> m = detection_mask.per_frame(fid);
                 set_mask(m);
                 if (m && m->on_device) mask_owner = std::move(m->owner);
-            } else if (will_detect && detection_mask.fixed && detection_mask.fixed->on_device) {
+            } else if (takes_mask && detection_mask.fixed && detection_mask.fixed->on_device) {
                 mask_owner = detection_mask.fixed->owner;
             }
             static const bool ingest_dma = !(std::getenv("POLYCHASE_INGEST_DMA") && std::atoi(std::getenv("POLYCHASE_INGEST_DMA")) == 0);
@@ -740,6 +746,7 @@ void GenerateOpticalFlowDatabase(const VideoInfo& video_info, FrameAccessorFunct
 void GenerateOpticalFlowShard(const VideoInfo& video_info, FrameAccessorFunction frame_accessor, OpticalFlowProgressCallback callback,
                               const std::string& database_path, OpticalFlowShard& shard, const GFTTOptions& detector_options,
                               const OpticalFlowOptions& flow_options, OpticalFlowRunStats* stats, const DetectionMask& detection_mask) {
+    CheckOpticalFlowOptions(flow_options);   // a bad option is the caller's error whatever else is wrong
     CHECK(shard.begin <= shard.end);
     CHECK(shard.device_log != nullptr || !database_path.empty());
     shard.used_bytes = 0;
@@ -752,6 +759,7 @@ size_t GenerateOpticalFlowRecords(const VideoInfo& video_info, FrameAccessorFunc
                                   OpticalFlowProgressCallback callback, int32_t shard_begin, int32_t shard_end,
                                   void* device_log, size_t capacity_bytes, const GFTTOptions& detector_options,
                                   const OpticalFlowOptions& flow_options, OpticalFlowRunStats* stats, const DetectionMask& detection_mask) {
+    CheckOpticalFlowOptions(flow_options);
     CHECK(device_log != nullptr);
     OpticalFlowShard shard;
     shard.begin = shard_begin;

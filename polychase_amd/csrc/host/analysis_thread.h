@@ -30,6 +30,7 @@ class OpticalFlowThread : public Worker<OpticalFlowThreadMessage> {
    public:
     OpticalFlowThread(VideoInfo video_info, std::string database_path, GFTTOptions detector_options = {},
                       OpticalFlowOptions flow_options = {}, bool write_images = false, DetectionMask detection_mask = {}) {
+        CheckOpticalFlowOptions(flow_options);   // here, not on the worker: the caller gets the exception
         // (the message protocol has no request for a mask: one mask for the whole clip, or a per_frame that needs no Python --
         // the bindings copy a dict of polygon masks into one)
         Start(

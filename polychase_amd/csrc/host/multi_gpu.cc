@@ -250,6 +250,7 @@ MultiGpuResult GenerateOpticalFlowDatabaseMultiGpu(const VideoInfo& video_info, 
                                                    OpticalFlowProgressCallback callback, const std::string& database_path,
                                                    const MultiGpuConfig& cfg, const GFTTOptions& detector_options,
                                                    const OpticalFlowOptions& flow_options, const DetectionMask& detection_mask) {
+    CheckOpticalFlowOptions(flow_options);   // before any rank connects or asks for a frame
     const int world = cfg.world_size, rank = cfg.rank;
     if (world < 1 || rank < 0 || rank >= world) Fail("rank " + std::to_string(rank) + " of " + std::to_string(world));
     if (cfg.transport != "rccl" && cfg.transport != "tcp") Fail("transport must be rccl or tcp");

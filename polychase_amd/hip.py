@@ -29,6 +29,7 @@ SYMBOLS = [
     "pc_frame_download_deriv", "pc_frame_download_level16", "pc_frame_detect", "pc_frame_download_min_eig", "pc_frame_num_candidates",
     "pc_frame_num_keypoints", "pc_frame_download_keypoints", "pc_frame_set_keypoints", "pc_frame_set_mask",
     "pc_frame_set_mask_polygons", "pc_frame_download_mask", "pc_analyzer_set_mask_polygons",
+    "pc_frame_download_choked_mask", "pc_lk_track_masked", "pc_analyzer_set_target_mask_margin",
     "pc_lk_track", "pc_lk_track_filtered", "pc_lk_track_fb", "pc_lk_track_filtered_fb",
     "pc_analyzer_create", "pc_analyzer_destroy", "pc_analyzer_reset", "pc_analyzer_put_frame", "pc_analyzer_put_frame_f32",
     "pc_analyzer_has_frame", "pc_analyzer_frame_ingested",
@@ -142,6 +143,7 @@ def load():
     L.pc_frame_set_mask.argtypes = [vp, vp, vp, C.c_size_t, C.c_int]
     L.pc_frame_set_mask_polygons.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int]
     L.pc_frame_download_mask.argtypes = [vp, vp, vp]
+    L.pc_frame_download_choked_mask.argtypes = [vp, vp, C.c_int, vp]
     L.pc_frame_download_min_eig.argtypes = [vp, vp, vp]
     L.pc_frame_num_candidates.argtypes = [vp, vp, ip]
     L.pc_frame_num_keypoints.argtypes = [vp, vp, ip]
@@ -151,6 +153,7 @@ def load():
     L.pc_lk_track_filtered.argtypes = [vp, vp, C.POINTER(vp), C.c_int, C.POINTER(FlowOptions), vp, vp, vp, vp]
     L.pc_lk_track_fb.argtypes = [vp, vp, C.POINTER(vp), C.c_int, C.POINTER(FlowOptions), C.c_double, vp, vp, vp, vp, vp]
     L.pc_lk_track_filtered_fb.argtypes = [vp, vp, C.POINTER(vp), C.c_int, C.POINTER(FlowOptions), C.c_double, vp, vp, vp, vp]
+    L.pc_lk_track_masked.argtypes = [vp, vp, C.POINTER(vp), C.c_int, C.POINTER(FlowOptions), C.c_double, C.c_int, vp, vp, vp]
     L.pc_analyzer_create.argtypes = [vp, C.c_int, C.c_int, C.POINTER(GfttOptions), C.POINTER(FlowOptions), C.c_int,
                                      C.c_int, C.POINTER(vp)]
     L.pc_analyzer_destroy.argtypes = [vp]
@@ -171,6 +174,7 @@ def load():
     L.pc_analyzer_set_fb_threshold.argtypes = [vp, C.c_double]
     L.pc_analyzer_set_mask.argtypes = [vp, vp, C.c_size_t, C.c_int]
     L.pc_analyzer_set_mask_polygons.argtypes = [vp, vp, vp, C.c_int, C.c_int]
+    L.pc_analyzer_set_target_mask_margin.argtypes = [vp, C.c_int]
     L.pc_peer_buffer_alloc.argtypes = [C.c_int, C.c_size_t, C.POINTER(vp)]
     L.pc_peer_buffer_free.argtypes = [C.c_int, vp]
     L.pc_peer_buffer_export.argtypes = [C.c_int, vp, C.c_char_p]
@@ -329,6 +333,7 @@ def _mask_ptr(mask, w: int, h: int):
 
 
 MASK_MAX_POLYGONS, MASK_MAX_VERTICES, MASK_SUBPIXEL = 32, 4096, 16   # PC_MASK_* of include/polychase_hip.h
+TARGET_MASK_MAX_MARGIN = 31   # PC_TARGET_MASK_MAX_MARGIN
 
 
 def _polygon_arrays(polys):
@@ -438,6 +443,13 @@ class Frame:
         _check(load().pc_frame_download_mask(self.ctx._h, self._h, out.ctypes.data))
         return out
 
+    def choked_mask(self, margin: int) -> np.ndarray:
+        """The choked plane of the mask in force, uint8 (H, W), 255 / 0: on where every pixel of the frame within `margin` in
+        both axes is on (pc_frame_download_choked_mask); margin 0..31."""
+        out = np.empty((self.h, self.w), np.uint8)
+        _check(load().pc_frame_download_choked_mask(self.ctx._h, self._h, int(margin), out.ctypes.data))
+        return out
+
     def detect(self, opt: GfttOptions | None = None):
         opt = opt or gftt_options()
         _check(load().pc_frame_detect(self.ctx._h, self._h, C.byref(opt)))
@@ -518,6 +530,21 @@ def lk_track_fb(ctx: Context, frame1: Frame, targets: list[Frame], fb_threshold:
     return xy, st, err, bxy, bst
 
 
+def lk_track_masked(ctx: Context, frame1: Frame, targets: list[Frame], fb_threshold: float, margin: int, opt: FlowOptions | None = None):
+    """lk_track_fb without the back outputs, plus the target-side mask test (include/polychase_hip.h: pc_lk_track_masked): a row
+    whose end point lies where the choked mask of its target is off gets status 0; a target without a mask keeps its rows.
+    margin -1: lk_track_fb.  -> next_xy [T,N,2], final status [T,N], err [T,N]."""
+    opt = opt or flow_options()
+    n, t = frame1.num_keypoints, len(targets)
+    xy = np.zeros((t, n, 2), np.float32)
+    st = np.zeros((t, n), np.uint8)
+    err = np.zeros((t, n), np.float32)
+    arr = (C.c_void_p * t)(*[f._h for f in targets])
+    _check(load().pc_lk_track_masked(ctx._h, frame1._h, arr, t, C.byref(opt), float(fb_threshold), int(margin), xy.ctypes.data,
+                                     st.ctypes.data, err.ctypes.data))
+    return xy, st, err
+
+
 def lk_track_filtered_fb(ctx: Context, frame1: Frame, targets: list[Frame], fb_threshold: float, opt: FlowOptions | None = None):
     """lk_track_filtered on the final status of the forward-backward check (pc_lk_track_filtered_fb)."""
     opt = opt or flow_options()
@@ -548,6 +575,7 @@ class Analyzer:
         self._h = C.c_void_p()
         self._keep = {}
         self._keep_mask, self._keep_masks = None, {}   # the device mask in force / per ring slot, of the frame put under it
+        self._target_margin = -1
         _check(load().pc_analyzer_create(ctx._h, width, height, C.byref(self.gftt), C.byref(self.flow), ring_frames,
                                          max_jobs, C.byref(self._h)))
         self.ring = ring_frames
@@ -584,7 +612,7 @@ class Analyzer:
             self._keep[frame_id % self.ring] = rgb  # device sources must outlive the async kernels
         # ... and so must the device mask this frame's detection copies: until the slot takes its next frame, whatever
         # set_mask is given in between
-        self._keep_masks[frame_id % self.ring] = self._keep_mask if will_detect else None
+        self._keep_masks[frame_id % self.ring] = self._keep_mask if will_detect or self._target_margin >= 0 else None
 
     def has_frame(self, frame_id: int) -> bool:
         return bool(load().pc_analyzer_has_frame(self._h, frame_id))
@@ -624,6 +652,12 @@ class Analyzer:
     def set_fb_threshold(self, fb_threshold: float):
         """forward-backward check for the jobs submitted from now on; 0 = off (pc_analyzer_set_fb_threshold)"""
         _check(load().pc_analyzer_set_fb_threshold(self._h, float(fb_threshold)))
+
+    def set_target_mask_margin(self, margin: int):
+        """target-side masks for the frames put from now on: -1 = off, 0..31 = the margin (pc_analyzer_set_target_mask_margin);
+        every frame put then takes the mask in force, and rows that end where its choked plane is off are dropped"""
+        _check(load().pc_analyzer_set_target_mask_margin(self._h, int(margin)))
+        self._target_margin = int(margin)
 
     def set_mask(self, mask):
         """Detection mask of the frames put from now on with will_detect (pc_analyzer_set_mask): uint8 (H, W), non-zero =

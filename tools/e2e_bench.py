@@ -2,7 +2,8 @@
 """End-to-end rates of GenerateOpticalFlowDatabase through the polychase_core module (what the Blender
 addon experiences), next to bench.py's HBM-resident number.  Not the headline metric.
 
-  python tools/e2e_bench.py [--config c2|c3] [--frames 60] [--mask-fraction F [--mask-polygon] [--mask-outline N]]
+  python tools/e2e_bench.py [--config c2|c3] [--frames 60] [--mask-fraction F [--mask-polygon] [--mask-outline N]
+                             [--target-mask-margin R]]
 
 Modes: frames as torch CUDA tensors / host numpy arrays (PCIe upload included), with and without the
 SQLite insert.  --mask-fraction F: every run takes detection_mask = a centred rectangle of the frame's aspect covering F of
@@ -15,7 +16,9 @@ Frame.set_mask_polygons (vertex copy, rasteriser launch, wait), mean of 200 call
 to no timed kernel class.  "gpu_ms_per_step": per-class GPU time, launches and keypoints of a step (pc_context_get_timing: HIP
 events around every launch) from a pass of this tool's own context and analyzer over the same frames under the same mask --
 the driver's context cannot be read from here, and events around every launch slow the step, so the rates above come from
-untimed runs."""
+untimed runs.  --target-mask-margin R (with --mask-fraction): OpticalFlowOptions.target_mask_margin of every run, and of the
+per-class pass -- rows that end where the mask, choked by R pixels, is off are dropped (-1, the default: off); the SQLite modes
+then also report the mean number of flow rows per frame."""
 import argparse
 import json
 import os
@@ -27,7 +30,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
-def per_class_ms(w, h, ml, frames, mask, steps=40, polygons=None):
+def per_class_ms(w, h, ml, frames, mask, steps=40, polygons=None, target_margin=-1):
     """one pipelined pass (polychase_amd.pipeline.ClipAnalyzer) with every kernel class timed: 20 untimed steps, then `steps`"""
     from polychase_amd import hip
     from polychase_amd.pipeline import ClipAnalyzer
@@ -38,6 +41,7 @@ def per_class_ms(w, h, ml, frames, mask, steps=40, polygons=None):
         an.an.set_mask_polygons(polygons)
     else:
         an.an.set_mask(mask)
+    an.an.set_target_mask_margin(target_margin)
     steps = min(steps, len(frames) - 9 - 29)
     an.run(range(9, 29), None)
     ctx.synchronize()
@@ -60,6 +64,7 @@ def main():
     ap.add_argument("--mask-fraction", type=float, default=None)
     ap.add_argument("--mask-polygon", action="store_true")
     ap.add_argument("--mask-outline", type=int, default=0)
+    ap.add_argument("--target-mask-margin", type=int, default=-1)
     a = ap.parse_args()
     import torch
     from polychase_amd import synth
@@ -73,6 +78,7 @@ def main():
     host = [f.cpu().numpy() for f in dev]
     fo = core.OpticalFlowOptions()
     fo.max_level = ml
+    fo.target_mask_margin = a.target_mask_margin
     vi = core.VideoInfo(w, h, 1, a.frames)
     out = {}
     mask = None
@@ -104,11 +110,13 @@ def main():
         out["mask_fraction"] = float(mask.mean() / 255.0)
         out["mask_vertices"] = int(len(polygons[0]))
         out["mask_polygon"] = bool(a.mask_polygon)
+        out["target_mask_margin"] = a.target_mask_margin
         if a.mask_polygon:
             mask = core.PolygonMask(polygons)
     polygons = polygons if a.mask_polygon and a.mask_fraction is not None else None
     if a.frames >= 39:
-        out["gpu_ms_per_step"] = per_class_ms(w, h, ml, dev, mask, polygons=polygons)
+        out["gpu_ms_per_step"] = per_class_ms(w, h, ml, dev, mask, polygons=polygons,
+                                              target_margin=a.target_mask_margin if a.mask_fraction is not None else -1)
     else:
         out["gpu_ms_per_step"] = {"skipped": "the per-class pass needs --frames 39 or more (20 untimed steps, then at least one)"}
     with tempfile.TemporaryDirectory() as td:
@@ -133,6 +141,7 @@ def main():
                 import sqlite3
                 con = sqlite3.connect(db)
                 out[name]["mean_keypoints_per_frame"] = con.execute("select avg(rows) from keypoints").fetchone()[0]
+                out[name]["mean_flow_rows_per_frame"] = con.execute("select sum(rows) from optical_flow").fetchone()[0] / a.frames
                 con.close()
     print(json.dumps({"config": a.config, "frames": a.frames, **out}))
 
