@@ -16,6 +16,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 import fb_scene  # noqa: E402
+import lk_subpixel_scene as subpixel  # noqa: E402
 import oracle  # noqa: E402
 from polychase_amd import hip, synth  # noqa: E402
 from test_lk_fb_gpu import CASES, _scene  # noqa: E402  (the six scenes of the forward-backward check: not copied)
@@ -30,6 +31,9 @@ LK4_CROSS_CHECKED = [c for c in BOARD_CASES if c[0] in (17, 24, 31)]   # windows
 # (scene, target) whose forward pass tracks EVERY keypoint on the oracle (422 of 422 and 428 of 428 in both orders): these 'shift'
 # targets lose their points only in the backward pass, so they cannot show both forward outcomes
 ALL_TRACKED = {("160x120_w15_l2", 5), ("160x120_w31_l2", 0)}
+# windows of tests/lk_subpixel_scene.py: keypoints off the integer grid (w11 == -1, rounding ties) and out of the frame; the product
+# kernels meet the same expected arrays in test_lk_subpixel_gpu.py
+SUBPIXEL_WINDOWS = (3, 7, 10, 16, 31)
 
 
 def _frozen(per_target):
@@ -130,8 +134,20 @@ def board_name(case):
     return "board_w%d_l%d_t%d" % case
 
 
+def subpixel_name(win):
+    return "subpixel_w%d" % win
+
+
+def subpixel_gpu_mismatch(ctx, win, arith):
+    g1, targets, kps = subpixel.scene(win)
+    got = gpu_lk(ctx, (subpixel.W, subpixel.H, win, subpixel.MAX_LEVEL), g1, targets, kps)
+    exp = subpixel.expected(win, arith)
+    # first by class and keypoint (the product kernels' rule: the tracked rows), then every row like the cases above
+    return subpixel.mismatch(win, got, exp) or mismatch(got, exp)
+
+
 def case_names():
-    return sorted(CASES) + ["counts_5", "counts_13"] + [board_name(c) for c in BOARD_CASES]
+    return sorted(CASES) + ["counts_5", "counts_13"] + [board_name(c) for c in BOARD_CASES] + [subpixel_name(w) for w in SUBPIXEL_WINDOWS]
 
 
 def main():
@@ -144,6 +160,8 @@ def main():
                 assert (st == 1).any() and (st == 0).any() != one_outcome, (case, arith, t, kind, int(st.sum()), len(st))
     for case in BOARD_CASES:
         assert orders_differ(case) >= 1, (case, "the two summation orders agree on every vector")
+    for win in SUBPIXEL_WINDOWS:
+        subpixel.check_classes(win)
 
     for arith in sorted(ARITH):
         ctx = hip.Context(0)
@@ -161,6 +179,8 @@ def main():
             report("counts_%d" % n, mismatch(gpu_lk(ctx, size, g1, targets, kps), _oracle_lk(g1, targets, kps, size[2], size[3], arith)))
         for case in BOARD_CASES:
             report(board_name(case), board_gpu_mismatch(ctx, case, arith))
+        for win in SUBPIXEL_WINDOWS:
+            report(subpixel_name(win), subpixel_gpu_mismatch(ctx, win, arith))
         ctx.close()
 
 

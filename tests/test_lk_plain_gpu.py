@@ -9,6 +9,8 @@ so the cases run in ONE subprocess (tests/_lk_plain_check.py, which has the scen
     target 0: 428 of 428), which lose points only in the backward pass and are asserted to be exactly that;
   * the checkerboard, where the two summation orders give different bits (asserted on the oracle first), at windows whose vector
     blocks cover 0 + 7 .. 24 + 7 columns;
+  * windows 3, 7, 10, 16 and 31 of tests/lk_subpixel_scene.py: keypoints off the integer grid (w11 == -1 and rounding ties on the
+    template side) and out of the frame, the arrays test_lk_subpixel_gpu.py holds the product kernels to;
   * windows 17, 24 and 31 of the checkerboard once more in THIS process, i.e. on the default variant's lk4 kernel, against the same
     expected arrays: the cross-check the plain kernel exists for."""
 import os
