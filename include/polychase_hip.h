@@ -125,7 +125,7 @@ int pc_context_get_arithmetic(const pc_context* ctx);
 /* hipStream_t the context enqueues on (for callers that time with HIP events / torch streams). */
 void* pc_context_stream(pc_context* ctx);
 /* Timing of the context's kernels with HIP events on the stream each launch is enqueued on.  `class_mask` bit k
- * enables kernel class PC_K_k (0 = off, 0x1ff = all); enabled classes accumulate (launches, total ms).
+ * enables kernel class PC_K_k (0 = off, 0x3ff = all); enabled classes accumulate (launches, total ms).
  * Two event records per timed launch: keep the mask to the class of interest inside timed regions.
  * pc_analyzer overlaps the LK launches of consecutive frames (two job lanes), so `total_ms` -- the sum of the
  * launches' own start-to-end durations -- exceeds the time the class kept the GPU busy; pc_context_get_busy_time
@@ -162,7 +162,8 @@ int pc_debug_llt9(pc_context* ctx, const float* a81, const float* b9, float* l81
 #define PC_K_LK 6
 #define PC_K_COMPACT 7
 #define PC_K_LK_FB 8   /* the backward launch of the forward-backward check (pc_lk_track_fb, pc_analyzer_set_fb_threshold) */
-#define PC_K_COUNT 9
+#define PC_K_LK_CORR 9 /* the correlation launch of the minimum-correlation check (pc_lk_track_correlated, pc_analyzer_set_min_correlation) */
+#define PC_K_COUNT 10
 
 /* ---- frame: gray image + LK pyramid (+ Scharr derivative planes) + keypoints, resident in HBM ----
  * Replaces the per-frame state of cpp/opticalflow.cc:223-226 (frame1_gray, features, frame1_pyramid)
@@ -307,6 +308,35 @@ int pc_lk_track_filtered_fb(pc_context* ctx, const pc_frame* frame1, const pc_fr
 int pc_lk_track_masked(pc_context* ctx, const pc_frame* frame1, const pc_frame* const* targets, int n_targets,
                        const pc_flow_options* opt, double fb_threshold, int margin, float* next_xy, uint8_t* status, float* err);
 
+/* ---- minimum correlation (not in the reference, off by default) ----
+ * The patch error `err` is OpenCV's L1 difference, which is not invariant to exposure: a gain or bias change between the frames
+ * raises it for every row.  This check judges a row by the normalised cross-correlation of the two windows LK itself compared.
+ * Take a forward record of a pair (keypoint p of frame1, target t) with status 1 and stored fp32 end point q; win = window_size,
+ * n = win * win, half = (float)(win - 1) * 0.5f.
+ *   I window   the win x win values ival that LK's template pass takes at level 0 from frame1's u8 plane at p - half: floor, fp32
+ *              fractions a, b, the 14-bit weights with iw11 = 2^14 - iw00 - iw01 - iw10 (which may be -1), DESCALE(., 9): values
+ *              x 32 in 0..8160.
+ *   J window   the same expression at q - half in the target's level-0 u8 plane: the window the err pass evaluates, before I is
+ *              subtracted.
+ *   bounds     a status-1 record has passed OpenCV's bounds test for both windows on these same floats; the kernel repeats the
+ *              test and drops a record that fails it, and never reads outside the padded plane, whatever it is handed.
+ *   sums       exact integers (int64: n * sum(I^2) <= 961 * 961 * 8160^2 ~ 6.2e13): cov = n sum(IJ) - sum(I) sum(J),
+ *              vI = n sum(I^2) - sum(I)^2, vJ = n sum(J^2) - sum(J)^2.
+ *   decision   without a square root: t2 = (double)min_correlation * (double)min_correlation, computed once on the host; the row
+ *              keeps status 1 iff cov > 0 && (double)cov * (double)cov >= ((double)vI * (double)vJ) * t2, every operation rounded
+ *              to fp64 on its own (no contraction; the int64 -> double conversions are exact).  A flat window (vI == 0 or
+ *              vJ == 0) gives cov == 0 and is dropped.  next_xy and err of the rows that stay are untouched.
+ *   score      (stage-level call only) corr = (float)((double)cov / sqrt((double)vI * (double)vJ)), or 0 when either variance is 0.
+ * min_correlation == 0: no filter; valid values are 0 <= v <= 1; NaN, negative or > 1: PC_E_INVALID.  The final status is the AND
+ * of all enabled checks; the order on the lane is target mask, correlation, forward-backward, so the backward launch does no work
+ * for rows already dropped (kernels_lk_corr.hip; the rule restated in numpy: tests/lk_correlation_ref.py).
+ * pc_lk_track_correlated: pc_lk_track_masked plus the check.  corr ([n_targets][N], may be NULL) receives the score, 0 wherever
+ * the record reached the pass with status 0.  min_correlation == 0 and corr == NULL: exactly pc_lk_track_masked (nothing else is
+ * enqueued); min_correlation == 0 and corr != NULL: the pass runs and only writes scores. */
+int pc_lk_track_correlated(pc_context* ctx, const pc_frame* frame1, const pc_frame* const* targets, int n_targets,
+                           const pc_flow_options* opt, double min_correlation, double fb_threshold, int margin, float* next_xy,
+                           uint8_t* status, float* err, float* corr);
+
 /* ---- analyzer: the pipelined per-clip engine behind GenerateOpticalFlowDatabase ----
  * (cpp/opticalflow.cc:209-321).  Holds a ring of resident frames (the reference's 17-frame
  * SequentialWrapper cache, cpp/opticalflow_thread.h:34-79, generalised), builds every frame's gray
@@ -390,6 +420,10 @@ int pc_analyzer_set_host_records(pc_analyzer* a, int enabled);
  * between the LK launch and the compaction, so rejected rows are simply absent from the records.  0 (the default): off, the
  * jobs enqueue what they always did.  Negative, NaN or infinite: PC_E_INVALID.  pc_analyzer_reset keeps the value. */
 int pc_analyzer_set_fb_threshold(pc_analyzer* a, double fb_threshold);
+/* Minimum correlation (pc_lk_track_correlated) of the jobs submitted FROM NOW ON: 0 = off (the default), else every job drops,
+ * between the target-side mask test and the forward-backward check, the rows whose windows correlate below the value.  Jobs
+ * already submitted keep theirs; pc_analyzer_reset keeps the value.  NaN, negative or > 1, or a null analyzer: PC_E_INVALID. */
+int pc_analyzer_set_min_correlation(pc_analyzer* a, double min_correlation);
 /* Detection mask (pc_frame_set_mask, gftt.cc:45-83) of the frames put FROM NOW ON with will_detect != 0; NULL: no mask (the
  * default).  Detection is enqueued inside pc_analyzer_put_frame, so every slot of the ring keeps a mask plane of its own: a
  * detection already enqueued keeps the mask it was enqueued with, and the mask may change from frame to frame.  A host mask

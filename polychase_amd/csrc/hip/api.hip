@@ -529,6 +529,34 @@ int run_lk_fb(pc_context* ctx, const pc_frame* frame1, const pc_frame* const* ta
     return PC_OK;
 }
 
+int check_min_correlation(double min_correlation) {
+    if (!(min_correlation >= 0.0 && min_correlation <= 1.0)) return fail(PC_E_INVALID, "min_correlation must be in [0, 1]");   // a NaN fails
+    return PC_OK;
+}
+
+int run_lk_corr(pc_context* ctx, const pc_frame* frame1, const pc_frame* const* targets, int n_targets, double min_correlation, int set,
+                float* corr) {
+    hipStream_t const lk_stream = ctx->lane_stream(set);
+    const int n = frame1->n_kps;
+    if (n == 0) return PC_OK;
+    pc::CorrParams p;
+    std::memset(&p, 0, sizeof(p));
+    p.f1 = frame1->levels[0];
+    for (int t = 0; t < n_targets; t++) p.timg[t] = targets[t]->levels[0].img;
+    p.n_targets = n_targets;
+    p.n = n;
+    p.win = frame1->win;
+    p.drop = min_correlation > 0.0 ? 1 : 0;
+    p.pts = frame1->d_kps;
+    p.perm = frame1->perm_valid ? frame1->d_perm : ctx->lk_perm.p;   // the order run_lk visited the keypoints in
+    p.t2 = min_correlation * min_correlation;
+    p.rec = ctx->lk_rec[set].p;
+    p.corr = corr;
+    ScopedTimer tm(ctx, PC_K_LK_CORR, lk_stream);
+    if (!pc::launch_lk_corr(p, lk_stream)) return fail(PC_E_INVALID, "unsupported window size %d", frame1->win);
+    return PC_OK;
+}
+
 int check_target_margin(int margin, bool allow_off) {
     if (margin < (allow_off ? -1 : 0) || margin > PC_TARGET_MASK_MAX_MARGIN)
         return fail(PC_E_INVALID, "margin %d, %d..%d allowed", margin, allow_off ? -1 : 0, PC_TARGET_MASK_MAX_MARGIN);
@@ -789,6 +817,7 @@ void pc_context_destroy(pc_context* c) {
     c->lk_back_xy.release();
     c->lk_back_status.release();
     c->lk_choked.release();
+    c->lk_corr.release();
     c->lk_cidx.release();
     for (auto& b : c->lk_block_counts) b.release();
     c->lk_perm.release();
@@ -1333,9 +1362,10 @@ int pc_frame_set_keypoints(pc_context* ctx, pc_frame* f, const float* xy, int n)
 // ---------------------------------------------------------------------------------------------
 static int lk_track_impl(pc_context* ctx, const pc_frame* frame1, const pc_frame* const* targets, int n_targets,
                          const pc_flow_options* opt, double fb_threshold, int margin, float* next_xy, uint8_t* status, float* err,
-                         float* back_xy, uint8_t* back_status) {
+                         float* back_xy, uint8_t* back_status, double min_correlation = 0.0, float* corr = nullptr) {
     int rc = check_target_margin(margin, true);   // first: a margin is refused whatever the handles
     if (rc != PC_OK) return rc;
+    if ((rc = check_min_correlation(min_correlation)) != PC_OK) return rc;   // ... and so is a correlation
     if ((rc = check_lk_args(ctx, frame1, targets, n_targets, opt)) != PC_OK) return rc;
     if (!next_xy || !status || !err) return fail(PC_E_INVALID, "null output");
     if ((rc = check_fb_threshold(fb_threshold)) != PC_OK) return rc;
@@ -1363,6 +1393,12 @@ static int lk_track_impl(pc_context* ctx, const pc_frame* frame1, const pc_frame
         }
         PC_HIP(hipGetLastError());
         if ((rc = run_lk_target_mask(ctx, frame1, plane, n_targets)) != PC_OK) return rc;
+    }
+    if (rows > 0 && (min_correlation > 0.0 || corr)) {
+        // minimum correlation: after the mask test, before the backward launch
+        if (corr) PC_HIP(ctx->lk_corr.ensure(rows));
+        if ((rc = run_lk_corr(ctx, frame1, targets, n_targets, min_correlation, 0, corr ? ctx->lk_corr.p : nullptr)) != PC_OK) return rc;
+        if (corr) PC_HIP(hipMemcpyAsync(corr, ctx->lk_corr.p, rows * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
     }
     const bool fb = fb_threshold > 0.0;
     if (rows > 0 && !fb) {
@@ -1407,6 +1443,13 @@ int pc_lk_track_fb(pc_context* ctx, const pc_frame* frame1, const pc_frame* cons
 int pc_lk_track_masked(pc_context* ctx, const pc_frame* frame1, const pc_frame* const* targets, int n_targets,
                        const pc_flow_options* opt, double fb_threshold, int margin, float* next_xy, uint8_t* status, float* err) {
     return lk_track_impl(ctx, frame1, targets, n_targets, opt, fb_threshold, margin, next_xy, status, err, nullptr, nullptr);
+}
+
+int pc_lk_track_correlated(pc_context* ctx, const pc_frame* frame1, const pc_frame* const* targets, int n_targets,
+                           const pc_flow_options* opt, double min_correlation, double fb_threshold, int margin, float* next_xy,
+                           uint8_t* status, float* err, float* corr) {
+    return lk_track_impl(ctx, frame1, targets, n_targets, opt, fb_threshold, margin, next_xy, status, err, nullptr, nullptr,
+                         min_correlation, corr);
 }
 
 static int lk_track_filtered_impl(pc_context* ctx, const pc_frame* frame1, const pc_frame* const* targets, int n_targets,

@@ -104,6 +104,7 @@ struct pc_analyzer {
     int puts = 0;
     bool host_records = true;            // download every job's records to pinned host memory
     double fb_threshold = 0.0;           // forward-backward check of the jobs submitted from now on (0: off)
+    double min_correlation = 0.0;        // minimum correlation of the jobs submitted from now on (0: off)
     // Target-side masks (pc_analyzer_set_target_mask_margin): -1 off, else the margin of the frames put from now on.  While it is
     // >= 0 and a mask is in force every frame put takes the mask -- pc_frame::target_margin is the frame's role as a target,
     // beside mask_on, which stays the detection's -- and with a margin > 0 its choked plane too.
@@ -536,6 +537,8 @@ int pc_analyzer_submit(pc_analyzer* a, int32_t frame1, const int32_t* targets, i
                 if (tg[t]->target_margin >= 0) plane[t] = tg[t]->target_margin > 0 ? tg[t]->d_choked : tg[t]->d_mask;
             if ((rc = run_lk_target_mask(ctx, s1->frame, plane, n_targets, lane)) != PC_OK) return rc;
         }
+        // minimum correlation: rows whose windows correlate below the value are dropped before the backward launch looks at them
+        if (a->min_correlation > 0.0 && (rc = run_lk_corr(ctx, s1->frame, tg, n_targets, a->min_correlation, lane)) != PC_OK) return rc;
         // forward-backward check: the backward launch follows on the same lane and rewrites the status of the records the
         // compaction below filters; the gate is the forward launch's alone
         if (a->fb_threshold > 0.0 && (rc = run_lk_fb(ctx, s1->frame, tg, n_targets, &a->fopt, a->fb_threshold, lane)) != PC_OK) return rc;
@@ -622,6 +625,13 @@ int pc_analyzer_set_fb_threshold(pc_analyzer* a, double fb_threshold) {
     if (!a) return fail(PC_E_INVALID, "null analyzer");
     if (int rc = check_fb_threshold(fb_threshold)) return rc;
     a->fb_threshold = fb_threshold;
+    return PC_OK;
+}
+
+int pc_analyzer_set_min_correlation(pc_analyzer* a, double min_correlation) {
+    if (int rc = check_min_correlation(min_correlation)) return rc;   // first: a value is refused whatever the handle
+    if (!a) return fail(PC_E_INVALID, "null analyzer");
+    a->min_correlation = min_correlation;
     return PC_OK;
 }
 

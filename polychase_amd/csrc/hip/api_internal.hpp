@@ -82,6 +82,12 @@ int run_lk(pc_context* ctx, const pc_frame* frame1, const pc_frame* const* targe
 int check_fb_threshold(double fb_threshold);
 int run_lk_fb(pc_context* ctx, const pc_frame* frame1, const pc_frame* const* targets, int n_targets, const pc_flow_options* opt,
               double fb_threshold, int set = 0, float2* back_xy = nullptr, uint8_t* back_status = nullptr);
+// minimum correlation (include/polychase_hip.h: pc_lk_track_correlated) on the records run_lk has just left in set `set`, on the
+// same lane, between run_lk_target_mask and run_lk_fb.  check_min_correlation: 0 <= v <= 1; run_lk_corr drops the rows below
+// min_correlation (0: none) and, with `corr` (device, [target][n]), writes the scores
+int check_min_correlation(double min_correlation);
+int run_lk_corr(pc_context* ctx, const pc_frame* frame1, const pc_frame* const* targets, int n_targets, double min_correlation, int set = 0,
+                float* corr = nullptr);
 // target-side masks (include/polychase_hip.h: pc_lk_track_masked).  check_target_margin: -1 (only with allow_off) .. 31;
 // ensure_choked_plane allocates pc_frame::d_choked (once); run_lk_target_mask drops, on the lane of set `set`, the records
 // run_lk has just left there that end where the plane of their target is off (plane[t] null: target t keeps its rows; all null:

@@ -262,6 +262,27 @@ bool launch_lk_fb(const LKFBParams& p, hipStream_t s);
 // keypoints -> packed record buffer (both 16-byte aligned)
 void launch_copy_keypoints(const float2* src, float2* dst, int n, hipStream_t s);
 
+// ---- kernels_lk_corr.hip ----
+// Minimum correlation (include/polychase_hip.h: pc_lk_track_correlated): for every record of the forward launch with status 1 the
+// normalised cross-correlation of the level-0 windows LK compared -- I at keypoint - half in frame1's u8 plane, J at end point -
+// half in the target's -- from exact integer sums; with `drop`, rec[...].w becomes 0 unless cov > 0 and cov^2 >= vI * vJ * t2 in
+// separately rounded fp64 operations, or when a window fails OpenCV's bounds test.  One launch per frame1 job.
+struct CorrParams {
+    Level f1;                  // frame1, level 0
+    const uint8_t* timg[8];    // [target] interior origins of the targets' level-0 u8 planes (frame1's geometry)
+    int n_targets;
+    int n;                     // keypoints
+    int win;                   // 3 .. PC_MAX_WINDOW, the padding of the planes
+    int drop;                  // 0: only the scores are written
+    const float2* pts;         // frame1's keypoints
+    const uint32_t* perm;      // visiting order of the forward launch (slot -> keypoint) or null
+    double t2;                 // (double)min_correlation * (double)min_correlation
+    float4* rec;               // the forward launch's records, LKParams::out_rec
+    float* corr;               // [target][n] in keypoint order: the score, 0 where the pair was not evaluated; or null
+};
+// false: window or target count out of range (nothing enqueued)
+bool launch_lk_corr(const CorrParams& p, hipStream_t s);
+
 
 // ---- kernels_tracker.hip ----
 struct RayCamera {

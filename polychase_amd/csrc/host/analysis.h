@@ -43,11 +43,17 @@ struct OpticalFlowOptions {
     // dropped when its end point lies where the detection mask of its TARGET frame, choked by this many pixels, is off.  Does
     // nothing without a detection_mask.
     int target_mask_margin = -1;
+    // not in the reference: minimum correlation (include/polychase_hip.h: pc_lk_track_correlated).  0 = off; 0 < v <= 1: a flow
+    // row is dropped when the normalised cross-correlation of the two windows LK compared lies below v (Blender's tracker
+    // calls it correlation_min, default 0.75 there)
+    double min_correlation = 0.0;
 };
 // std::invalid_argument for what no run accepts; every entry point calls it before it asks for a frame
 inline void CheckOpticalFlowOptions(const OpticalFlowOptions& o) {
     if (o.target_mask_margin < -1 || o.target_mask_margin > 31)
         throw std::invalid_argument("target_mask_margin must be -1 (off) or 0..31, got " + std::to_string(o.target_mask_margin));
+    if (!(o.min_correlation >= 0.0 && o.min_correlation <= 1.0))   // a NaN fails
+        throw std::invalid_argument("min_correlation must be in [0, 1] (0 = off), got " + std::to_string(o.min_correlation));
 }
 
 // The clip: frames first_frame .. first_frame + num_frames - 1, all width x height.

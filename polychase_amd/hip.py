@@ -14,7 +14,10 @@ import numpy as np
 from . import build as _build
 
 PC_MAX_TARGETS = 8
-KERNEL_CLASSES = ["gray", "pyramid", "min_eig", "nms", "sort", "suppress", "lk", "compact", "lk_fb"]
+KERNEL_CLASSES = ["gray", "pyramid", "min_eig", "nms", "sort", "suppress", "lk", "compact", "lk_fb", "lk_corr"]
+# Classes that Context.timing() lists only once they have launched: with the minimum-correlation check off nothing of it is
+# enqueued, and the dictionary of such a context stays the one its readers (bench.py's breakdown, launch-count tests) know.
+TIMING_CLASSES_LISTED_ON_USE = ("lk_corr",)
 
 # every symbol include/polychase_hip.h declares (tests check they are all exported)
 SYMBOLS = [
@@ -30,6 +33,7 @@ SYMBOLS = [
     "pc_frame_num_keypoints", "pc_frame_download_keypoints", "pc_frame_set_keypoints", "pc_frame_set_mask",
     "pc_frame_set_mask_polygons", "pc_frame_download_mask", "pc_analyzer_set_mask_polygons",
     "pc_frame_download_choked_mask", "pc_lk_track_masked", "pc_analyzer_set_target_mask_margin",
+    "pc_lk_track_correlated", "pc_analyzer_set_min_correlation",
     "pc_lk_track", "pc_lk_track_filtered", "pc_lk_track_fb", "pc_lk_track_filtered_fb",
     "pc_analyzer_create", "pc_analyzer_destroy", "pc_analyzer_reset", "pc_analyzer_put_frame", "pc_analyzer_put_frame_f32",
     "pc_analyzer_has_frame", "pc_analyzer_frame_ingested",
@@ -154,6 +158,8 @@ def load():
     L.pc_lk_track_fb.argtypes = [vp, vp, C.POINTER(vp), C.c_int, C.POINTER(FlowOptions), C.c_double, vp, vp, vp, vp, vp]
     L.pc_lk_track_filtered_fb.argtypes = [vp, vp, C.POINTER(vp), C.c_int, C.POINTER(FlowOptions), C.c_double, vp, vp, vp, vp]
     L.pc_lk_track_masked.argtypes = [vp, vp, C.POINTER(vp), C.c_int, C.POINTER(FlowOptions), C.c_double, C.c_int, vp, vp, vp]
+    L.pc_lk_track_correlated.argtypes = [vp, vp, C.POINTER(vp), C.c_int, C.POINTER(FlowOptions), C.c_double, C.c_double, C.c_int, vp, vp,
+                                         vp, vp]
     L.pc_analyzer_create.argtypes = [vp, C.c_int, C.c_int, C.POINTER(GfttOptions), C.POINTER(FlowOptions), C.c_int,
                                      C.c_int, C.POINTER(vp)]
     L.pc_analyzer_destroy.argtypes = [vp]
@@ -175,6 +181,7 @@ def load():
     L.pc_analyzer_set_mask.argtypes = [vp, vp, C.c_size_t, C.c_int]
     L.pc_analyzer_set_mask_polygons.argtypes = [vp, vp, vp, C.c_int, C.c_int]
     L.pc_analyzer_set_target_mask_margin.argtypes = [vp, C.c_int]
+    L.pc_analyzer_set_min_correlation.argtypes = [vp, C.c_double]
     L.pc_peer_buffer_alloc.argtypes = [C.c_int, C.c_size_t, C.POINTER(vp)]
     L.pc_peer_buffer_free.argtypes = [C.c_int, vp]
     L.pc_peer_buffer_export.argtypes = [C.c_int, vp, C.c_char_p]
@@ -261,11 +268,13 @@ class Context:
         _check(load().pc_context_reset_timing(self._h))
 
     def timing(self) -> dict:
+        """{class: (launches, total ms)} since reset_timing(); the classes of TIMING_CLASSES_LISTED_ON_USE only with launches"""
         out = {}
         for k, name in enumerate(KERNEL_CLASSES):
             n, ms = C.c_int(), C.c_double()
             _check(load().pc_context_get_timing(self._h, k, C.byref(n), C.byref(ms)))
-            out[name] = (n.value, ms.value)
+            if n.value or name not in TIMING_CLASSES_LISTED_ON_USE:
+                out[name] = (n.value, ms.value)
         return out
 
     def lk_profile(self) -> list:
@@ -545,6 +554,24 @@ def lk_track_masked(ctx: Context, frame1: Frame, targets: list[Frame], fb_thresh
     return xy, st, err
 
 
+def lk_track_correlated(ctx: Context, frame1: Frame, targets: list[Frame], min_correlation: float, fb_threshold: float = 0.0,
+                        margin: int = -1, opt: FlowOptions | None = None, corr: bool = True):
+    """lk_track_masked plus the minimum-correlation check (include/polychase_hip.h: pc_lk_track_correlated): a row whose reference
+    and matched windows correlate below min_correlation gets status 0; 0 = no filter.  corr=True also returns the scores (0 where
+    the record reached the pass with status 0); corr=False with min_correlation 0 is lk_track_masked.
+    -> next_xy [T,N,2], final status [T,N], err [T,N], corr [T,N] or None."""
+    opt = opt or flow_options()
+    n, t = frame1.num_keypoints, len(targets)
+    xy = np.zeros((t, n, 2), np.float32)
+    st = np.zeros((t, n), np.uint8)
+    err = np.zeros((t, n), np.float32)
+    sc = np.zeros((t, n), np.float32) if corr else None
+    arr = (C.c_void_p * t)(*[f._h for f in targets])
+    _check(load().pc_lk_track_correlated(ctx._h, frame1._h, arr, t, C.byref(opt), float(min_correlation), float(fb_threshold), int(margin),
+                                         xy.ctypes.data, st.ctypes.data, err.ctypes.data, sc.ctypes.data if corr else None))
+    return xy, st, err, sc
+
+
 def lk_track_filtered_fb(ctx: Context, frame1: Frame, targets: list[Frame], fb_threshold: float, opt: FlowOptions | None = None):
     """lk_track_filtered on the final status of the forward-backward check (pc_lk_track_filtered_fb)."""
     opt = opt or flow_options()
@@ -652,6 +679,10 @@ class Analyzer:
     def set_fb_threshold(self, fb_threshold: float):
         """forward-backward check for the jobs submitted from now on; 0 = off (pc_analyzer_set_fb_threshold)"""
         _check(load().pc_analyzer_set_fb_threshold(self._h, float(fb_threshold)))
+
+    def set_min_correlation(self, min_correlation: float):
+        """minimum correlation for the jobs submitted from now on; 0 = off, 0 < v <= 1 (pc_analyzer_set_min_correlation)"""
+        _check(load().pc_analyzer_set_min_correlation(self._h, float(min_correlation)))
 
     def set_target_mask_margin(self, margin: int):
         """target-side masks for the frames put from now on: -1 = off, 0..31 = the margin (pc_analyzer_set_target_mask_margin);

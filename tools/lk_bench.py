@@ -7,11 +7,13 @@ C ABI, then `pc_lk_track` is repeated: the LK class is timed with HIP events by 
 the average launch time and a checksum of the raw outputs (equal checksums <=> bit-identical
 results, the way kernel variants are compared: POLYCHASE_HIP_LIB selects the library).
 
-    python tools/lk_bench.py [--config c2|c3] [--reps 20] [--fb PX]
+    python tools/lk_bench.py [--config c2|c3] [--reps 20] [--fb PX] [--min-correlation V]
 
 --fb PX also times the forward-backward check (pc_lk_track_fb, threshold PX): the forward launch and the backward launch of
 the same call, and as the baseline the same backward work through the calls that existed before it -- per target,
 set_keypoints(q[status_f == 1]) on the target frame and pc_lk_track(target, [frame1]): eight launches.
+--min-correlation V also times the minimum-correlation check (pc_lk_track_correlated, threshold V): the forward launch and the
+correlation launch of the same call, and the share of rows the check drops.
 
 (Parity against the CPU oracle is the test suite's business: tests/test_gpu_parity.py, tests/test_fullsize_gpu.py.)
 """
@@ -71,6 +73,22 @@ def fb_timing(ctx, hip, f1, targets, fopt, thr, reps, xy, st, err):
             "dropped_fraction": (fwd_rows - kept_rows) / max(1, fwd_rows), "status_b_zero": int(((st == 1) & (bst == 0)).sum())}
 
 
+def corr_timing(ctx, hip, f1, targets, fopt, thr, reps, xy, st, err):
+    """forward + correlation launch of pc_lk_track_correlated; the check must leave the forward values alone"""
+    cxy, cst, cerr, _ = hip.lk_track_correlated(ctx, f1, targets, thr, opt=fopt, corr=False)      # warm-up + the output that is compared
+    assert np.array_equal(cxy, xy) and np.array_equal(cerr, err) and not (cst & ~st).any(), "the check changed a forward value"
+    ctx.enable_timing(["lk", "lk_corr"])
+    ctx.reset_timing()
+    for _ in range(reps):
+        hip.lk_track_correlated(ctx, f1, targets, thr, opt=fopt, corr=False)
+    t = ctx.timing()
+    ctx.enable_timing(False)
+    fwd_ms, corr_ms = t["lk"][1] / max(1, t["lk"][0]), t["lk_corr"][1] / max(1, t["lk_corr"][0])
+    fwd_rows, kept_rows = int((st == 1).sum()), int((cst == 1).sum())
+    return {"threshold": thr, "forward_ms": fwd_ms, "correlation_ms": corr_ms, "correlation_over_forward": corr_ms / fwd_ms if fwd_ms else None,
+            "forward_rows": fwd_rows, "kept_rows": kept_rows, "dropped_fraction": (fwd_rows - kept_rows) / max(1, fwd_rows)}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", default="c2", choices=sorted(CONFIGS))
@@ -81,6 +99,7 @@ def main():
     ap.add_argument("--max-iters", type=int, default=30, help="term_max_iters (30 = the reference's default); smaller values CUT the "
                     "stragglers' iterations off -- wrong results, but the time saved is the ceiling of what deferring them could gain")
     ap.add_argument("--fb", type=float, default=0.0, metavar="PX", help="also time the forward-backward check at this threshold")
+    ap.add_argument("--min-correlation", type=float, default=0.0, metavar="V", help="also time the minimum-correlation check at this threshold")
     args = ap.parse_args()
 
     import torch
@@ -135,6 +154,8 @@ def main():
            "sha256": hsh.hexdigest()[:16], "lib": os.environ.get("POLYCHASE_HIP_LIB", "default")}
     if x86_stats is not None:
         out["x86_stats_one_launch"] = x86_stats
+    if args.min_correlation > 0:      # (before --fb: that one leaves other keypoints on the target frames)
+        out["min_correlation"] = corr_timing(ctx, hip, f1, targets, fopt, args.min_correlation, args.reps, xy, st, err)
     if args.fb > 0:
         out["fb"] = fb_timing(ctx, hip, f1, targets, fopt, args.fb, args.reps, xy, st, err)
     prof = ctx.lk_profile()
