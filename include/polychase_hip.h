@@ -337,6 +337,36 @@ int pc_lk_track_correlated(pc_context* ctx, const pc_frame* frame1, const pc_fra
                            const pc_flow_options* opt, double min_correlation, double fb_threshold, int margin, float* next_xy,
                            uint8_t* status, float* err, float* corr);
 
+/* ---- brightness normalisation (not in the reference, off by default) ----
+ * LK assumes brightness constancy: its mismatch vector is b = sum (J - I) grad I, and a bias c between the two frames adds
+ * c sum grad I to it -- non-zero for every window with a net gradient, so an exposure ramp or a flicker displaces every end point.
+ * With normalize == 1 every LK pass of the call (the forward launch, and the backward launch of the forward-backward check where
+ * fb_threshold > 0) runs the rule below instead: Gauss-Newton on g (J - mean J) - (I - mean I), g the ratio of the two windows'
+ * standard deviations.  The residual has zero sum, so the gradient means drop out of b and a bias changes nothing at all.
+ * The rule is OpenCV's pass (oracle/pc_oracle.c: pco_lk; lk_plain.hpp: plain_lk_pair) level by level -- the bounds tests, the
+ * bilinear weights, the template values ival (0..8160), ix, iy (DESCALE by 9 / 14), the interpolation of the searched plane, the
+ * 2x2 solve, the epsilon test, the oscillation exit and the level-0 L1 patch error are identical in fp32 -- with two
+ * replacements.  n = win * win; every sum is an exact integer (int64), every fp64 operation is rounded on its own (no
+ * contraction), and the arithmetic mode (pc_context_set_arithmetic) plays no part.
+ *   template, once per level   over the window (x = ix, y = iy, I = ival): S_I, S_II, S_x, S_y, S_xx, S_xy, S_yy, S_Ix, S_Iy;
+ *              G11 = n S_xx - S_x^2, G12 = n S_xy - S_x S_y, G22 = n S_yy - S_y^2, C_Ix = n S_Ix - S_I S_x, C_Iy = n S_Iy - S_I S_y,
+ *              vI = n S_II - S_I^2 (all below 2^53);  A11 = (float)((double)G11 / (double)n) * FLT_SCALE, A12 and A22 likewise:
+ *              the centred Gram matrix.  The bias is eliminated, so a pure ramp is degenerate: the unchanged D / min_eig test
+ *              refuses it.
+ *   each iteration   over the J window (J = the interpolated value, 0..8160): T_J, T_JJ, T_Jx = sum J ix, T_Jy = sum J iy;
+ *              vJ = n T_JJ - T_J^2, C_Jx = n T_Jx - T_J S_x, C_Jy = n T_Jy - T_J S_y;
+ *              gain: vI > 0 && vJ > 0 ? g = (float)sqrt((double)vI / (double)vJ) clamped to [0.25f, 4.0f] : g = 1.0f;
+ *              b1 = (float)(((double)g * (double)C_Jx - (double)C_Ix) / (double)n) * FLT_SCALE, b2 likewise with C_Jy, C_Iy.
+ * The stored err stays OpenCV's un-normalised L1 patch error; min_correlation is the gain-invariant measure of a row, and the two
+ * options compose (the correlation pass judges the normalised rows like any others).  Records, target-mask test, correlation pass,
+ * compaction and unpacking are unchanged (kernels_lk_norm.hip; the rule restated in numpy: tests/lk_normalized_ref.py).
+ * pc_lk_track_normalized: normalize == 0 is exactly pc_lk_track_correlated without scores, plus the back outputs of
+ * pc_lk_track_fb (nothing else is enqueued); normalize == 1 swaps the LK launches, timed under PC_K_LK and PC_K_LK_FB as before.
+ * Any other value: PC_E_INVALID. */
+int pc_lk_track_normalized(pc_context* ctx, const pc_frame* frame1, const pc_frame* const* targets, int n_targets,
+                           const pc_flow_options* opt, int normalize, double min_correlation, double fb_threshold, int margin,
+                           float* next_xy, uint8_t* status, float* err, float* back_xy, uint8_t* back_status);
+
 /* ---- analyzer: the pipelined per-clip engine behind GenerateOpticalFlowDatabase ----
  * (cpp/opticalflow.cc:209-321).  Holds a ring of resident frames (the reference's 17-frame
  * SequentialWrapper cache, cpp/opticalflow_thread.h:34-79, generalised), builds every frame's gray
@@ -424,6 +454,10 @@ int pc_analyzer_set_fb_threshold(pc_analyzer* a, double fb_threshold);
  * between the target-side mask test and the forward-backward check, the rows whose windows correlate below the value.  Jobs
  * already submitted keep theirs; pc_analyzer_reset keeps the value.  NaN, negative or > 1, or a null analyzer: PC_E_INVALID. */
 int pc_analyzer_set_min_correlation(pc_analyzer* a, double min_correlation);
+/* Brightness normalisation (pc_lk_track_normalized) of the jobs submitted FROM NOW ON: 0 = off (the default), 1 = the forward
+ * launch, and the backward launch where the forward-backward check is on, run the normalised rule.  Jobs already submitted keep
+ * theirs; pc_analyzer_reset keeps the value.  Any other value, or a null analyzer: PC_E_INVALID. */
+int pc_analyzer_set_normalize(pc_analyzer* a, int normalize);
 /* Detection mask (pc_frame_set_mask, gftt.cc:45-83) of the frames put FROM NOW ON with will_detect != 0; NULL: no mask (the
  * default).  Detection is enqueued inside pc_analyzer_put_frame, so every slot of the ring keeps a mask plane of its own: a
  * detection already enqueued keeps the mask it was enqueued with, and the mask may change from frame to frame.  A host mask

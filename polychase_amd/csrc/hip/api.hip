@@ -428,7 +428,7 @@ int check_lk_args(pc_context* ctx, const pc_frame* frame1, const pc_frame* const
 }
 
 int run_lk(pc_context* ctx, const pc_frame* frame1, const pc_frame* const* targets, int n_targets,
-           const pc_flow_options* opt, int set) {
+           const pc_flow_options* opt, int set, int normalize) {
     hipStream_t const lk_stream = ctx->lane_stream(set);
     const int n = frame1->n_kps;
     const size_t rows = (size_t)n * n_targets;
@@ -483,7 +483,8 @@ int run_lk(pc_context* ctx, const pc_frame* frame1, const pc_frame* const* targe
         p.prof = ctx->lk_prof.p;
     }
     ScopedTimer tm(ctx, PC_K_LK, lk_stream);
-    if (!pc::launch_lk(p, frame1->win, lk_stream)) return fail(PC_E_INVALID, "unsupported window size %d", frame1->win);
+    if (!(normalize ? pc::launch_lk_norm(p, frame1->win, lk_stream) : pc::launch_lk(p, frame1->win, lk_stream)))
+        return fail(PC_E_INVALID, "unsupported window size %d", frame1->win);
     return PC_OK;
 }
 
@@ -493,7 +494,7 @@ int check_fb_threshold(double fb_threshold) {
 }
 
 int run_lk_fb(pc_context* ctx, const pc_frame* frame1, const pc_frame* const* targets, int n_targets, const pc_flow_options* opt,
-              double fb_threshold, int set, float2* back_xy, uint8_t* back_status) {
+              double fb_threshold, int set, float2* back_xy, uint8_t* back_status, int normalize) {
     hipStream_t const lk_stream = ctx->lane_stream(set);
     const int n = frame1->n_kps;
     if (n == 0) return PC_OK;
@@ -525,7 +526,13 @@ int run_lk_fb(pc_context* ctx, const pc_frame* frame1, const pc_frame* const* ta
     p.back_status = back_status;
     p.x86_order = (ctx->arith & PC_ARITH_LK_X86_ORDER) ? 1 : 0;
     ScopedTimer tm(ctx, PC_K_LK_FB, lk_stream);
-    if (!pc::launch_lk_fb(p, lk_stream)) return fail(PC_E_INVALID, "unsupported window size %d", frame1->win);
+    if (!(normalize ? pc::launch_lk_norm_fb(p, lk_stream) : pc::launch_lk_fb(p, lk_stream)))
+        return fail(PC_E_INVALID, "unsupported window size %d", frame1->win);
+    return PC_OK;
+}
+
+int check_normalize(int normalize) {
+    if (normalize != 0 && normalize != 1) return fail(PC_E_INVALID, "normalize must be 0 or 1, got %d", normalize);
     return PC_OK;
 }
 
@@ -1362,16 +1369,17 @@ int pc_frame_set_keypoints(pc_context* ctx, pc_frame* f, const float* xy, int n)
 // ---------------------------------------------------------------------------------------------
 static int lk_track_impl(pc_context* ctx, const pc_frame* frame1, const pc_frame* const* targets, int n_targets,
                          const pc_flow_options* opt, double fb_threshold, int margin, float* next_xy, uint8_t* status, float* err,
-                         float* back_xy, uint8_t* back_status, double min_correlation = 0.0, float* corr = nullptr) {
+                         float* back_xy, uint8_t* back_status, double min_correlation = 0.0, float* corr = nullptr, int normalize = 0) {
     int rc = check_target_margin(margin, true);   // first: a margin is refused whatever the handles
     if (rc != PC_OK) return rc;
+    if ((rc = check_normalize(normalize)) != PC_OK) return rc;   // ... and so is a switch that is neither off nor on
     if ((rc = check_min_correlation(min_correlation)) != PC_OK) return rc;   // ... and so is a correlation
     if ((rc = check_lk_args(ctx, frame1, targets, n_targets, opt)) != PC_OK) return rc;
     if (!next_xy || !status || !err) return fail(PC_E_INVALID, "null output");
     if ((rc = check_fb_threshold(fb_threshold)) != PC_OK) return rc;
     PC_HIP(hipSetDevice(ctx->device));
     if (int jrc = join_prep(ctx)) return jrc;
-    rc = run_lk(ctx, frame1, targets, n_targets, opt);
+    rc = run_lk(ctx, frame1, targets, n_targets, opt, 0, normalize);
     if (rc != PC_OK) return rc;
     const size_t rows = (size_t)frame1->n_kps * n_targets;
     if (margin >= 0 && rows > 0) {
@@ -1409,7 +1417,7 @@ static int lk_track_impl(pc_context* ctx, const pc_frame* frame1, const pc_frame
         if (back_xy) PC_HIP(ctx->lk_back_xy.ensure(rows));
         if (back_status) PC_HIP(ctx->lk_back_status.ensure(rows));
         rc = run_lk_fb(ctx, frame1, targets, n_targets, opt, fb_threshold, 0, back_xy ? ctx->lk_back_xy.p : nullptr,
-                       back_status ? ctx->lk_back_status.p : nullptr);
+                       back_status ? ctx->lk_back_status.p : nullptr, normalize);
         if (rc != PC_OK) return rc;
         if (back_xy) PC_HIP(hipMemcpyAsync(back_xy, ctx->lk_back_xy.p, rows * sizeof(float2), hipMemcpyDeviceToHost, ctx->stream));
         if (back_status) PC_HIP(hipMemcpyAsync(back_status, ctx->lk_back_status.p, rows, hipMemcpyDeviceToHost, ctx->stream));
@@ -1450,6 +1458,13 @@ int pc_lk_track_correlated(pc_context* ctx, const pc_frame* frame1, const pc_fra
                            uint8_t* status, float* err, float* corr) {
     return lk_track_impl(ctx, frame1, targets, n_targets, opt, fb_threshold, margin, next_xy, status, err, nullptr, nullptr,
                          min_correlation, corr);
+}
+
+int pc_lk_track_normalized(pc_context* ctx, const pc_frame* frame1, const pc_frame* const* targets, int n_targets,
+                           const pc_flow_options* opt, int normalize, double min_correlation, double fb_threshold, int margin,
+                           float* next_xy, uint8_t* status, float* err, float* back_xy, uint8_t* back_status) {
+    return lk_track_impl(ctx, frame1, targets, n_targets, opt, fb_threshold, margin, next_xy, status, err, back_xy, back_status,
+                         min_correlation, nullptr, normalize);
 }
 
 static int lk_track_filtered_impl(pc_context* ctx, const pc_frame* frame1, const pc_frame* const* targets, int n_targets,

@@ -105,6 +105,7 @@ struct pc_analyzer {
     bool host_records = true;            // download every job's records to pinned host memory
     double fb_threshold = 0.0;           // forward-backward check of the jobs submitted from now on (0: off)
     double min_correlation = 0.0;        // minimum correlation of the jobs submitted from now on (0: off)
+    int normalize = 0;                   // brightness-normalised LK for the jobs submitted from now on (0: off)
     // Target-side masks (pc_analyzer_set_target_mask_margin): -1 off, else the margin of the frames put from now on.  While it is
     // >= 0 and a mask is in force every frame put takes the mask -- pc_frame::target_margin is the frame's role as a target,
     // beside mask_on, which stays the detection's -- and with a margin > 0 its choked plane too.
@@ -529,7 +530,7 @@ int pc_analyzer_submit(pc_analyzer* a, int32_t frame1, const int32_t* targets, i
             if (ctx->lk_gate_next == 0) ctx->lk_gate_next = ++ctx->lk_gate_seq;
             a->gate_armed = true;
         }
-        if ((rc = run_lk(ctx, s1->frame, tg, n_targets, &a->fopt, lane)) != PC_OK) return rc;
+        if ((rc = run_lk(ctx, s1->frame, tg, n_targets, &a->fopt, lane, a->normalize)) != PC_OK) return rc;
         // target-side masks: rows that end where their target's plane is off are dropped before the backward launch looks at them
         {
             const uint8_t* plane[PC_MAX_TARGETS] = {};
@@ -541,7 +542,7 @@ int pc_analyzer_submit(pc_analyzer* a, int32_t frame1, const int32_t* targets, i
         if (a->min_correlation > 0.0 && (rc = run_lk_corr(ctx, s1->frame, tg, n_targets, a->min_correlation, lane)) != PC_OK) return rc;
         // forward-backward check: the backward launch follows on the same lane and rewrites the status of the records the
         // compaction below filters; the gate is the forward launch's alone
-        if (a->fb_threshold > 0.0 && (rc = run_lk_fb(ctx, s1->frame, tg, n_targets, &a->fopt, a->fb_threshold, lane)) != PC_OK) return rc;
+        if (a->fb_threshold > 0.0 && (rc = run_lk_fb(ctx, s1->frame, tg, n_targets, &a->fopt, a->fb_threshold, lane, nullptr, nullptr, a->normalize)) != PC_OK) return rc;
     }
     SlowSection ss_post("submit/post enqueue");
     uint8_t* const pack = ctx->lk_pack[lane].p;
@@ -632,6 +633,13 @@ int pc_analyzer_set_min_correlation(pc_analyzer* a, double min_correlation) {
     if (int rc = check_min_correlation(min_correlation)) return rc;   // first: a value is refused whatever the handle
     if (!a) return fail(PC_E_INVALID, "null analyzer");
     a->min_correlation = min_correlation;
+    return PC_OK;
+}
+
+int pc_analyzer_set_normalize(pc_analyzer* a, int normalize) {
+    if (int rc = check_normalize(normalize)) return rc;   // first: a value is refused whatever the handle
+    if (!a) return fail(PC_E_INVALID, "null analyzer");
+    a->normalize = normalize;
     return PC_OK;
 }
 

@@ -74,14 +74,16 @@ int join_prep(pc_context* ctx);
 int order_keypoints_spatially(pc_context* ctx, pc_frame* f, DevBuf<uint32_t>& hist);
 int check_lk_args(pc_context* ctx, const pc_frame* frame1, const pc_frame* const* targets, int n_targets,
                   const pc_flow_options* opt);
-// LK launch into output set `set` on job lane `set` (0: the context's main stream)
+// LK launch into output set `set` on job lane `set` (0: the context's main stream); normalize (check_normalize: 0 or 1): the
+// brightness-normalised kernels (include/polychase_hip.h: pc_lk_track_normalized) instead, here and in run_lk_fb
+int check_normalize(int normalize);
 int run_lk(pc_context* ctx, const pc_frame* frame1, const pc_frame* const* targets, int n_targets, const pc_flow_options* opt,
-           int set = 0);
+           int set = 0, int normalize = 0);
 // forward-backward check on the records run_lk has just left in set `set`, on the same lane (fb_threshold > 0);
 // back_xy / back_status: device arrays [n_targets][n] or null
 int check_fb_threshold(double fb_threshold);
 int run_lk_fb(pc_context* ctx, const pc_frame* frame1, const pc_frame* const* targets, int n_targets, const pc_flow_options* opt,
-              double fb_threshold, int set = 0, float2* back_xy = nullptr, uint8_t* back_status = nullptr);
+              double fb_threshold, int set = 0, float2* back_xy = nullptr, uint8_t* back_status = nullptr, int normalize = 0);
 // minimum correlation (include/polychase_hip.h: pc_lk_track_correlated) on the records run_lk has just left in set `set`, on the
 // same lane, between run_lk_target_mask and run_lk_fb.  check_min_correlation: 0 <= v <= 1; run_lk_corr drops the rows below
 // min_correlation (0: none) and, with `corr` (device, [target][n]), writes the scores

@@ -283,6 +283,14 @@ struct CorrParams {
 // false: window or target count out of range (nothing enqueued)
 bool launch_lk_corr(const CorrParams& p, hipStream_t s);
 
+// ---- kernels_lk_norm.hip ----
+// Brightness-normalised LK (include/polychase_hip.h: pc_lk_track_normalized has the rule): what launch_lk / launch_lk_fb are
+// replaced by when the option is on.  Same parameters, same records and back arrays; one instance, whatever x86_order says.
+// launch_lk_norm reads the resident u8 and Scharr planes (LKParams::src[].img / .der, LKParams::tgt), not the uint16 ones.
+// false: window or target count out of range (nothing enqueued)
+bool launch_lk_norm(const LKParams& p, int win, hipStream_t s);
+bool launch_lk_norm_fb(const LKFBParams& p, hipStream_t s);
+
 
 // ---- kernels_tracker.hip ----
 struct RayCamera {

@@ -47,6 +47,10 @@ struct OpticalFlowOptions {
     // row is dropped when the normalised cross-correlation of the two windows LK compared lies below v (Blender's tracker
     // calls it correlation_min, default 0.75 there)
     double min_correlation = 0.0;
+    // not in the reference: brightness normalisation (include/polychase_hip.h: pc_lk_track_normalized).  true: every LK pass of the
+    // analysis tracks g (J - mean J) against (I - mean I), so a gain or bias change between two frames no longer displaces the
+    // end points (Blender's tracker calls it "normalize")
+    bool normalize = false;
 };
 // std::invalid_argument for what no run accepts; every entry point calls it before it asks for a frame
 inline void CheckOpticalFlowOptions(const OpticalFlowOptions& o) {

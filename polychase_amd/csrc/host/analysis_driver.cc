@@ -433,6 +433,8 @@ static void RunAnalysis(const VideoInfo& video_info, FrameAccessorFunction frame
     if (pc_analyzer_set_fb_threshold(eng.an, flow_options.forward_backward_threshold) != PC_OK) ThrowHip("pc_analyzer_set_fb_threshold");
     // ... the minimum correlation ...
     if (pc_analyzer_set_min_correlation(eng.an, flow_options.min_correlation) != PC_OK) ThrowHip("pc_analyzer_set_min_correlation");
+    // ... the brightness normalisation ...
+    if (pc_analyzer_set_normalize(eng.an, flow_options.normalize ? 1 : 0) != PC_OK) ThrowHip("pc_analyzer_set_normalize");
     // ... the target-side margin, off without a mask to choke ...
     const int target_margin = detection_mask.empty() ? -1 : flow_options.target_mask_margin;
     if (pc_analyzer_set_target_mask_margin(eng.an, target_margin) != PC_OK) ThrowHip("pc_analyzer_set_target_mask_margin");

@@ -479,7 +479,8 @@ PYBIND11_MODULE(polychase_core, m) {
         .def_readwrite("min_eigen_threshold", &OpticalFlowOptions::min_eigen_threshold)
         .def_readwrite("forward_backward_threshold", &OpticalFlowOptions::forward_backward_threshold)   // not in the reference; 0 = off
         .def_readwrite("target_mask_margin", &OpticalFlowOptions::target_mask_margin)   // not in the reference; -1 = off, 0..31
-        .def_readwrite("min_correlation", &OpticalFlowOptions::min_correlation);   // not in the reference; 0 = off, 0..1
+        .def_readwrite("min_correlation", &OpticalFlowOptions::min_correlation)   // not in the reference; 0 = off, 0..1
+        .def_readwrite("normalize", &OpticalFlowOptions::normalize);   // not in the reference; brightness-normalised LK, off by default
 
     py::class_<OpticalFlowProgress>(m, "OpticalFlowProgress")
         .def_readonly("progress", &OpticalFlowProgress::progress)

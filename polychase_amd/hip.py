@@ -34,6 +34,7 @@ SYMBOLS = [
     "pc_frame_set_mask_polygons", "pc_frame_download_mask", "pc_analyzer_set_mask_polygons",
     "pc_frame_download_choked_mask", "pc_lk_track_masked", "pc_analyzer_set_target_mask_margin",
     "pc_lk_track_correlated", "pc_analyzer_set_min_correlation",
+    "pc_lk_track_normalized", "pc_analyzer_set_normalize",
     "pc_lk_track", "pc_lk_track_filtered", "pc_lk_track_fb", "pc_lk_track_filtered_fb",
     "pc_analyzer_create", "pc_analyzer_destroy", "pc_analyzer_reset", "pc_analyzer_put_frame", "pc_analyzer_put_frame_f32",
     "pc_analyzer_has_frame", "pc_analyzer_frame_ingested",
@@ -160,6 +161,8 @@ def load():
     L.pc_lk_track_masked.argtypes = [vp, vp, C.POINTER(vp), C.c_int, C.POINTER(FlowOptions), C.c_double, C.c_int, vp, vp, vp]
     L.pc_lk_track_correlated.argtypes = [vp, vp, C.POINTER(vp), C.c_int, C.POINTER(FlowOptions), C.c_double, C.c_double, C.c_int, vp, vp,
                                          vp, vp]
+    L.pc_lk_track_normalized.argtypes = [vp, vp, C.POINTER(vp), C.c_int, C.POINTER(FlowOptions), C.c_int, C.c_double, C.c_double, C.c_int,
+                                         vp, vp, vp, vp, vp]
     L.pc_analyzer_create.argtypes = [vp, C.c_int, C.c_int, C.POINTER(GfttOptions), C.POINTER(FlowOptions), C.c_int,
                                      C.c_int, C.POINTER(vp)]
     L.pc_analyzer_destroy.argtypes = [vp]
@@ -182,6 +185,7 @@ def load():
     L.pc_analyzer_set_mask_polygons.argtypes = [vp, vp, vp, C.c_int, C.c_int]
     L.pc_analyzer_set_target_mask_margin.argtypes = [vp, C.c_int]
     L.pc_analyzer_set_min_correlation.argtypes = [vp, C.c_double]
+    L.pc_analyzer_set_normalize.argtypes = [vp, C.c_int]
     L.pc_peer_buffer_alloc.argtypes = [C.c_int, C.c_size_t, C.POINTER(vp)]
     L.pc_peer_buffer_free.argtypes = [C.c_int, vp]
     L.pc_peer_buffer_export.argtypes = [C.c_int, vp, C.c_char_p]
@@ -572,6 +576,25 @@ def lk_track_correlated(ctx: Context, frame1: Frame, targets: list[Frame], min_c
     return xy, st, err, sc
 
 
+def lk_track_normalized(ctx: Context, frame1: Frame, targets: list[Frame], normalize: int = 1, min_correlation: float = 0.0,
+                        fb_threshold: float = 0.0, margin: int = -1, opt: FlowOptions | None = None):
+    """brightness-normalised LK (include/polychase_hip.h: pc_lk_track_normalized): with normalize 1 the forward launch, and the
+    backward launch where fb_threshold > 0, track g (J - mean J) against (I - mean I); with 0 it is lk_track_correlated without
+    scores plus the back outputs of lk_track_fb.
+    -> next_xy [T,N,2], final status [T,N], err [T,N], back_xy [T,N,2], back_status [T,N]."""
+    opt = opt or flow_options()
+    n, t = frame1.num_keypoints, len(targets)
+    xy = np.zeros((t, n, 2), np.float32)
+    st = np.zeros((t, n), np.uint8)
+    err = np.zeros((t, n), np.float32)
+    bxy = np.zeros((t, n, 2), np.float32)
+    bst = np.zeros((t, n), np.uint8)
+    arr = (C.c_void_p * t)(*[f._h for f in targets])
+    _check(load().pc_lk_track_normalized(ctx._h, frame1._h, arr, t, C.byref(opt), int(normalize), float(min_correlation), float(fb_threshold),
+                                         int(margin), xy.ctypes.data, st.ctypes.data, err.ctypes.data, bxy.ctypes.data, bst.ctypes.data))
+    return xy, st, err, bxy, bst
+
+
 def lk_track_filtered_fb(ctx: Context, frame1: Frame, targets: list[Frame], fb_threshold: float, opt: FlowOptions | None = None):
     """lk_track_filtered on the final status of the forward-backward check (pc_lk_track_filtered_fb)."""
     opt = opt or flow_options()
@@ -683,6 +706,10 @@ class Analyzer:
     def set_min_correlation(self, min_correlation: float):
         """minimum correlation for the jobs submitted from now on; 0 = off, 0 < v <= 1 (pc_analyzer_set_min_correlation)"""
         _check(load().pc_analyzer_set_min_correlation(self._h, float(min_correlation)))
+
+    def set_normalize(self, normalize):
+        """brightness-normalised LK for the jobs submitted from now on; 0 / False = off, 1 / True = on (pc_analyzer_set_normalize)"""
+        _check(load().pc_analyzer_set_normalize(self._h, int(normalize)))
 
     def set_target_mask_margin(self, margin: int):
         """target-side masks for the frames put from now on: -1 = off, 0..31 = the margin (pc_analyzer_set_target_mask_margin);

@@ -7,13 +7,15 @@ C ABI, then `pc_lk_track` is repeated: the LK class is timed with HIP events by 
 the average launch time and a checksum of the raw outputs (equal checksums <=> bit-identical
 results, the way kernel variants are compared: POLYCHASE_HIP_LIB selects the library).
 
-    python tools/lk_bench.py [--config c2|c3] [--reps 20] [--fb PX] [--min-correlation V]
+    python tools/lk_bench.py [--config c2|c3] [--reps 20] [--fb PX] [--min-correlation V] [--normalize]
 
 --fb PX also times the forward-backward check (pc_lk_track_fb, threshold PX): the forward launch and the backward launch of
 the same call, and as the baseline the same backward work through the calls that existed before it -- per target,
 set_keypoints(q[status_f == 1]) on the target frame and pc_lk_track(target, [frame1]): eight launches.
 --min-correlation V also times the minimum-correlation check (pc_lk_track_correlated, threshold V): the forward launch and the
 correlation launch of the same call, and the share of rows the check drops.
+--normalize also times the brightness-normalised launch (pc_lk_track_normalized, normalize = 1) and reports its ratio to the plain
+launch measured above; with --fb PX the normalised backward launch beside it, against the plain backward launch.
 
 (Parity against the CPU oracle is the test suite's business: tests/test_gpu_parity.py, tests/test_fullsize_gpu.py.)
 """
@@ -89,6 +91,34 @@ def corr_timing(ctx, hip, f1, targets, fopt, thr, reps, xy, st, err):
             "forward_rows": fwd_rows, "kept_rows": kept_rows, "dropped_fraction": (fwd_rows - kept_rows) / max(1, fwd_rows)}
 
 
+def norm_timing(ctx, hip, f1, targets, fopt, fb, reps, plain_ms, st):
+    """forward (and, with fb > 0, backward) launch of pc_lk_track_normalized with the option on, against the plain launches of the
+    same build: the forward one measured by the caller, the backward one measured here"""
+    res = hip.lk_track_normalized(ctx, f1, targets, 1, 0.0, fb, -1, fopt)      # warm-up + the output that is compared
+    off = hip.lk_track_normalized(ctx, f1, targets, 0, 0.0, fb, -1, fopt)
+    hsh = hashlib.sha256()
+    for a in res:
+        hsh.update(np.ascontiguousarray(a).tobytes())
+    out = {"rows": int((res[1] == 1).sum()), "rows_option_off": int((off[1] == 1).sum()), "sha256": hsh.hexdigest()[:16]}
+    for name, flag in (("plain", 0), ("normalized", 1)):
+        ctx.enable_timing(["lk", "lk_fb"])
+        ctx.reset_timing()
+        for _ in range(reps):
+            again = hip.lk_track_normalized(ctx, f1, targets, flag, 0.0, fb, -1, fopt)
+        t = ctx.timing()
+        ctx.enable_timing(False)
+        assert all(np.array_equal(a, b) for a, b in zip(again, res if flag else off)), "results vary between launches"
+        out[name + "_forward_ms"] = t["lk"][1] / max(1, t["lk"][0])
+        if fb > 0:
+            out[name + "_backward_ms"] = t["lk_fb"][1] / max(1, t["lk_fb"][0])
+    out["forward_over_plain"] = out["normalized_forward_ms"] / out["plain_forward_ms"] if out["plain_forward_ms"] else None
+    out["forward_over_plain_of_the_first_loop"] = out["normalized_forward_ms"] / plain_ms if plain_ms else None
+    if fb > 0:
+        out["fb_threshold"] = fb
+        out["backward_over_plain"] = out["normalized_backward_ms"] / out["plain_backward_ms"] if out["plain_backward_ms"] else None
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", default="c2", choices=sorted(CONFIGS))
@@ -100,6 +130,7 @@ def main():
                     "stragglers' iterations off -- wrong results, but the time saved is the ceiling of what deferring them could gain")
     ap.add_argument("--fb", type=float, default=0.0, metavar="PX", help="also time the forward-backward check at this threshold")
     ap.add_argument("--min-correlation", type=float, default=0.0, metavar="V", help="also time the minimum-correlation check at this threshold")
+    ap.add_argument("--normalize", action="store_true", help="also time the brightness-normalised launch (with --fb: and its backward launch)")
     args = ap.parse_args()
 
     import torch
@@ -154,6 +185,8 @@ def main():
            "sha256": hsh.hexdigest()[:16], "lib": os.environ.get("POLYCHASE_HIP_LIB", "default")}
     if x86_stats is not None:
         out["x86_stats_one_launch"] = x86_stats
+    if args.normalize:
+        out["normalize"] = norm_timing(ctx, hip, f1, targets, fopt, args.fb, args.reps, ms / max(1, launches), st)
     if args.min_correlation > 0:      # (before --fb: that one leaves other keypoints on the target frames)
         out["min_correlation"] = corr_timing(ctx, hip, f1, targets, fopt, args.min_correlation, args.reps, xy, st, err)
     if args.fb > 0:

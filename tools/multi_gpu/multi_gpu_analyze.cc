@@ -2,7 +2,7 @@
 //
 //     polychase_multi_gpu --gpus N --database clip.db [--width 1920 --height 1080 --frames 64 --max-level 3]
 //                         [--transport rccl|tcp] [--share-gpu] [--port 29611] [--piece-frames 16] [--frames-file clip.rgb]
-//                         [--fb-threshold PX] [--min-correlation V]
+//                         [--fb-threshold PX] [--min-correlation V] [--normalize]
 //
 // forks N ranks BEFORE the process touches HIP (one process per GPU; --share-gpu puts every rank on GPU 0, which RCCL
 // refuses: use it with --transport tcp, the testing aid of csrc/host/multi_gpu.h), each rank calls
@@ -76,6 +76,7 @@ int RunRank(int rank, int world, int argc, char** argv) {
     fo.max_level = std::atoi(Arg(argc, argv, "--max-level", "3"));
     fo.forward_backward_threshold = std::atof(Arg(argc, argv, "--fb-threshold", "0"));   // forward-backward check, 0 = off
     fo.min_correlation = std::atof(Arg(argc, argv, "--min-correlation", "0"));           // minimum correlation, 0 = off
+    fo.normalize = Flag(argc, argv, "--normalize");                                       // brightness-normalised LK, off by default
     const size_t frame_bytes = static_cast<size_t>(w) * h * 3;
     std::ifstream in;
     if (!file.empty()) {
@@ -127,7 +128,7 @@ int main(int argc, char** argv) {
     const int world = std::atoi(Arg(argc, argv, "--gpus", "1"));
     if (world < 1 || std::string(Arg(argc, argv, "--database", "")).empty()) {
         std::fprintf(stderr, "usage: %s --gpus N --database clip.db [--width W --height H --frames n --max-level L --transport rccl|tcp "
-                             "--share-gpu --port P --piece-frames k --frames-file raw.rgb --fb-threshold px --min-correlation v]\n", argv[0]);
+                             "--share-gpu --port P --piece-frames k --frames-file raw.rgb --fb-threshold px --min-correlation v --normalize]\n", argv[0]);
         return 2;
     }
     if (const char* r = std::getenv("POLYCHASE_RANK")) return RunRank(std::atoi(r), world, argc, argv);   // launched by something else
