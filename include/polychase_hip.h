@@ -367,6 +367,58 @@ int pc_lk_track_normalized(pc_context* ctx, const pc_frame* frame1, const pc_fra
                            const pc_flow_options* opt, int normalize, double min_correlation, double fb_threshold, int margin,
                            float* next_xy, uint8_t* status, float* err, float* back_xy, uint8_t* back_status);
 
+/* ---- affine refinement (not in the reference, off by default) ----
+ * Every LK pass tracks a translating window.  Between frames up to 8 apart a rolling or zooming camera rotates and scales the
+ * window's content, and the translational fit then lands a fraction of a pixel off.  With affine == 1 ONE additional launch,
+ * directly after the forward launch, refines the end point of every forward record with status 1 at level 0 under a 6-parameter
+ * warp of the window (Blender's tracker calls it the affine motion model).  It is a refinement, not a check: it overwrites
+ * (q.x, q.y, err) of the record when the result is accepted, leaves the record untouched bit for bit otherwise, and never changes a
+ * status.  It runs before the target-mask test, the correlation pass and the backward launch, which judge the refined end points.
+ * win = window_size, n = win * win, half = (float)(win - 1) * 0.5f.  Every fp32 and fp64 operation is rounded on its own (no
+ * contraction), every sum is an exact integer (int64), and the arithmetic mode (pc_context_set_arithmetic) plays no part.
+ *   template   the correlation pass's I window plus the derivatives: at p - half in frame1's level-0 planes, floor, the bounds
+ *              test, the 14-bit weights and the template values ival (0..8160), ix, iy (DESCALE by 9 / 14) of LK's template pass,
+ *              per window pixel (c, r).  A template that fails the bounds test: no refinement for any of the keypoint's rows.
+ *   Jacobian   U = 2c - (win - 1), V = 2r - (win - 1) (twice the offset from the window centre); per pixel
+ *              g = (ix U, ix V, iy U, iy V, ix, iy); H[i][j] = sum g_i g_j: 21 exact integers below 2^53.
+ *   factor     once per keypoint, lower Cholesky of (double)H in fp64, column by column, j = 0..5: s = H[j][j]; for ascending
+ *              k < j: s = s - L[j][k] * L[j][k]; no refinement unless s > 0; L[j][j] = sqrt(s); for i > j: s = H[i][j]; for
+ *              ascending k < j: s = s - L[i][k] * L[j][k]; L[i][j] = s / L[j][j].
+ *   state      per row: centre (cx, cy) = q, the stored fp32 end point; m11 = m22 = 1.0f, m12 = m21 = 0.0f.
+ *   warped J window   pixel (c, r): u = (float)U * 0.5f, v = (float)V * 0.5f; xj = (cx + m11 * u) + m12 * v,
+ *              yj = (cy + m21 * u) + m22 * v; fx = floorf(xj), fy = floorf(yj).  The window FAILS unless -win <= fx <= w + win - 2
+ *              and -win <= fy <= h + win - 2 hold for every pixel (a NaN fails): every tap then lies inside the padded plane, so
+ *              the kernel never reads outside it, whatever it is handed.  The pixel's weights are LK's 14-bit ones of
+ *              (xj - fx, yj - fy) with w11 = 2^14 - w00 - w01 - w10; jv = DESCALE(., 9) of the four taps of the target's level-0
+ *              u8 plane, 0..8160.
+ *   iteration  at most term_max_iters times (clamped to 0..100 as in LK; eps = term_epsilon clamped to [0, 10]): evaluate the
+ *              warped window -- a failed window ends the refinement with the row unchanged --; e = jv - ival; b_i = sum e g_i, six
+ *              exact integers below 2^44; solve L L^T t = -b in fp64: forward, i = 0..5: s = -(double)b_i; for ascending k < i:
+ *              s = s - L[i][k] * y_k; y_i = s / L[i][i]; backward, i = 5..0: s = y_i; for ascending k > i: s = s - L[k][i] * t_k;
+ *              t_i = s / L[i][i].  Update in fp32: m11 += (float)(2.0 * t0), m12 += (float)(2.0 * t1), m21 += (float)(2.0 * t2),
+ *              m22 += (float)(2.0 * t3), cx += (float)t4, cy += (float)t5.  Stop when
+ *              (t4^2 + t5^2) + (double)(win - 1)^2 * (((t0^2 + t1^2) + t2^2) + t3^2) <= eps^2 in fp64.
+ *   final      the warped window once more at the final parameters (a failed window leaves the row unchanged):
+ *              err_a = (float)sum |jv - ival| / (float)(32 * n).
+ *   acceptance in fp32, all of: err_a <= err (the record's stored patch error); 0.5f <= m11 * m22 - m12 * m21 <= 2.0f;
+ *              |m11 - 1|, |m12|, |m21|, |m22 - 1| <= 0.5f; (cx - q.x)^2 + (cy - q.y)^2 <= half^2.  Accepted: the record becomes
+ *              (cx, cy, err_a, status 1); otherwise it stays (q.x, q.y, err, 1).
+ * A target identical to frame1 has e = 0 everywhere: every row whose template has a factor is accepted and stays bit-identical, m
+ * exactly the identity.  A row is never replaced by one that matches its patch worse.  At wide windows six parameters fit noise:
+ * rows of an unrelated target are accepted too, and dropping them stays the job of the checks that follow.
+ * The residual assumes brightness constancy: affine == 1 together with normalize == 1 is PC_E_INVALID (a gain-aware affine
+ * residual is a follow-up).  Records, compaction, unpacking and everything downstream are unchanged (kernels_lk_affine.hip; the
+ * rule restated in numpy: tests/lk_affine_ref.py).
+ * pc_lk_track_affine: affine == 0 is exactly pc_lk_track_normalized (nothing else is enqueued); affine == 1 adds the launch, timed
+ * under PC_K_LK (a call then shows two launches of that class).  affine_m ([n_targets][N][4] floats (m11, m12, m21, m22), may be
+ * NULL) receives the matrix the refinement ended with; affine_state ([n_targets][N] bytes, may be NULL): 0 = not run (forward
+ * status 0, or affine == 0), 1 = accepted, 2 = run and left unchanged.  affine_m is zero where the state is 0.  Any value other than
+ * 0 and 1: PC_E_INVALID. */
+int pc_lk_track_affine(pc_context* ctx, const pc_frame* frame1, const pc_frame* const* targets, int n_targets,
+                       const pc_flow_options* opt, int affine, int normalize, double min_correlation, double fb_threshold, int margin,
+                       float* next_xy, uint8_t* status, float* err, float* back_xy, uint8_t* back_status, float* affine_m,
+                       uint8_t* affine_state);
+
 /* ---- analyzer: the pipelined per-clip engine behind GenerateOpticalFlowDatabase ----
  * (cpp/opticalflow.cc:209-321).  Holds a ring of resident frames (the reference's 17-frame
  * SequentialWrapper cache, cpp/opticalflow_thread.h:34-79, generalised), builds every frame's gray
@@ -458,6 +510,11 @@ int pc_analyzer_set_min_correlation(pc_analyzer* a, double min_correlation);
  * launch, and the backward launch where the forward-backward check is on, run the normalised rule.  Jobs already submitted keep
  * theirs; pc_analyzer_reset keeps the value.  Any other value, or a null analyzer: PC_E_INVALID. */
 int pc_analyzer_set_normalize(pc_analyzer* a, int normalize);
+/* Affine refinement (pc_lk_track_affine) of the jobs submitted FROM NOW ON: 0 = off (the default), 1 = every job refines its
+ * forward records in one more launch directly after the forward one.  Jobs already submitted keep theirs; pc_analyzer_reset keeps
+ * the value.  Any other value, a null analyzer, or 1 while normalize is 1: PC_E_INVALID; pc_analyzer_submit refuses a job while
+ * both are 1. */
+int pc_analyzer_set_affine_refinement(pc_analyzer* a, int affine);
 /* Detection mask (pc_frame_set_mask, gftt.cc:45-83) of the frames put FROM NOW ON with will_detect != 0; NULL: no mask (the
  * default).  Detection is enqueued inside pc_analyzer_put_frame, so every slot of the ring keeps a mask plane of its own: a
  * detection already enqueued keeps the mask it was enqueued with, and the mask may change from frame to frame.  A host mask

@@ -147,6 +147,8 @@ def main(argv=None) -> int:
                     help="minimum correlation: drop flow rows whose reference and matched windows correlate below V, 0 < V <= 1 (0: off)")
     ap.add_argument("--normalize", action="store_true",
                     help="brightness-normalised LK: end points that survive a gain or bias change between two frames (off by default)")
+    ap.add_argument("--affine", action="store_true",
+                    help="affine refinement: end points that survive the roll and zoom between the paired frames (off by default; not with --normalize)")
     ap.add_argument("--piece-frames", type=int, default=16, help="frames per piece of the record log handed to rank 0")
     ap.add_argument("--gpus", type=int, default=0, help="launch this many ranks (one per GPU) of this command")
     args = ap.parse_args(argv)
@@ -198,6 +200,7 @@ def main(argv=None) -> int:
     fopt.forward_backward_threshold = args.fb_threshold
     fopt.min_correlation = args.min_correlation
     fopt.normalize = args.normalize
+    fopt.affine_refinement = args.affine
     if int(os.environ.get("RANK", "0")) == 0 and os.path.exists(args.database):
         os.remove(args.database)
     if world > 1:

@@ -536,6 +536,38 @@ int check_normalize(int normalize) {
     return PC_OK;
 }
 
+int check_affine(int affine, int normalize) {
+    if (affine != 0 && affine != 1) return fail(PC_E_INVALID, "affine must be 0 or 1, got %d", affine);
+    if (affine == 1 && normalize == 1) return fail(PC_E_INVALID, "affine refinement assumes brightness constancy: not together with normalize");
+    return PC_OK;
+}
+
+int run_lk_affine(pc_context* ctx, const pc_frame* frame1, const pc_frame* const* targets, int n_targets, const pc_flow_options* opt,
+                  int set, float4* affine_m, uint8_t* affine_state) {
+    hipStream_t const lk_stream = ctx->lane_stream(set);
+    const int n = frame1->n_kps;
+    if (n == 0) return PC_OK;
+    pc::AffineParams p;
+    std::memset(&p, 0, sizeof(p));
+    p.f1 = frame1->levels[0];
+    for (int t = 0; t < n_targets; t++) p.timg[t] = targets[t]->levels[0].img;
+    p.n_targets = n_targets;
+    p.n = n;
+    p.win = frame1->win;
+    // TermCriteria clamps of calcOpticalFlowPyrLK, as in run_lk
+    p.max_iters = std::min(std::max(opt->term_max_iters, 0), 100);
+    const double eps = std::min(std::max(opt->term_epsilon, 0.), 10.);
+    p.eps_sq = eps * eps;
+    p.pts = frame1->d_kps;
+    p.perm = frame1->perm_valid ? frame1->d_perm : ctx->lk_perm.p;   // the order run_lk visited the keypoints in
+    p.rec = ctx->lk_rec[set].p;
+    p.affine_m = affine_m;
+    p.affine_state = affine_state;
+    ScopedTimer tm(ctx, PC_K_LK, lk_stream);   // no class of its own: a job with the option shows two lk launches
+    if (!pc::launch_lk_affine(p, lk_stream)) return fail(PC_E_INVALID, "unsupported window size %d", frame1->win);
+    return PC_OK;
+}
+
 int check_min_correlation(double min_correlation) {
     if (!(min_correlation >= 0.0 && min_correlation <= 1.0)) return fail(PC_E_INVALID, "min_correlation must be in [0, 1]");   // a NaN fails
     return PC_OK;
@@ -825,6 +857,8 @@ void pc_context_destroy(pc_context* c) {
     c->lk_back_status.release();
     c->lk_choked.release();
     c->lk_corr.release();
+    c->lk_affine_m.release();
+    c->lk_affine_state.release();
     c->lk_cidx.release();
     for (auto& b : c->lk_block_counts) b.release();
     c->lk_perm.release();
@@ -1369,10 +1403,12 @@ int pc_frame_set_keypoints(pc_context* ctx, pc_frame* f, const float* xy, int n)
 // ---------------------------------------------------------------------------------------------
 static int lk_track_impl(pc_context* ctx, const pc_frame* frame1, const pc_frame* const* targets, int n_targets,
                          const pc_flow_options* opt, double fb_threshold, int margin, float* next_xy, uint8_t* status, float* err,
-                         float* back_xy, uint8_t* back_status, double min_correlation = 0.0, float* corr = nullptr, int normalize = 0) {
+                         float* back_xy, uint8_t* back_status, double min_correlation = 0.0, float* corr = nullptr, int normalize = 0,
+                         int affine = 0, float* affine_m = nullptr, uint8_t* affine_state = nullptr) {
     int rc = check_target_margin(margin, true);   // first: a margin is refused whatever the handles
     if (rc != PC_OK) return rc;
     if ((rc = check_normalize(normalize)) != PC_OK) return rc;   // ... and so is a switch that is neither off nor on
+    if ((rc = check_affine(affine, normalize)) != PC_OK) return rc;
     if ((rc = check_min_correlation(min_correlation)) != PC_OK) return rc;   // ... and so is a correlation
     if ((rc = check_lk_args(ctx, frame1, targets, n_targets, opt)) != PC_OK) return rc;
     if (!next_xy || !status || !err) return fail(PC_E_INVALID, "null output");
@@ -1382,6 +1418,26 @@ static int lk_track_impl(pc_context* ctx, const pc_frame* frame1, const pc_frame
     rc = run_lk(ctx, frame1, targets, n_targets, opt, 0, normalize);
     if (rc != PC_OK) return rc;
     const size_t rows = (size_t)frame1->n_kps * n_targets;
+    if (rows > 0 && !affine) {
+        if (affine_m) std::memset(affine_m, 0, rows * sizeof(float4));
+        if (affine_state) std::memset(affine_state, 0, rows);
+    }
+    if (rows > 0 && affine) {
+        // affine refinement: directly after the forward launch, so that every check below judges the refined end points
+        if (affine_m) {
+            PC_HIP(ctx->lk_affine_m.ensure(rows));
+            PC_HIP(hipMemsetAsync(ctx->lk_affine_m.p, 0, rows * sizeof(float4), ctx->stream));
+        }
+        if (affine_state) {
+            PC_HIP(ctx->lk_affine_state.ensure(rows));
+            PC_HIP(hipMemsetAsync(ctx->lk_affine_state.p, 0, rows, ctx->stream));
+        }
+        rc = run_lk_affine(ctx, frame1, targets, n_targets, opt, 0, affine_m ? ctx->lk_affine_m.p : nullptr,
+                           affine_state ? ctx->lk_affine_state.p : nullptr);
+        if (rc != PC_OK) return rc;
+        if (affine_m) PC_HIP(hipMemcpyAsync(affine_m, ctx->lk_affine_m.p, rows * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream));
+        if (affine_state) PC_HIP(hipMemcpyAsync(affine_state, ctx->lk_affine_state.p, rows, hipMemcpyDeviceToHost, ctx->stream));
+    }
     if (margin >= 0 && rows > 0) {
         // target-side masks: each masked target's plane -- choked into the context's scratch when there is a margin -- judges
         // the rows that end in it, before the backward launch
@@ -1465,6 +1521,14 @@ int pc_lk_track_normalized(pc_context* ctx, const pc_frame* frame1, const pc_fra
                            float* next_xy, uint8_t* status, float* err, float* back_xy, uint8_t* back_status) {
     return lk_track_impl(ctx, frame1, targets, n_targets, opt, fb_threshold, margin, next_xy, status, err, back_xy, back_status,
                          min_correlation, nullptr, normalize);
+}
+
+int pc_lk_track_affine(pc_context* ctx, const pc_frame* frame1, const pc_frame* const* targets, int n_targets,
+                       const pc_flow_options* opt, int affine, int normalize, double min_correlation, double fb_threshold, int margin,
+                       float* next_xy, uint8_t* status, float* err, float* back_xy, uint8_t* back_status, float* affine_m,
+                       uint8_t* affine_state) {
+    return lk_track_impl(ctx, frame1, targets, n_targets, opt, fb_threshold, margin, next_xy, status, err, back_xy, back_status,
+                         min_correlation, nullptr, normalize, affine, affine_m, affine_state);
 }
 
 static int lk_track_filtered_impl(pc_context* ctx, const pc_frame* frame1, const pc_frame* const* targets, int n_targets,

@@ -106,6 +106,7 @@ struct pc_analyzer {
     double fb_threshold = 0.0;           // forward-backward check of the jobs submitted from now on (0: off)
     double min_correlation = 0.0;        // minimum correlation of the jobs submitted from now on (0: off)
     int normalize = 0;                   // brightness-normalised LK for the jobs submitted from now on (0: off)
+    int affine = 0;                      // affine refinement of the jobs submitted from now on (0: off); submit refuses 1 beside normalize
     // Target-side masks (pc_analyzer_set_target_mask_margin): -1 off, else the margin of the frames put from now on.  While it is
     // >= 0 and a mask is in force every frame put takes the mask -- pc_frame::target_margin is the frame's role as a target,
     // beside mask_on, which stays the detection's -- and with a margin > 0 its choked plane too.
@@ -444,6 +445,7 @@ int pc_analyzer_submit(pc_analyzer* a, int32_t frame1, const int32_t* targets, i
     if (!a || (n_targets > 0 && !targets)) return fail(PC_E_INVALID, "null argument");
     if (n_targets < 0 || n_targets > PC_MAX_TARGETS) return fail(PC_E_INVALID, "n_targets must be in [0,%d]", PC_MAX_TARGETS);
     if (a->job_count == a->jobs.size()) return fail(PC_E_STATE, "%zu jobs already in flight: call pc_analyzer_collect", a->job_count);
+    if (int arc = check_affine(a->affine, a->normalize)) return arc;   // normalize may have been switched on after the refinement
     pc_context* ctx = a->ctx;
     PC_HIP(hipSetDevice(ctx->device));
     HelperPriorityScope prio_scope(a->prio.hi);
@@ -531,6 +533,8 @@ int pc_analyzer_submit(pc_analyzer* a, int32_t frame1, const int32_t* targets, i
             a->gate_armed = true;
         }
         if ((rc = run_lk(ctx, s1->frame, tg, n_targets, &a->fopt, lane, a->normalize)) != PC_OK) return rc;
+        // affine refinement: the launch follows the forward one on the same lane; everything below judges the refined end points
+        if (a->affine && (rc = run_lk_affine(ctx, s1->frame, tg, n_targets, &a->fopt, lane)) != PC_OK) return rc;
         // target-side masks: rows that end where their target's plane is off are dropped before the backward launch looks at them
         {
             const uint8_t* plane[PC_MAX_TARGETS] = {};
@@ -640,6 +644,14 @@ int pc_analyzer_set_normalize(pc_analyzer* a, int normalize) {
     if (int rc = check_normalize(normalize)) return rc;   // first: a value is refused whatever the handle
     if (!a) return fail(PC_E_INVALID, "null analyzer");
     a->normalize = normalize;
+    return PC_OK;
+}
+
+int pc_analyzer_set_affine_refinement(pc_analyzer* a, int affine) {
+    if (int rc = check_affine(affine, 0)) return rc;   // first: a value is refused whatever the handle
+    if (!a) return fail(PC_E_INVALID, "null analyzer");
+    if (int rc = check_affine(affine, a->normalize)) return rc;
+    a->affine = affine;
     return PC_OK;
 }
 

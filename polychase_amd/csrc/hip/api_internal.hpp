@@ -84,6 +84,12 @@ int run_lk(pc_context* ctx, const pc_frame* frame1, const pc_frame* const* targe
 int check_fb_threshold(double fb_threshold);
 int run_lk_fb(pc_context* ctx, const pc_frame* frame1, const pc_frame* const* targets, int n_targets, const pc_flow_options* opt,
               double fb_threshold, int set = 0, float2* back_xy = nullptr, uint8_t* back_status = nullptr, int normalize = 0);
+// affine refinement (include/polychase_hip.h: pc_lk_track_affine) of the records run_lk has just left in set `set`, on the same
+// lane, before run_lk_target_mask, run_lk_corr and run_lk_fb, which then judge the refined end points.  check_affine: 0 or 1, and
+// not together with normalize; affine_m / affine_state: device arrays [target][n], zeroed by the caller, or null
+int check_affine(int affine, int normalize);
+int run_lk_affine(pc_context* ctx, const pc_frame* frame1, const pc_frame* const* targets, int n_targets, const pc_flow_options* opt,
+                  int set = 0, float4* affine_m = nullptr, uint8_t* affine_state = nullptr);
 // minimum correlation (include/polychase_hip.h: pc_lk_track_correlated) on the records run_lk has just left in set `set`, on the
 // same lane, between run_lk_target_mask and run_lk_fb.  check_min_correlation: 0 <= v <= 1; run_lk_corr drops the rows below
 // min_correlation (0: none) and, with `corr` (device, [target][n]), writes the scores

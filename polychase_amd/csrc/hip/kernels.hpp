@@ -283,6 +283,27 @@ struct CorrParams {
 // false: window or target count out of range (nothing enqueued)
 bool launch_lk_corr(const CorrParams& p, hipStream_t s);
 
+// ---- kernels_lk_affine.hip ----
+// Affine refinement (include/polychase_hip.h: pc_lk_track_affine has the rule): for every record of the forward launch with
+// status 1 the end point is refined at level 0 under a 6-parameter warp of the window; (q, err) of the record is overwritten when
+// the result is accepted, the status never changes.  One launch per frame1 job, directly after the forward launch.
+struct AffineParams {
+    Level f1;                  // frame1, level 0 (u8 and Scharr planes)
+    const uint8_t* timg[8];    // [target] interior origins of the targets' level-0 u8 planes (frame1's geometry)
+    int n_targets;
+    int n;                     // keypoints
+    int win;                   // 3 .. PC_MAX_WINDOW, the padding of the planes
+    int max_iters;             // TermCriteria clamps of the forward launch
+    double eps_sq;
+    const float2* pts;         // frame1's keypoints
+    const uint32_t* perm;      // visiting order of the forward launch (slot -> keypoint) or null
+    float4* rec;               // the forward launch's records, LKParams::out_rec
+    float4* affine_m;          // [target][n] in keypoint order: (m11, m12, m21, m22) of the rows with status 1; or null
+    uint8_t* affine_state;     // [target][n]: 1 accepted, 2 left unchanged, written for the rows with status 1 only; or null
+};
+// false: window or target count out of range (nothing enqueued)
+bool launch_lk_affine(const AffineParams& p, hipStream_t s);
+
 // ---- kernels_lk_norm.hip ----
 // Brightness-normalised LK (include/polychase_hip.h: pc_lk_track_normalized has the rule): what launch_lk / launch_lk_fb are
 // replaced by when the option is on.  Same parameters, same records and back arrays; one instance, whatever x86_order says.

@@ -51,6 +51,10 @@ struct OpticalFlowOptions {
     // analysis tracks g (J - mean J) against (I - mean I), so a gain or bias change between two frames no longer displaces the
     // end points (Blender's tracker calls it "normalize")
     bool normalize = false;
+    // not in the reference: affine refinement (include/polychase_hip.h: pc_lk_track_affine).  true: the end point of every forward
+    // row is refined at level 0 under a 6-parameter warp of the window, so that it survives the roll and zoom between frames up
+    // to 8 apart (Blender's tracker calls it the affine motion model).  Not together with normalize.
+    bool affine_refinement = false;
 };
 // std::invalid_argument for what no run accepts; every entry point calls it before it asks for a frame
 inline void CheckOpticalFlowOptions(const OpticalFlowOptions& o) {
@@ -58,6 +62,8 @@ inline void CheckOpticalFlowOptions(const OpticalFlowOptions& o) {
         throw std::invalid_argument("target_mask_margin must be -1 (off) or 0..31, got " + std::to_string(o.target_mask_margin));
     if (!(o.min_correlation >= 0.0 && o.min_correlation <= 1.0))   // a NaN fails
         throw std::invalid_argument("min_correlation must be in [0, 1] (0 = off), got " + std::to_string(o.min_correlation));
+    if (o.affine_refinement && o.normalize)
+        throw std::invalid_argument("affine_refinement assumes brightness constancy: it cannot be combined with normalize");
 }
 
 // The clip: frames first_frame .. first_frame + num_frames - 1, all width x height.

@@ -435,6 +435,8 @@ static void RunAnalysis(const VideoInfo& video_info, FrameAccessorFunction frame
     if (pc_analyzer_set_min_correlation(eng.an, flow_options.min_correlation) != PC_OK) ThrowHip("pc_analyzer_set_min_correlation");
     // ... the brightness normalisation ...
     if (pc_analyzer_set_normalize(eng.an, flow_options.normalize ? 1 : 0) != PC_OK) ThrowHip("pc_analyzer_set_normalize");
+    // ... the affine refinement (after the normalisation it excludes: a parked engine may hold either from its last run) ...
+    if (pc_analyzer_set_affine_refinement(eng.an, flow_options.affine_refinement ? 1 : 0) != PC_OK) ThrowHip("pc_analyzer_set_affine_refinement");
     // ... the target-side margin, off without a mask to choke ...
     const int target_margin = detection_mask.empty() ? -1 : flow_options.target_mask_margin;
     if (pc_analyzer_set_target_mask_margin(eng.an, target_margin) != PC_OK) ThrowHip("pc_analyzer_set_target_mask_margin");

@@ -480,7 +480,8 @@ PYBIND11_MODULE(polychase_core, m) {
         .def_readwrite("forward_backward_threshold", &OpticalFlowOptions::forward_backward_threshold)   // not in the reference; 0 = off
         .def_readwrite("target_mask_margin", &OpticalFlowOptions::target_mask_margin)   // not in the reference; -1 = off, 0..31
         .def_readwrite("min_correlation", &OpticalFlowOptions::min_correlation)   // not in the reference; 0 = off, 0..1
-        .def_readwrite("normalize", &OpticalFlowOptions::normalize);   // not in the reference; brightness-normalised LK, off by default
+        .def_readwrite("normalize", &OpticalFlowOptions::normalize)   // not in the reference; brightness-normalised LK, off by default
+        .def_readwrite("affine_refinement", &OpticalFlowOptions::affine_refinement);   // not in the reference; off by default, not with normalize
 
     py::class_<OpticalFlowProgress>(m, "OpticalFlowProgress")
         .def_readonly("progress", &OpticalFlowProgress::progress)

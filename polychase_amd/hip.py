@@ -35,6 +35,7 @@ SYMBOLS = [
     "pc_frame_download_choked_mask", "pc_lk_track_masked", "pc_analyzer_set_target_mask_margin",
     "pc_lk_track_correlated", "pc_analyzer_set_min_correlation",
     "pc_lk_track_normalized", "pc_analyzer_set_normalize",
+    "pc_lk_track_affine", "pc_analyzer_set_affine_refinement",
     "pc_lk_track", "pc_lk_track_filtered", "pc_lk_track_fb", "pc_lk_track_filtered_fb",
     "pc_analyzer_create", "pc_analyzer_destroy", "pc_analyzer_reset", "pc_analyzer_put_frame", "pc_analyzer_put_frame_f32",
     "pc_analyzer_has_frame", "pc_analyzer_frame_ingested",
@@ -163,6 +164,8 @@ def load():
                                          vp, vp]
     L.pc_lk_track_normalized.argtypes = [vp, vp, C.POINTER(vp), C.c_int, C.POINTER(FlowOptions), C.c_int, C.c_double, C.c_double, C.c_int,
                                          vp, vp, vp, vp, vp]
+    L.pc_lk_track_affine.argtypes = [vp, vp, C.POINTER(vp), C.c_int, C.POINTER(FlowOptions), C.c_int, C.c_int, C.c_double, C.c_double, C.c_int,
+                                     vp, vp, vp, vp, vp, vp, vp]
     L.pc_analyzer_create.argtypes = [vp, C.c_int, C.c_int, C.POINTER(GfttOptions), C.POINTER(FlowOptions), C.c_int,
                                      C.c_int, C.POINTER(vp)]
     L.pc_analyzer_destroy.argtypes = [vp]
@@ -186,6 +189,7 @@ def load():
     L.pc_analyzer_set_target_mask_margin.argtypes = [vp, C.c_int]
     L.pc_analyzer_set_min_correlation.argtypes = [vp, C.c_double]
     L.pc_analyzer_set_normalize.argtypes = [vp, C.c_int]
+    L.pc_analyzer_set_affine_refinement.argtypes = [vp, C.c_int]
     L.pc_peer_buffer_alloc.argtypes = [C.c_int, C.c_size_t, C.POINTER(vp)]
     L.pc_peer_buffer_free.argtypes = [C.c_int, vp]
     L.pc_peer_buffer_export.argtypes = [C.c_int, vp, C.c_char_p]
@@ -595,6 +599,29 @@ def lk_track_normalized(ctx: Context, frame1: Frame, targets: list[Frame], norma
     return xy, st, err, bxy, bst
 
 
+def lk_track_affine(ctx: Context, frame1: Frame, targets: list[Frame], affine: int = 1, normalize: int = 0, min_correlation: float = 0.0,
+                    fb_threshold: float = 0.0, margin: int = -1, opt: FlowOptions | None = None):
+    """affine refinement of the forward rows (include/polychase_hip.h: pc_lk_track_affine): with affine 1 one more launch directly
+    after the forward one refines every end point at level 0 under a 6-parameter warp of the window, and the checks judge the
+    refined rows; with 0 it is lk_track_normalized.  affine 1 with normalize 1 is refused.
+    -> next_xy [T,N,2], final status [T,N], err [T,N], back_xy [T,N,2], back_status [T,N], affine_m [T,N,4] (m11, m12, m21, m22),
+    affine_state [T,N] (0 not run, 1 accepted, 2 left unchanged)."""
+    opt = opt or flow_options()
+    n, t = frame1.num_keypoints, len(targets)
+    xy = np.zeros((t, n, 2), np.float32)
+    st = np.zeros((t, n), np.uint8)
+    err = np.zeros((t, n), np.float32)
+    bxy = np.zeros((t, n, 2), np.float32)
+    bst = np.zeros((t, n), np.uint8)
+    am = np.zeros((t, n, 4), np.float32)
+    ast = np.zeros((t, n), np.uint8)
+    arr = (C.c_void_p * t)(*[f._h for f in targets])
+    _check(load().pc_lk_track_affine(ctx._h, frame1._h, arr, t, C.byref(opt), int(affine), int(normalize), float(min_correlation),
+                                     float(fb_threshold), int(margin), xy.ctypes.data, st.ctypes.data, err.ctypes.data, bxy.ctypes.data,
+                                     bst.ctypes.data, am.ctypes.data, ast.ctypes.data))
+    return xy, st, err, bxy, bst, am, ast
+
+
 def lk_track_filtered_fb(ctx: Context, frame1: Frame, targets: list[Frame], fb_threshold: float, opt: FlowOptions | None = None):
     """lk_track_filtered on the final status of the forward-backward check (pc_lk_track_filtered_fb)."""
     opt = opt or flow_options()
@@ -710,6 +737,11 @@ class Analyzer:
     def set_normalize(self, normalize):
         """brightness-normalised LK for the jobs submitted from now on; 0 / False = off, 1 / True = on (pc_analyzer_set_normalize)"""
         _check(load().pc_analyzer_set_normalize(self._h, int(normalize)))
+
+    def set_affine_refinement(self, affine):
+        """affine refinement for the jobs submitted from now on; 0 / False = off, 1 / True = on, refused while normalize is on
+        (pc_analyzer_set_affine_refinement)"""
+        _check(load().pc_analyzer_set_affine_refinement(self._h, int(affine)))
 
     def set_target_mask_margin(self, margin: int):
         """target-side masks for the frames put from now on: -1 = off, 0..31 = the margin (pc_analyzer_set_target_mask_margin);

@@ -3,7 +3,7 @@
 addon experiences), next to bench.py's HBM-resident number.  Not the headline metric.
 
   python tools/e2e_bench.py [--config c2|c3] [--frames 60] [--mask-fraction F [--mask-polygon] [--mask-outline N]
-                             [--target-mask-margin R]] [--min-correlation V] [--normalize]
+                             [--target-mask-margin R]] [--min-correlation V] [--normalize] [--affine]
 
 Modes: frames as torch CUDA tensors / host numpy arrays (PCIe upload included), with and without the
 SQLite insert.  --mask-fraction F: every run takes detection_mask = a centred rectangle of the frame's aspect covering F of
@@ -21,7 +21,8 @@ per-class pass -- rows that end where the mask, choked by R pixels, is off are d
 then also report the mean number of flow rows per frame.  --min-correlation V: OpticalFlowOptions.min_correlation of every run, and
 of the per-class pass (class "lk_corr") -- rows whose reference and matched windows correlate below V are dropped (0, the default:
 off); the SQLite modes then report the mean number of flow rows per frame too.  --normalize: OpticalFlowOptions.normalize of every
-run, and of the per-class pass (the normalised launch is timed under class "lk")."""
+run, and of the per-class pass (the normalised launch is timed under class "lk").  --affine: OpticalFlowOptions.affine_refinement of
+every run, and of the per-class pass (the refinement launch is timed under class "lk" too: two launches per step)."""
 import argparse
 import json
 import os
@@ -33,7 +34,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
-def per_class_ms(w, h, ml, frames, mask, steps=40, polygons=None, target_margin=-1, min_correlation=0.0, normalize=False):
+def per_class_ms(w, h, ml, frames, mask, steps=40, polygons=None, target_margin=-1, min_correlation=0.0, normalize=False, affine=False):
     """one pipelined pass (polychase_amd.pipeline.ClipAnalyzer) with every kernel class timed: 20 untimed steps, then `steps`"""
     from polychase_amd import hip
     from polychase_amd.pipeline import ClipAnalyzer
@@ -47,6 +48,7 @@ def per_class_ms(w, h, ml, frames, mask, steps=40, polygons=None, target_margin=
     an.an.set_target_mask_margin(target_margin)
     an.an.set_min_correlation(min_correlation)
     an.an.set_normalize(normalize)
+    an.an.set_affine_refinement(affine)
     steps = min(steps, len(frames) - 9 - 29)
     an.run(range(9, 29), None)
     ctx.synchronize()
@@ -72,6 +74,7 @@ def main():
     ap.add_argument("--target-mask-margin", type=int, default=-1)
     ap.add_argument("--min-correlation", type=float, default=0.0)
     ap.add_argument("--normalize", action="store_true")
+    ap.add_argument("--affine", action="store_true")
     a = ap.parse_args()
     import torch
     from polychase_amd import synth
@@ -88,6 +91,7 @@ def main():
     fo.target_mask_margin = a.target_mask_margin
     fo.min_correlation = a.min_correlation
     fo.normalize = a.normalize
+    fo.affine_refinement = a.affine
     vi = core.VideoInfo(w, h, 1, a.frames)
     out = {}
     mask = None
@@ -127,10 +131,12 @@ def main():
         out["min_correlation"] = a.min_correlation
     if a.normalize:
         out["normalize"] = True
+    if a.affine:
+        out["affine_refinement"] = True
     if a.frames >= 39:
         out["gpu_ms_per_step"] = per_class_ms(w, h, ml, dev, mask, polygons=polygons,
                                               target_margin=a.target_mask_margin if a.mask_fraction is not None else -1,
-                                              min_correlation=a.min_correlation, normalize=a.normalize)
+                                              min_correlation=a.min_correlation, normalize=a.normalize, affine=a.affine)
     else:
         out["gpu_ms_per_step"] = {"skipped": "the per-class pass needs --frames 39 or more (20 untimed steps, then at least one)"}
     with tempfile.TemporaryDirectory() as td:

@@ -7,7 +7,7 @@ C ABI, then `pc_lk_track` is repeated: the LK class is timed with HIP events by 
 the average launch time and a checksum of the raw outputs (equal checksums <=> bit-identical
 results, the way kernel variants are compared: POLYCHASE_HIP_LIB selects the library).
 
-    python tools/lk_bench.py [--config c2|c3] [--reps 20] [--fb PX] [--min-correlation V] [--normalize]
+    python tools/lk_bench.py [--config c2|c3] [--reps 20] [--fb PX] [--min-correlation V] [--normalize] [--affine]
 
 --fb PX also times the forward-backward check (pc_lk_track_fb, threshold PX): the forward launch and the backward launch of
 the same call, and as the baseline the same backward work through the calls that existed before it -- per target,
@@ -16,6 +16,8 @@ set_keypoints(q[status_f == 1]) on the target frame and pc_lk_track(target, [fra
 correlation launch of the same call, and the share of rows the check drops.
 --normalize also times the brightness-normalised launch (pc_lk_track_normalized, normalize = 1) and reports its ratio to the plain
 launch measured above; with --fb PX the normalised backward launch beside it, against the plain backward launch.
+--affine also times the affine refinement (pc_lk_track_affine, affine = 1): its launch is timed under the forward launch's class, so
+the figure is the class total of the calls with the option minus that of the same number of calls without it.
 
 (Parity against the CPU oracle is the test suite's business: tests/test_gpu_parity.py, tests/test_fullsize_gpu.py.)
 """
@@ -119,6 +121,37 @@ def norm_timing(ctx, hip, f1, targets, fopt, fb, reps, plain_ms, st):
     return out
 
 
+def affine_timing(ctx, hip, f1, targets, fopt, reps, xy, st, err):
+    """forward + refinement launch of pc_lk_track_affine against the forward launch alone (affine = 0) in alternating rounds; both
+    launches are timed under class "lk", so the refinement's time is the difference of the class totals"""
+    res = hip.lk_track_affine(ctx, f1, targets, 1, opt=fopt)      # warm-up + the output that is compared
+    off = hip.lk_track_affine(ctx, f1, targets, 0, opt=fopt)
+    assert np.array_equal(off[0], xy) and np.array_equal(off[1], st) and np.array_equal(off[2], err), "affine = 0 changed a forward value"
+    assert np.array_equal(res[1], st), "the refinement changed a status"
+    hsh = hashlib.sha256()
+    for a in res:
+        hsh.update(np.ascontiguousarray(a).tobytes())
+    ms, launches = {0: 0.0, 1: 0.0}, {0: 0, 1: 0}
+    ctx.enable_timing(["lk"])
+    for _ in range(reps):
+        for flag in (0, 1):
+            ctx.reset_timing()
+            again = hip.lk_track_affine(ctx, f1, targets, flag, opt=fopt)
+            t = ctx.timing()["lk"]
+            launches[flag] += t[0]
+            ms[flag] += t[1]
+    ctx.enable_timing(False)
+    assert all(np.array_equal(a, b) for a, b in zip(again, res)), "results vary between launches"
+    assert launches[0] == reps and launches[1] == 2 * reps, launches
+    fwd_ms, aff_ms = ms[0] / reps, (ms[1] - ms[0]) / reps
+    state = res[6]
+    fwd_rows, accepted = int((st == 1).sum()), int((state == 1).sum())
+    moved = np.hypot(*(res[0] - xy)[state == 1].T)
+    return {"forward_ms": fwd_ms, "affine_ms": aff_ms, "affine_over_forward": aff_ms / fwd_ms if fwd_ms else None, "forward_rows": fwd_rows,
+            "accepted_rows": accepted, "accepted_fraction": accepted / max(1, fwd_rows),
+            "median_move_px": float(np.median(moved)) if accepted else None, "sha256": hsh.hexdigest()[:16]}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", default="c2", choices=sorted(CONFIGS))
@@ -131,6 +164,7 @@ def main():
     ap.add_argument("--fb", type=float, default=0.0, metavar="PX", help="also time the forward-backward check at this threshold")
     ap.add_argument("--min-correlation", type=float, default=0.0, metavar="V", help="also time the minimum-correlation check at this threshold")
     ap.add_argument("--normalize", action="store_true", help="also time the brightness-normalised launch (with --fb: and its backward launch)")
+    ap.add_argument("--affine", action="store_true", help="also time the affine refinement launch beside the forward launch")
     args = ap.parse_args()
 
     import torch
@@ -187,6 +221,8 @@ def main():
         out["x86_stats_one_launch"] = x86_stats
     if args.normalize:
         out["normalize"] = norm_timing(ctx, hip, f1, targets, fopt, args.fb, args.reps, ms / max(1, launches), st)
+    if args.affine:
+        out["affine"] = affine_timing(ctx, hip, f1, targets, fopt, args.reps, xy, st, err)
     if args.min_correlation > 0:      # (before --fb: that one leaves other keypoints on the target frames)
         out["min_correlation"] = corr_timing(ctx, hip, f1, targets, fopt, args.min_correlation, args.reps, xy, st, err)
     if args.fb > 0:

@@ -2,7 +2,7 @@
 //
 //     polychase_multi_gpu --gpus N --database clip.db [--width 1920 --height 1080 --frames 64 --max-level 3]
 //                         [--transport rccl|tcp] [--share-gpu] [--port 29611] [--piece-frames 16] [--frames-file clip.rgb]
-//                         [--fb-threshold PX] [--min-correlation V] [--normalize]
+//                         [--fb-threshold PX] [--min-correlation V] [--normalize] [--affine]
 //
 // forks N ranks BEFORE the process touches HIP (one process per GPU; --share-gpu puts every rank on GPU 0, which RCCL
 // refuses: use it with --transport tcp, the testing aid of csrc/host/multi_gpu.h), each rank calls
@@ -77,6 +77,7 @@ int RunRank(int rank, int world, int argc, char** argv) {
     fo.forward_backward_threshold = std::atof(Arg(argc, argv, "--fb-threshold", "0"));   // forward-backward check, 0 = off
     fo.min_correlation = std::atof(Arg(argc, argv, "--min-correlation", "0"));           // minimum correlation, 0 = off
     fo.normalize = Flag(argc, argv, "--normalize");                                       // brightness-normalised LK, off by default
+    fo.affine_refinement = Flag(argc, argv, "--affine");                                  // affine refinement, off by default
     const size_t frame_bytes = static_cast<size_t>(w) * h * 3;
     std::ifstream in;
     if (!file.empty()) {
@@ -128,7 +129,7 @@ int main(int argc, char** argv) {
     const int world = std::atoi(Arg(argc, argv, "--gpus", "1"));
     if (world < 1 || std::string(Arg(argc, argv, "--database", "")).empty()) {
         std::fprintf(stderr, "usage: %s --gpus N --database clip.db [--width W --height H --frames n --max-level L --transport rccl|tcp "
-                             "--share-gpu --port P --piece-frames k --frames-file raw.rgb --fb-threshold px --min-correlation v --normalize]\n", argv[0]);
+                             "--share-gpu --port P --piece-frames k --frames-file raw.rgb --fb-threshold px --min-correlation v --normalize --affine]\n", argv[0]);
         return 2;
     }
     if (const char* r = std::getenv("POLYCHASE_RANK")) return RunRank(std::atoi(r), world, argc, argv);   // launched by something else
