@@ -122,6 +122,56 @@ int pc_context_pci_bus_id(pc_context* ctx, char* buf, int len);
 int pc_context_download(pc_context* ctx, void* dst_host, const void* src_device, size_t bytes);
 int pc_context_set_arithmetic(pc_context* ctx, int flags);
 int pc_context_get_arithmetic(const pc_context* ctx);
+
+/* ---- gray conversion (not in the reference): which channels are tracked, and a transfer curve for float frames ----
+ * How an RGB frame becomes the gray plane that detection and LK read.  The default is the reference's: cv::cvtColor's
+ * Y = (9798 R + 19235 G + 3735 B + 2^14) >> 15 on u8 channels, float channels first through the addon's `(x * 255).astype(uint8)`
+ * (pc_frame_set_rgb_f32).  A conversion replaces either part:
+ *   weights      three integers weight_r, weight_g, weight_b, each 0 .. 32768, sum exactly 32768:
+ *                Y = (weight_r R + weight_g G + weight_b B + 2^14) >> 15 on the u8 channel values in unsigned 32-bit; always
+ *                0 .. 255; (32768, 0, 0) gives exactly R.  Callers quantise user weights (r, g, b), finite, >= 0, s = r + g + b > 0,
+ *                in fp64 as q_c = floor((c / s) * 32768.0 + 0.5) and add the residual 32768 - (q_r + q_g + q_b) to the channel
+ *                with the largest input weight, ties in the order R, G, B.  (0.299, 0.587, 0.114) quantises to (9798, 19234,
+ *                3736), NOT to the default's constants: the reference's bits come from the default alone.
+ *   float_table  a host pointer to PC_TRANSFER_ENTRIES bytes, or NULL = the `(x * 255)` rule.  With a table a float channel
+ *                value v with fp32 pattern `bits` becomes table[idx]: idx = 0 unless v >= 2^-16 (NaN, negatives, zeros,
+ *                denormals and tiny values), else idx = min((bits >> 13) - (111 << 10) + 1, PC_TRANSFER_ENTRIES - 1).  Entry
+ *                i >= 1 thus covers [x_i, x_i + 2^e / 1024) with e = -16 + (i - 1) / 1024, m = (i - 1) mod 1024,
+ *                x_i = 2^e (1 + m / 1024): 20 octaves in 1024 steps each; values >= 16 and +inf read the last entry, so
+ *                highlights clamp where the `(x * 255)` rule wraps.  Alpha is ignored.  The three channel values then go through
+ *                the weights.  No floating-point arithmetic happens on the device: the kernels look the value up.
+ * pc_context_set_gray_conversion: NULL = the default.  Weights outside 0 .. 32768 or with another sum: PC_E_INVALID (checked
+ * before the handle), and the previous conversion stays in force.  The table is copied into device memory the context owns.  A
+ * per-run call: it may wait for the context's streams.  It takes effect for every frame put afterwards through pc_frame_set_rgb,
+ * pc_frame_set_rgb_f32 and pc_analyzer_put_frame[_f32] of this context; weights apply to u8 and float RGB, the table to float
+ * frames only; gray sources (pc_frame_set_gray) are untouched.  With the default conversion these calls enqueue exactly what
+ * they enqueue without this call ever made.
+ * pc_context_get_gray_conversion: the conversion in force; c->float_table is NULL without a table and otherwise `table_out` (may
+ * be NULL), which then receives the PC_TRANSFER_ENTRIES bytes.
+ * pc_float_transfer_table: the built-in tables, computed on the host in fp64 (no device, no context): entry 0 is 0; for i >= 1
+ * y = (x_i + 2^e / 2048) * 2^exposure, the interval's midpoint under an exposure of `exposure` stops, and
+ * code = floor(255 * min(f(y), 1) + 0.5) with
+ *   PC_TRANSFER_SRGB   f = y <= 0.0031308 ? 12.92 y : 1.055 pow(y, 1 / 2.4) - 0.055   (gamma unused)
+ *   PC_TRANSFER_GAMMA  f = pow(y, 1 / gamma)
+ * 1 <= gamma <= 4, |exposure| <= 16, both finite; anything else, or another kind: PC_E_INVALID.
+ * pc_gray_quantize_weights: the quantisation above of user weights rgb[3] into out->weight_r / _g / _b (float_table is left as it
+ * is), on the host -- the one quantiser the driver, polychase_core and the ctypes binding use; a weight that is negative or not
+ * finite, or a sum that is not positive: PC_E_INVALID, `out` untouched.
+ * pc_float_transfer_index: the table entry idx of each of n float values, computed on the host by the function the kernels
+ * compile (testing aid: the rule above is a float compare and a shift, the kernels test an integer range). */
+#define PC_TRANSFER_ENTRIES 20481
+#define PC_TRANSFER_SRGB 1
+#define PC_TRANSFER_GAMMA 2
+typedef struct pc_gray_conversion {
+    int32_t weight_r, weight_g, weight_b;
+    const uint8_t* float_table;
+} pc_gray_conversion;
+void pc_gray_default_conversion(pc_gray_conversion* c);
+int pc_context_set_gray_conversion(pc_context* ctx, const pc_gray_conversion* c);
+int pc_context_get_gray_conversion(const pc_context* ctx, pc_gray_conversion* c, uint8_t* table_out);
+int pc_float_transfer_table(int kind, double gamma, double exposure, uint8_t* out);
+int pc_gray_quantize_weights(const double* rgb, pc_gray_conversion* out);
+int pc_float_transfer_index(const float* values, int n, uint32_t* out);
 /* hipStream_t the context enqueues on (for callers that time with HIP events / torch streams). */
 void* pc_context_stream(pc_context* ctx);
 /* Timing of the context's kernels with HIP events on the stream each launch is enqueued on.  `class_mask` bit k

@@ -149,6 +149,12 @@ def main(argv=None) -> int:
                     help="brightness-normalised LK: end points that survive a gain or bias change between two frames (off by default)")
     ap.add_argument("--affine", action="store_true",
                     help="affine refinement: end points that survive the roll and zoom between the paired frames (off by default; not with --normalize)")
+    ap.add_argument("--channel-weights", type=float, nargs=3, default=None, metavar=("R", "G", "B"),
+                    help="gray conversion: the weights of the three channels in the plane that is detected and tracked (default: RGB2GRAY)")
+    ap.add_argument("--float-transfer", choices=["none", "srgb", "gamma"], default="none",
+                    help="transfer curve for float32 frames: scene-linear values through the sRGB curve or a power law (nothing for uint8 frames)")
+    ap.add_argument("--float-gamma", type=float, default=2.2, metavar="G", help="--float-transfer gamma: the exponent's inverse, 1..4")
+    ap.add_argument("--float-exposure", type=float, default=0.0, metavar="STOPS", help="gain in stops in front of the transfer curve, -16..16")
     ap.add_argument("--piece-frames", type=int, default=16, help="frames per piece of the record log handed to rank 0")
     ap.add_argument("--gpus", type=int, default=0, help="launch this many ranks (one per GPU) of this command")
     args = ap.parse_args(argv)
@@ -201,6 +207,10 @@ def main(argv=None) -> int:
     fopt.min_correlation = args.min_correlation
     fopt.normalize = args.normalize
     fopt.affine_refinement = args.affine
+    fopt.channel_weights = tuple(args.channel_weights) if args.channel_weights else None
+    fopt.float_transfer = args.float_transfer
+    fopt.float_transfer_gamma = args.float_gamma
+    fopt.float_exposure = args.float_exposure
     if int(os.environ.get("RANK", "0")) == 0 and os.path.exists(args.database):
         os.remove(args.database)
     if world > 1:

@@ -822,6 +822,106 @@ int pc_context_set_arithmetic(pc_context* c, int flags) {
 }
 int pc_context_get_arithmetic(const pc_context* c) { return c ? c->arith : -1; }
 
+// ---- gray conversion (include/polychase_hip.h has the rule) ----
+static_assert(pc::kTransferEntries == PC_TRANSFER_ENTRIES, "kernels.hpp holds the header's table size");
+
+void pc_gray_default_conversion(pc_gray_conversion* c) {
+    if (!c) return;
+    c->weight_r = 9798;
+    c->weight_g = 19235;
+    c->weight_b = 3735;
+    c->float_table = nullptr;
+}
+
+int pc_gray_quantize_weights(const double* rgb, pc_gray_conversion* out) {
+    if (!rgb || !out) return fail(PC_E_INVALID, "null argument");
+    for (int k = 0; k < 3; k++)
+        if (!(std::isfinite(rgb[k]) && rgb[k] >= 0.0)) return fail(PC_E_INVALID, "channel weight %d is %g: weights must be finite and >= 0", k, rgb[k]);
+    const double s = rgb[0] + rgb[1] + rgb[2];
+    if (!(s > 0.0 && std::isfinite(s))) return fail(PC_E_INVALID, "channel weights must have a positive, finite sum");
+    int32_t q[3], sum = 0;
+    int largest = 0;
+    for (int k = 0; k < 3; k++) {
+        q[k] = (int32_t)std::floor((rgb[k] / s) * 32768.0 + 0.5);
+        sum += q[k];
+        if (rgb[k] > rgb[largest]) largest = k;   // strictly: ties stay with the earlier channel, R before G before B
+    }
+    q[largest] += 32768 - sum;
+    out->weight_r = q[0];
+    out->weight_g = q[1];
+    out->weight_b = q[2];
+    return PC_OK;
+}
+
+int pc_float_transfer_index(const float* values, int n, uint32_t* out) {
+    if (n < 0 || (n > 0 && (!values || !out))) return fail(PC_E_INVALID, "bad argument");
+    for (int i = 0; i < n; i++) {
+        uint32_t bits;
+        memcpy(&bits, values + i, sizeof(bits));
+        out[i] = pc::transfer_index(bits);
+    }
+    return PC_OK;
+}
+
+int pc_context_set_gray_conversion(pc_context* c, const pc_gray_conversion* conv) {
+    pc_gray_conversion d;
+    pc_gray_default_conversion(&d);
+    if (!conv) conv = &d;
+    // first: the weights are refused whatever the handle
+    const int32_t w[3] = {conv->weight_r, conv->weight_g, conv->weight_b};
+    for (int k = 0; k < 3; k++)
+        if (w[k] < 0 || w[k] > 32768) return fail(PC_E_INVALID, "gray conversion: weight %d is %d, 0..32768 allowed", k, (int)w[k]);
+    if ((int64_t)w[0] + w[1] + w[2] != 32768) return fail(PC_E_INVALID, "gray conversion: the weights %d + %d + %d do not sum to 32768", (int)w[0], (int)w[1], (int)w[2]);
+    if (!c) return fail(PC_E_INVALID, "null context");
+    PC_HIP(hipSetDevice(c->device));
+    // a table other than the one already on the device (a run that repeats the last run's conversion uploads nothing)
+    if (conv->float_table && !(c->gray_table_host.size() == (size_t)PC_TRANSFER_ENTRIES &&
+                               memcmp(c->gray_table_host.data(), conv->float_table, (size_t)PC_TRANSFER_ENTRIES) == 0)) {
+        // into the spare buffer, which launches of the conversion before the one in force may still read; the buffers change
+        // places only once the copy is complete, so a failure on the way leaves the conversion in force untouched
+        if (c->prep_stream) PC_HIP(c->sync_side_streams());
+        PC_HIP(hipStreamSynchronize(c->stream));
+        DevBuf<uint8_t>& spare = c->gray_table_buf[c->gray_table_cur ^ 1];
+        PC_HIP(spare.ensure((size_t)PC_TRANSFER_ENTRIES, /*exact=*/true));
+        std::vector<uint8_t> host(conv->float_table, conv->float_table + PC_TRANSFER_ENTRIES);
+        PC_HIP(hipMemcpy(spare.p, host.data(), (size_t)PC_TRANSFER_ENTRIES, hipMemcpyHostToDevice));
+        c->gray_table_host.swap(host);
+        c->gray_table_cur ^= 1;
+    }
+    c->gray_table_on = conv->float_table != nullptr;
+    for (int k = 0; k < 3; k++) c->gray_w[k] = w[k];
+    return PC_OK;
+}
+
+int pc_context_get_gray_conversion(const pc_context* c, pc_gray_conversion* conv, uint8_t* table_out) {
+    if (!c || !conv) return fail(PC_E_INVALID, "null argument");
+    conv->weight_r = c->gray_w[0];
+    conv->weight_g = c->gray_w[1];
+    conv->weight_b = c->gray_w[2];
+    conv->float_table = c->gray_table_on ? table_out : nullptr;
+    if (c->gray_table_on && table_out) memcpy(table_out, c->gray_table_host.data(), (size_t)PC_TRANSFER_ENTRIES);
+    return PC_OK;
+}
+
+int pc_float_transfer_table(int kind, double gamma, double exposure, uint8_t* out) {
+    if (kind != PC_TRANSFER_SRGB && kind != PC_TRANSFER_GAMMA) return fail(PC_E_INVALID, "float transfer: unknown kind %d", kind);
+    if (!(gamma >= 1.0 && gamma <= 4.0)) return fail(PC_E_INVALID, "float transfer: gamma must be in [1, 4], got %g", gamma);   // a NaN fails
+    if (!(std::fabs(exposure) <= 16.0)) return fail(PC_E_INVALID, "float transfer: exposure must be in [-16, 16] stops, got %g", exposure);
+    if (!out) return fail(PC_E_INVALID, "null argument");
+    const double gain = std::exp2(exposure);
+    out[0] = 0;
+    for (int i = 1; i < PC_TRANSFER_ENTRIES; i++) {
+        const int oct = (i - 1) / 1024, m = (i - 1) % 1024;
+        const double scale = std::ldexp(1.0, oct - 16);                                // 2^e
+        const double y = (scale * (1.0 + m / 1024.0) + scale / 2048.0) * gain;         // the interval's midpoint, exposed
+        double f;
+        if (kind == PC_TRANSFER_SRGB) f = y <= 0.0031308 ? 12.92 * y : 1.055 * std::pow(y, 1.0 / 2.4) - 0.055;
+        else f = std::pow(y, 1.0 / gamma);
+        out[i] = (uint8_t)std::floor(255.0 * std::min(f, 1.0) + 0.5);
+    }
+    return PC_OK;
+}
+
 void pc_context_destroy(pc_context* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
@@ -846,6 +946,7 @@ void pc_context_destroy(pc_context* c) {
         c->detect = nullptr;
     }
     c->sort_temp.release();
+    for (auto& b : c->gray_table_buf) b.release();
     c->poly_host.release();
     c->poly_dev.release();
     c->lk_rec[0].release();
@@ -1171,7 +1272,14 @@ int pc_api::set_image(pc_context* ctx, pc_frame* f, const uint8_t* src, size_t r
     if (!unfused_pyramid() && level_fits_fused(f->levels[0], f->win)) {
         // level 0 in one pass: gray conversion fused with the padding, the uint16 plane and the Scharr plane
         pc::LevelSource in{};
-        in.kind = elem_size == 4 ? pc::SRC_RGBF32 : (channels == 3 ? pc::SRC_RGB8 : pc::SRC_GRAY8);
+        // the default gray conversion: the instances (and the launch arguments they read) of a context that never set one
+        const bool dw = ctx->gray_default_weights();
+        if (elem_size == 4) in.kind = ctx->gray_table_on ? pc::SRC_RGBF32_T : (dw ? pc::SRC_RGBF32 : pc::SRC_RGBF32_W);
+        else in.kind = channels == 3 ? (dw ? pc::SRC_RGB8 : pc::SRC_RGB8_W) : pc::SRC_GRAY8;
+        in.wr = (uint32_t)ctx->gray_w[0];
+        in.wg = (uint32_t)ctx->gray_w[1];
+        in.wb = (uint32_t)ctx->gray_w[2];
+        in.table = ctx->gray_table_dev();
         in.src = d_src;
         in.src_pitch = d_pitch;
         in.channels = channels;
@@ -1188,7 +1296,12 @@ int pc_api::set_image(pc_context* ctx, pc_frame* f, const uint8_t* src, size_t r
         if (clear) PC_HIP(hipMemsetAsync(clear, 0, (size_t)clear_words * sizeof(uint32_t), ctx->work));
         {
             ScopedTimer t(ctx, PC_K_GRAY);
-            if (elem_size == 4) pc::launch_rgbf32_to_gray(reinterpret_cast<const float*>(d_src), d_pitch, channels, f->levels[0], ctx->work);
+            const bool dw = ctx->gray_default_weights();
+            if (elem_size == 4 && (ctx->gray_table_on || !dw))
+                pc::launch_rgbf32_to_gray_converted(reinterpret_cast<const float*>(d_src), d_pitch, channels, f->levels[0], ctx->gray_w,
+                                                    ctx->gray_table_dev(), ctx->work);
+            else if (elem_size == 4) pc::launch_rgbf32_to_gray(reinterpret_cast<const float*>(d_src), d_pitch, channels, f->levels[0], ctx->work);
+            else if (channels == 3 && !dw) pc::launch_rgb2gray_weighted(d_src, d_pitch, f->levels[0], ctx->gray_w, ctx->work);
             else if (channels == 3) pc::launch_rgb2gray(d_src, d_pitch, f->levels[0], ctx->work);
             else pc::launch_copy_gray(d_src, d_pitch, f->levels[0], ctx->work);
         }

@@ -38,6 +38,17 @@ __host__ __device__ __forceinline__ int reflect101(int p, int len) {
     return p;
 }
 
+// Entry of the float transfer table (include/polychase_hip.h: pc_gray_conversion) for a channel value with fp32 pattern
+// `bits`: 0 unless v >= 2^-16 (NaN, negatives, zeros, denormals, tiny values), else 1 + the 20 octaves from 2^-16 on in 1024
+// steps each (exponent and the top 10 mantissa bits), capped at the last entry (v >= 16, +inf).  Integers only: the patterns of
+// [2^-16, +inf] are the unsigned range [0x37800000, 0x7f800000]; a negative or a NaN lies outside it.
+__host__ __device__ __forceinline__ uint32_t transfer_index(uint32_t bits) {
+    const uint32_t rel = bits - 0x37800000u;
+    if (rel > 0x7f800000u - 0x37800000u) return 0u;
+    const uint32_t i = (rel >> 13) + 1u;
+    return i < 20480u ? i : 20480u;
+}
+
 // Order-preserving map float -> uint32 (a < b  <=>  key(a) < key(b)), used for atomicMax and for the
 // candidate sort keys (value desc, then linear index desc == gftt.cc:7-12).
 __host__ __device__ __forceinline__ uint32_t float_to_ordered(float f) {

@@ -173,6 +173,14 @@ struct pc_context {
     hipStream_t work = nullptr;
     hipEvent_t prep_fence = nullptr;     // orders `stream` after everything queued on prep_stream so far
     bool prep_dirty = false;
+    // pc_context_set_gray_conversion: the channel weights and the float transfer table of the RGB frames put from now on
+    int gray_w[3] = {9798, 19235, 3735};
+    bool gray_table_on = false;
+    DevBuf<uint8_t> gray_table_buf[2];     // PC_TRANSFER_ENTRIES bytes each: the table in force and the one a setter uploads into
+    int gray_table_cur = 0;                // ... gray_table_buf[gray_table_cur] is the one in force (swapped once an upload is complete)
+    const uint8_t* gray_table_dev() const { return gray_table_on ? gray_table_buf[gray_table_cur].p : nullptr; }
+    std::vector<uint8_t> gray_table_host;  // the table in force (pc_context_get_gray_conversion)
+    bool gray_default_weights() const { return gray_w[0] == 9798 && gray_w[1] == 19235 && gray_w[2] == 3735; }
     // staging of host-provided frames
     DevBuf<uint8_t> staging;
     // the analyzer's host frames (PC_FRAME_PINNED_HOST): transfers on a stream of their own, two buffers in turn;

@@ -16,6 +16,13 @@ void set_helper_prio(int hi);
 void launch_rgb2gray(const uint8_t* rgb, size_t rgb_pitch, const Level& l0, hipStream_t s);
 // float32 RGB / RGBA (numpy `(x * 255).astype(uint8)` semantics) -> gray u8 in the level-0 interior
 void launch_rgbf32_to_gray(const float* rgb, size_t rgb_pitch, int channels, const Level& l0, hipStream_t s);
+// The same two under a gray conversion other than the default (include/polychase_hip.h: pc_context_set_gray_conversion):
+// Y = (wr R + wg G + wb B + 2^14) >> 15 with w[] = (wr, wg, wb), sum 2^15; for float frames `table` (device memory,
+// kTransferEntries bytes) maps a channel's fp32 bit pattern to its u8 value, null: the `(x * 255).astype(uint8)` rule.
+constexpr int kTransferEntries = 20481;   // == PC_TRANSFER_ENTRIES: black + 20 octaves x 1024 from 2^-16 on
+void launch_rgb2gray_weighted(const uint8_t* rgb, size_t rgb_pitch, const Level& l0, const int w[3], hipStream_t s);
+void launch_rgbf32_to_gray_converted(const float* rgb, size_t rgb_pitch, int channels, const Level& l0, const int w[3], const uint8_t* table,
+                                     hipStream_t s);
 // gray u8 (arbitrary pitch) -> level-0 interior
 void launch_copy_gray(const uint8_t* gray, size_t gray_pitch, const Level& l0, hipStream_t s);
 // K7: pyrDown 5x5 (src interior -> dst interior)
@@ -30,7 +37,9 @@ void launch_scharr(const Level& l, hipStream_t s);
 // ---- kernels_pyramid.hip ----
 // One fused kernel per pyramid level: the level's pixels (gray conversion of the frame for level 0, pyrDown of the
 // parent's padded plane otherwise) -> u8 plane + REFLECT_101 padding + uint16 plane + Scharr plane.
-enum LevelSourceKind { SRC_PYR = 0, SRC_RGB8 = 1, SRC_GRAY8 = 2, SRC_RGBF32 = 3 };
+// SRC_RGB8_W / SRC_RGBF32_W / SRC_RGBF32_T: the RGB sources under a gray conversion other than the default -- channel weights
+// LevelSource::wr, wg, wb; _T: float channels through LevelSource::table instead of the `(x * 255).astype(uint8)` rule
+enum LevelSourceKind { SRC_PYR = 0, SRC_RGB8 = 1, SRC_GRAY8 = 2, SRC_RGBF32 = 3, SRC_RGB8_W = 4, SRC_RGBF32_W = 5, SRC_RGBF32_T = 6 };
 struct LevelSource {
     int kind;
     const uint8_t* src;   // level 0: the frame on the device (u8 RGB, u8 gray or float32 RGB / RGBA)
@@ -40,6 +49,8 @@ struct LevelSource {
     Level parent;         // SRC_PYR
     uint32_t* clear;      // clear_words words zeroed by the launch (the detection's counters: saves the fill command
     int clear_words;      // in front of the detection chain), or null
+    uint32_t wr, wg, wb;  // SRC_*_W, SRC_RGBF32_T: the channel weights, each 0 .. 2^15, sum 2^15
+    const uint8_t* table; // SRC_RGBF32_T: the float transfer table (device memory, kTransferEntries bytes)
 };
 // requires out.w > win + 1 and out.h > win + 1 (single reflection in the padding); smaller levels take the unfused kernels
 void launch_level(const LevelSource& in, const Level& out, int win, hipStream_t s);

@@ -83,6 +83,53 @@ void launch_rgbf32_to_gray(const float* rgb, size_t rgb_pitch, int channels, con
     hipLaunchKernelGGL(rgbf32_to_gray_kernel, grid, dim3(256), 0, s, rgb, rgb_pitch, channels, l0.img, l0.pitch, l0.w, l0.h);
 }
 
+// The same two under a gray conversion other than the default (pc_context_set_gray_conversion), one pixel per lane:
+// Y = (wr R + wg G + wb B + 2^14) >> 15; float channels through the transfer table (a pure look-up) or, without one, through
+// float_channel_to_u8.
+__global__ __launch_bounds__(256) void rgb2gray_weighted_kernel(const uint8_t* __restrict__ rgb, size_t rgb_pitch, uint8_t* __restrict__ dst,
+                                                                int dst_pitch, int w, int h, uint32_t wr, uint32_t wg, uint32_t wb) {
+    const int x = blockIdx.x * blockDim.x + threadIdx.x;
+    const int y = blockIdx.y;
+    if (x >= w) return;
+    const uint8_t* s = rgb + (size_t)y * rgb_pitch + 3 * (size_t)x;
+    dst[(size_t)y * dst_pitch + x] = (uint8_t)((s[0] * wr + s[1] * wg + s[2] * wb + (1u << 14)) >> 15);
+}
+
+void launch_rgb2gray_weighted(const uint8_t* rgb, size_t rgb_pitch, const Level& l0, const int w[3], hipStream_t s) {
+    dim3 grid((l0.w + 255) / 256, l0.h);
+    hipLaunchKernelGGL(rgb2gray_weighted_kernel, grid, dim3(256), 0, s, rgb, rgb_pitch, l0.img, l0.pitch, l0.w, l0.h, (uint32_t)w[0],
+                       (uint32_t)w[1], (uint32_t)w[2]);
+}
+
+template <bool TABLE>
+__global__ __launch_bounds__(256) void rgbf32_to_gray_converted_kernel(const float* __restrict__ src, size_t src_pitch, int channels,
+                                                                       uint8_t* __restrict__ dst, int dst_pitch, int w, int h, uint32_t wr,
+                                                                       uint32_t wg, uint32_t wb, const uint8_t* __restrict__ table) {
+    const int x = blockIdx.x * blockDim.x + threadIdx.x;
+    const int y = blockIdx.y;
+    if (x >= w) return;
+    const float* p = reinterpret_cast<const float*>(reinterpret_cast<const uint8_t*>(src) + (size_t)y * src_pitch) +
+                     (size_t)x * channels;
+    uint32_t c[3];
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        if constexpr (TABLE) c[k] = table[transfer_index(reinterpret_cast<const uint32_t*>(p)[k])];
+        else c[k] = float_channel_to_u8(p[k]);
+    }
+    dst[(size_t)y * dst_pitch + x] = (uint8_t)((c[0] * wr + c[1] * wg + c[2] * wb + (1u << 14)) >> 15);
+}
+
+void launch_rgbf32_to_gray_converted(const float* rgb, size_t rgb_pitch, int channels, const Level& l0, const int w[3], const uint8_t* table,
+                                     hipStream_t s) {
+    dim3 grid((l0.w + 255) / 256, l0.h);
+    if (table)
+        hipLaunchKernelGGL(rgbf32_to_gray_converted_kernel<true>, grid, dim3(256), 0, s, rgb, rgb_pitch, channels, l0.img, l0.pitch, l0.w, l0.h,
+                           (uint32_t)w[0], (uint32_t)w[1], (uint32_t)w[2], table);
+    else
+        hipLaunchKernelGGL(rgbf32_to_gray_converted_kernel<false>, grid, dim3(256), 0, s, rgb, rgb_pitch, channels, l0.img, l0.pitch, l0.w, l0.h,
+                           (uint32_t)w[0], (uint32_t)w[1], (uint32_t)w[2], table);
+}
+
 __global__ __launch_bounds__(256) void copy_gray_kernel(const uint8_t* __restrict__ src, size_t src_pitch,
                                                         uint8_t* __restrict__ dst, int dst_pitch, int w, int h) {
     const int x = blockIdx.x * blockDim.x + threadIdx.x;

@@ -2,7 +2,8 @@
 //
 // Replaces, per level l of cv::buildOpticalFlowPyramid (reference cpp/opticalflow.cc:180-187) and the
 // cv::cvtColor(COLOR_RGB2GRAY) in front of it (cpp/opticalflow.cc:259,:298):
-//     level 0:  RGB / gray / float RGB(A) frame  -> gray tile                      (RGB2Gray, 15-bit coefficients)
+//     level 0:  RGB / gray / float RGB(A) frame  -> gray tile                      (RGB2Gray, 15-bit coefficients; or the
+//               context's gray conversion: channel weights, a transfer table for float channels)
 //     level l:  parent level's padded plane      -> pyrDown tile (5x5, (sum + 128) >> 8, REFLECT_101)
 //   and then, from that tile in LDS (64 x 16 pixels + a 1-px halo), in the same kernel:
 //     the u8 image plane, its REFLECT_101 padding of `win` pixels (copyMakeBorder), the uint16 (pixel << 7) plane
@@ -40,17 +41,31 @@ __device__ __forceinline__ uint32_t float_channel_to_u8(float v) {
     return (uint32_t)i & 0xffu;
 }
 
+// the gray conversions other than the default (pc_context_set_gray_conversion): channel weights from the launch's arguments
+// and, for SRC_RGBF32_T, float channels through the transfer table -- a pure look-up in global memory (20 KiB that every
+// workgroup of the launch shares: it stays in the L1 / L2; DESIGN.md section 4, "Grey conversion")
+template <int SRC>
+__device__ __forceinline__ uint32_t gray_src(const LevelSource& in, uint32_t r, uint32_t g, uint32_t b) {
+    if constexpr (SRC == SRC_RGB8_W || SRC == SRC_RGBF32_W || SRC == SRC_RGBF32_T) return (r * in.wr + g * in.wg + b * in.wb + (1u << 14)) >> 15;
+    else return gray_of(r, g, b);
+}
+template <int SRC>
+__device__ __forceinline__ uint32_t float_channel(const LevelSource& in, const float* s) {
+    if constexpr (SRC == SRC_RGBF32_T) return in.table[transfer_index(*reinterpret_cast<const uint32_t*>(s))];
+    else return float_channel_to_u8(*s);
+}
+
 template <int SRC>
 __device__ __forceinline__ uint32_t source_gray(const LevelSource& in, int x, int y) {
     const uint8_t* row = in.src + (size_t)y * in.src_pitch;
-    if (SRC == SRC_RGB8) {
+    if (SRC == SRC_RGB8 || SRC == SRC_RGB8_W) {
         const uint8_t* s = row + 3 * (size_t)x;
-        return gray_of(s[0], s[1], s[2]);
+        return gray_src<SRC>(in, s[0], s[1], s[2]);
     } else if (SRC == SRC_GRAY8) {
         return row[x];
     } else {
         const float* s = reinterpret_cast<const float*>(row) + (size_t)x * in.channels;
-        return gray_of(float_channel_to_u8(s[0]), float_channel_to_u8(s[1]), float_channel_to_u8(s[2]));
+        return gray_src<SRC>(in, float_channel<SRC>(in, s), float_channel<SRC>(in, s + 1), float_channel<SRC>(in, s + 2));
     }
 }
 
@@ -128,13 +143,13 @@ __global__ __launch_bounds__(256) void level_kernel(const LevelSource in, const 
             uint32_t px[4] = {0, 0, 0, 0};
             if (in.aligned && x + 3 < w) {
                 const uint8_t* row = in.src + (size_t)y * in.src_pitch;
-                if (SRC == SRC_RGB8) {
+                if (SRC == SRC_RGB8 || SRC == SRC_RGB8_W) {
                     const uint32_t* s = reinterpret_cast<const uint32_t*>(row) + 3 * (x >> 2);
                     const uint32_t d0 = s[0], d1 = s[1], d2 = s[2];
-                    px[0] = gray_of(d0 & 0xff, (d0 >> 8) & 0xff, (d0 >> 16) & 0xff);
-                    px[1] = gray_of(d0 >> 24, d1 & 0xff, (d1 >> 8) & 0xff);
-                    px[2] = gray_of((d1 >> 16) & 0xff, d1 >> 24, d2 & 0xff);
-                    px[3] = gray_of((d2 >> 8) & 0xff, (d2 >> 16) & 0xff, d2 >> 24);
+                    px[0] = gray_src<SRC>(in, d0 & 0xff, (d0 >> 8) & 0xff, (d0 >> 16) & 0xff);
+                    px[1] = gray_src<SRC>(in, d0 >> 24, d1 & 0xff, (d1 >> 8) & 0xff);
+                    px[2] = gray_src<SRC>(in, (d1 >> 16) & 0xff, d1 >> 24, d2 & 0xff);
+                    px[3] = gray_src<SRC>(in, (d2 >> 8) & 0xff, (d2 >> 16) & 0xff, d2 >> 24);
                 } else if (SRC == SRC_GRAY8) {
                     const uint32_t d = *reinterpret_cast<const uint32_t*>(row + x);
                     px[0] = d & 0xff; px[1] = (d >> 8) & 0xff; px[2] = (d >> 16) & 0xff; px[3] = d >> 24;
@@ -256,6 +271,9 @@ void launch_level(const LevelSource& in, const Level& out, int win, hipStream_t 
         case SRC_PYR: hipLaunchKernelGGL(level_kernel<SRC_PYR>, grid, dim3(256), 0, s, in, out, win, helper_prio_arg()); break;
         case SRC_RGB8: hipLaunchKernelGGL(level_kernel<SRC_RGB8>, grid, dim3(256), 0, s, in, out, win, helper_prio_arg()); break;
         case SRC_GRAY8: hipLaunchKernelGGL(level_kernel<SRC_GRAY8>, grid, dim3(256), 0, s, in, out, win, helper_prio_arg()); break;
+        case SRC_RGB8_W: hipLaunchKernelGGL(level_kernel<SRC_RGB8_W>, grid, dim3(256), 0, s, in, out, win, helper_prio_arg()); break;
+        case SRC_RGBF32_W: hipLaunchKernelGGL(level_kernel<SRC_RGBF32_W>, grid, dim3(256), 0, s, in, out, win, helper_prio_arg()); break;
+        case SRC_RGBF32_T: hipLaunchKernelGGL(level_kernel<SRC_RGBF32_T>, grid, dim3(256), 0, s, in, out, win, helper_prio_arg()); break;
         default: hipLaunchKernelGGL(level_kernel<SRC_RGBF32>, grid, dim3(256), 0, s, in, out, win, helper_prio_arg()); break;
     }
 }

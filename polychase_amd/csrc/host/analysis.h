@@ -6,6 +6,8 @@
 // OpticalFlowOptions and VideoInfo <- cpp/opticalflow.h:20-33.  cv::Mat is replaced by FrameView.
 #pragma once
 
+#include <array>
+#include <cmath>
 #include <cstdint>
 #include <functional>
 #include <memory>
@@ -55,6 +57,15 @@ struct OpticalFlowOptions {
     // row is refined at level 0 under a 6-parameter warp of the window, so that it survives the roll and zoom between frames up
     // to 8 apart (Blender's tracker calls it the affine motion model).  Not together with normalize.
     bool affine_refinement = false;
+    // not in the reference: gray conversion (include/polychase_hip.h: pc_gray_conversion).  channel_weights: nothing = the
+    // reference's RGB2GRAY; (r, g, b), finite, >= 0, not all zero = the weights of the three channels in the gray plane that is
+    // detected and tracked (Blender's tracker has R / G / B switches), for u8 and float frames.  float_transfer: "none" = float
+    // frames through the addon's `(x * 255).astype(uint8)`; "srgb" / "gamma" = scene-linear float frames through the sRGB curve or
+    // pow(y, 1 / float_transfer_gamma), 1 <= gamma <= 4, after float_exposure stops (|v| <= 16) of gain; nothing for u8 frames.
+    std::optional<std::array<double, 3>> channel_weights;
+    std::string float_transfer = "none";
+    double float_transfer_gamma = 2.2;
+    double float_exposure = 0.0;
 };
 // std::invalid_argument for what no run accepts; every entry point calls it before it asks for a frame
 inline void CheckOpticalFlowOptions(const OpticalFlowOptions& o) {
@@ -64,6 +75,20 @@ inline void CheckOpticalFlowOptions(const OpticalFlowOptions& o) {
         throw std::invalid_argument("min_correlation must be in [0, 1] (0 = off), got " + std::to_string(o.min_correlation));
     if (o.affine_refinement && o.normalize)
         throw std::invalid_argument("affine_refinement assumes brightness constancy: it cannot be combined with normalize");
+    if (o.channel_weights) {
+        const auto& w = *o.channel_weights;
+        for (double c : w)
+            if (!(std::isfinite(c) && c >= 0.0))
+                throw std::invalid_argument("channel_weights must be finite and >= 0, got " + std::to_string(c));
+        const double s = w[0] + w[1] + w[2];
+        if (!(s > 0.0 && std::isfinite(s))) throw std::invalid_argument("channel_weights must have a positive, finite sum");
+    }
+    if (o.float_transfer != "none" && o.float_transfer != "srgb" && o.float_transfer != "gamma")
+        throw std::invalid_argument("float_transfer must be \"none\", \"srgb\" or \"gamma\", got \"" + o.float_transfer + "\"");
+    if (!(o.float_transfer_gamma >= 1.0 && o.float_transfer_gamma <= 4.0))   // a NaN fails
+        throw std::invalid_argument("float_transfer_gamma must be in [1, 4], got " + std::to_string(o.float_transfer_gamma));
+    if (!(std::fabs(o.float_exposure) <= 16.0))
+        throw std::invalid_argument("float_exposure must be in [-16, 16] stops, got " + std::to_string(o.float_exposure));
 }
 
 // The clip: frames first_frame .. first_frame + num_frames - 1, all width x height.

@@ -437,6 +437,22 @@ static void RunAnalysis(const VideoInfo& video_info, FrameAccessorFunction frame
     if (pc_analyzer_set_normalize(eng.an, flow_options.normalize ? 1 : 0) != PC_OK) ThrowHip("pc_analyzer_set_normalize");
     // ... the affine refinement (after the normalisation it excludes: a parked engine may hold either from its last run) ...
     if (pc_analyzer_set_affine_refinement(eng.an, flow_options.affine_refinement ? 1 : 0) != PC_OK) ThrowHip("pc_analyzer_set_affine_refinement");
+    // ... the gray conversion, the default included (a per-run call: it may wait for the engine's idle streams) ...
+    {
+        pc_gray_conversion conv;
+        pc_gray_default_conversion(&conv);
+        if (flow_options.channel_weights && pc_gray_quantize_weights(flow_options.channel_weights->data(), &conv) != PC_OK)
+            ThrowHip("pc_gray_quantize_weights");
+        std::vector<uint8_t> table;
+        if (flow_options.float_transfer != "none") {
+            table.resize(PC_TRANSFER_ENTRIES);
+            if (pc_float_transfer_table(flow_options.float_transfer == "srgb" ? PC_TRANSFER_SRGB : PC_TRANSFER_GAMMA, flow_options.float_transfer_gamma,
+                                        flow_options.float_exposure, table.data()) != PC_OK)
+                ThrowHip("pc_float_transfer_table");
+            conv.float_table = table.data();
+        }
+        if (pc_context_set_gray_conversion(eng.ctx, &conv) != PC_OK) ThrowHip("pc_context_set_gray_conversion");
+    }
     // ... the target-side margin, off without a mask to choke ...
     const int target_margin = detection_mask.empty() ? -1 : flow_options.target_mask_margin;
     if (pc_analyzer_set_target_mask_margin(eng.an, target_margin) != PC_OK) ThrowHip("pc_analyzer_set_target_mask_margin");

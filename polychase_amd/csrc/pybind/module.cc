@@ -481,7 +481,12 @@ PYBIND11_MODULE(polychase_core, m) {
         .def_readwrite("target_mask_margin", &OpticalFlowOptions::target_mask_margin)   // not in the reference; -1 = off, 0..31
         .def_readwrite("min_correlation", &OpticalFlowOptions::min_correlation)   // not in the reference; 0 = off, 0..1
         .def_readwrite("normalize", &OpticalFlowOptions::normalize)   // not in the reference; brightness-normalised LK, off by default
-        .def_readwrite("affine_refinement", &OpticalFlowOptions::affine_refinement);   // not in the reference; off by default, not with normalize
+        .def_readwrite("affine_refinement", &OpticalFlowOptions::affine_refinement)   // not in the reference; off by default, not with normalize
+        // not in the reference: the gray conversion (include/polychase_hip.h: pc_gray_conversion)
+        .def_readwrite("channel_weights", &OpticalFlowOptions::channel_weights)           // None or three floats (r, g, b)
+        .def_readwrite("float_transfer", &OpticalFlowOptions::float_transfer)             // "none", "srgb" or "gamma"
+        .def_readwrite("float_transfer_gamma", &OpticalFlowOptions::float_transfer_gamma)
+        .def_readwrite("float_exposure", &OpticalFlowOptions::float_exposure);            // stops
 
     py::class_<OpticalFlowProgress>(m, "OpticalFlowProgress")
         .def_readonly("progress", &OpticalFlowProgress::progress)
@@ -568,6 +573,23 @@ PYBIND11_MODULE(polychase_core, m) {
         ReleaseCachedEngine();
         ReleaseTrackerCaches();
     });
+    // not in the reference: the built-in float transfer table of OpticalFlowOptions.float_transfer (include/polychase_hip.h:
+    // pc_float_transfer_table), uint8 [PC_TRANSFER_ENTRIES]; computed on the host
+    m.def("float_transfer_table", [](const std::string& kind, double gamma, double exposure) {
+        if (kind != "srgb" && kind != "gamma") throw std::invalid_argument("float transfer kind must be \"srgb\" or \"gamma\", got \"" + kind + "\"");
+        py::array_t<uint8_t> out(PC_TRANSFER_ENTRIES);
+        if (pc_float_transfer_table(kind == "srgb" ? PC_TRANSFER_SRGB : PC_TRANSFER_GAMMA, gamma, exposure, out.mutable_data()) != PC_OK)
+            throw std::invalid_argument(pc_last_error());
+        return out;
+    }, py::arg("kind"), py::arg("gamma") = 2.2, py::arg("exposure") = 0.0);
+    // not in the reference: what OpticalFlowOptions.channel_weights becomes -- the three 15-bit integers of pc_gray_conversion
+    // (include/polychase_hip.h: pc_gray_quantize_weights, the quantiser the driver calls)
+    m.def("quantize_channel_weights", [](const std::array<double, 3>& weights) {
+        pc_gray_conversion c;
+        pc_gray_default_conversion(&c);
+        if (pc_gray_quantize_weights(weights.data(), &c) != PC_OK) throw std::invalid_argument(pc_last_error());
+        return py::make_tuple(c.weight_r, c.weight_g, c.weight_b);
+    }, py::arg("weights"));
     m.def("generate_optical_flow_shard", &GenerateOpticalFlowShardPy, py::arg("video_info"), py::arg("frame_accessor_function"),
           py::arg("callback"), py::arg("database_path"), py::arg("shard_begin"), py::arg("shard_end"), py::arg("device_log") = 0,
           py::arg("capacity_bytes") = 0, py::arg("log_buffers") = 1, py::arg("piece_frames") = 0, py::arg("on_piece") = py::none(),

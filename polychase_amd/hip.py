@@ -24,6 +24,8 @@ SYMBOLS = [
     "pc_gftt_default_options", "pc_flow_default_options", "pc_last_error", "pc_version",
     "pc_context_create", "pc_context_destroy", "pc_context_synchronize", "pc_context_stream",
     "pc_runtime_init", "pc_context_set_arithmetic", "pc_context_get_arithmetic", "pc_context_download",
+    "pc_gray_default_conversion", "pc_context_set_gray_conversion", "pc_context_get_gray_conversion", "pc_float_transfer_table",
+    "pc_gray_quantize_weights", "pc_float_transfer_index",
     "pc_context_enable_timing", "pc_context_get_timing", "pc_context_get_busy_time", "pc_context_reset_timing",
     "pc_debug_lk_profile", "pc_debug_lk_x86_stats", "pc_debug_llt9",
     "pc_frame_create", "pc_frame_destroy", "pc_frame_set_rgb", "pc_frame_set_rgb_f32", "pc_frame_set_gray",
@@ -71,6 +73,16 @@ class FlowOptions(C.Structure):
     """OpticalFlowOptions (reference cpp/opticalflow.h:27-33)."""
     _fields_ = [("window_size", C.c_int), ("max_level", C.c_int), ("term_max_iters", C.c_int),
                 ("term_epsilon", C.c_double), ("min_eigen_threshold", C.c_double)]
+
+
+class GrayConversion(C.Structure):
+    """pc_gray_conversion (include/polychase_hip.h)."""
+    _fields_ = [("weight_r", C.c_int32), ("weight_g", C.c_int32), ("weight_b", C.c_int32), ("float_table", C.c_void_p)]
+
+
+TRANSFER_ENTRIES = 20481                      # PC_TRANSFER_ENTRIES
+TRANSFER_KINDS = {"srgb": 1, "gamma": 2}      # PC_TRANSFER_SRGB, PC_TRANSFER_GAMMA
+DEFAULT_GRAY_WEIGHTS = (9798, 19235, 3735)
 
 
 class FrameResult(C.Structure):
@@ -122,6 +134,13 @@ def load():
     L.pc_context_download.argtypes = [vp, vp, vp, C.c_size_t]
     L.pc_context_set_arithmetic.argtypes = [vp, C.c_int]
     L.pc_context_get_arithmetic.argtypes = [vp]
+    L.pc_gray_default_conversion.argtypes = [C.POINTER(GrayConversion)]
+    L.pc_gray_default_conversion.restype = None
+    L.pc_context_set_gray_conversion.argtypes = [vp, C.POINTER(GrayConversion)]
+    L.pc_context_get_gray_conversion.argtypes = [vp, C.POINTER(GrayConversion), vp]
+    L.pc_float_transfer_table.argtypes = [C.c_int, C.c_double, C.c_double, vp]
+    L.pc_gray_quantize_weights.argtypes = [C.POINTER(C.c_double), C.POINTER(GrayConversion)]
+    L.pc_float_transfer_index.argtypes = [vp, C.c_int, vp]
     L.pc_context_stream.restype = vp
     L.pc_context_enable_timing.argtypes = [vp, C.c_int]
     L.pc_context_get_timing.argtypes = [vp, C.c_int, ip, C.POINTER(C.c_double)]
@@ -223,6 +242,35 @@ def gftt_options(**kw) -> GfttOptions:
     return o
 
 
+def quantize_channel_weights(weights) -> tuple:
+    """user weights (r, g, b) -> the three 15-bit integers of pc_gray_conversion (pc_gray_quantize_weights: the library's own
+    quantiser, the one the analysis driver calls); ValueError for what it refuses"""
+    w = [float(c) for c in weights]
+    if len(w) != 3:
+        raise ValueError(f"channel weights must be three values, got {tuple(weights)}")
+    c = GrayConversion()
+    if load().pc_gray_quantize_weights((C.c_double * 3)(*w), C.byref(c)) != 0:
+        raise ValueError(load().pc_last_error().decode())
+    return (c.weight_r, c.weight_g, c.weight_b)
+
+
+def transfer_index(values) -> np.ndarray:
+    """table entries of float32 values, by the function the kernels compile, on the host (pc_float_transfer_index)"""
+    v = np.ascontiguousarray(values, dtype=np.float32).ravel()
+    out = np.empty(len(v), np.uint32)
+    _check(load().pc_float_transfer_index(v.ctypes.data, len(v), out.ctypes.data))
+    return out.reshape(np.shape(values))
+
+
+def float_transfer_table(kind: str, gamma: float = 2.2, exposure: float = 0.0) -> np.ndarray:
+    """the built-in float transfer table (pc_float_transfer_table): kind "srgb" or "gamma" -> uint8 [TRANSFER_ENTRIES]"""
+    if kind not in TRANSFER_KINDS:
+        raise ValueError(f"float transfer kind must be one of {sorted(TRANSFER_KINDS)}, got {kind!r}")
+    out = np.empty(TRANSFER_ENTRIES, np.uint8)
+    _check(load().pc_float_transfer_table(TRANSFER_KINDS[kind], float(gamma), float(exposure), out.ctypes.data))
+    return out
+
+
 def flow_options(**kw) -> FlowOptions:
     o = FlowOptions()
     load().pc_flow_default_options(C.byref(o))
@@ -254,6 +302,28 @@ class Context:
     @property
     def arithmetic(self) -> int:
         return load().pc_context_get_arithmetic(self._h)
+
+    def set_gray_conversion(self, weights=None, float_table=None):
+        """Gray conversion of the RGB frames put from now on (pc_context_set_gray_conversion).  weights: None = the default's
+        (9798, 19235, 3735), else three integers 0..32768 with sum 32768 (quantize_channel_weights makes them from user weights);
+        float_table: None = the `(x * 255).astype(uint8)` rule, else uint8 [TRANSFER_ENTRIES].  Both None: the default."""
+        c = GrayConversion()
+        load().pc_gray_default_conversion(C.byref(c))
+        if weights is not None:
+            c.weight_r, c.weight_g, c.weight_b = (int(v) for v in weights)
+        if float_table is not None:
+            float_table = np.ascontiguousarray(float_table)
+            if float_table.dtype != np.uint8 or float_table.shape != (TRANSFER_ENTRIES,):
+                raise ValueError(f"float_table must be uint8 [{TRANSFER_ENTRIES}], got {float_table.dtype} {float_table.shape}")
+            c.float_table = float_table.ctypes.data
+        _check(load().pc_context_set_gray_conversion(self._h, C.byref(c)))
+
+    def gray_conversion(self):
+        """-> ((weight_r, weight_g, weight_b), float table uint8 [TRANSFER_ENTRIES] or None) in force (pc_context_get_gray_conversion)"""
+        c = GrayConversion()
+        table = np.empty(TRANSFER_ENTRIES, np.uint8)
+        _check(load().pc_context_get_gray_conversion(self._h, C.byref(c), table.ctypes.data))
+        return (c.weight_r, c.weight_g, c.weight_b), (table if c.float_table else None)
 
     def synchronize(self):
         _check(load().pc_context_synchronize(self._h))

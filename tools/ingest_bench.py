@@ -1,12 +1,18 @@
 #!/usr/bin/env python3
-"""Frame ingestion through polychase_core: host frames as uint8 RGB and as Blender's float32 RGBA,
-no database.  `POLYCHASE_COPY_THREADS=1` gives the single-threaded copy for comparison.
+"""Frame ingestion through polychase_core: host frames as uint8 RGB, as Blender's float32 RGBA and as
+scene-linear float32 RGB (the uint8 clip through the sRGB EOTF: what an EXR plate holds), no database.
+`POLYCHASE_COPY_THREADS=1` gives the single-threaded copy for comparison.
 
-    python tools/ingest_bench.py [--config c2] [--frames 120]
+    python tools/ingest_bench.py [--config c2] [--frames 120] [--clips uint8_rgb,float32_rgba,float32_rgb_linear]
+                                 [--channel-weights R G B] [--float-transfer none|srgb|gamma] [--float-gamma G] [--float-exposure STOPS]
+
+The last four are OpticalFlowOptions' gray conversion (channel_weights, float_transfer, float_transfer_gamma, float_exposure) of
+every run; --repeat N times every clip N times and reports the median with min and max beside it.
 """
 import argparse
 import json
 import os
+import statistics
 import sys
 import time
 
@@ -14,36 +20,66 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "polychase_amd", "core"))
 
+CLIPS = ("uint8_rgb", "float32_rgba", "float32_rgb_linear")
+
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", default="c2")
     ap.add_argument("--frames", type=int, default=120)
+    ap.add_argument("--clips", default="uint8_rgb,float32_rgba")
+    ap.add_argument("--repeat", type=int, default=1)
+    ap.add_argument("--channel-weights", type=float, nargs=3, default=None, metavar=("R", "G", "B"))
+    ap.add_argument("--float-transfer", choices=["none", "srgb", "gamma"], default="none")
+    ap.add_argument("--float-gamma", type=float, default=2.2)
+    ap.add_argument("--float-exposure", type=float, default=0.0)
     a = ap.parse_args()
     import numpy as np
     import torch  # noqa: F401
     import polychase_core as core
     from polychase_amd import synth
 
+    names = [c for c in a.clips.split(",") if c]
+    assert set(names) <= set(CLIPS), names
     w, h, ml = {"c2": (1920, 1080, 3), "c3": (3840, 2160, 4)}[a.config]
     clip = synth.NoiseClip(w, h, 24)
     u8 = [clip.frame(t) for t in range(24)]
-    f32 = [np.concatenate([x.astype(np.float32) / 255.0, np.ones((h, w, 1), np.float32)], axis=2) for x in u8[:12]]
+    clips = {"uint8_rgb": u8}
+    if "float32_rgba" in names:
+        clips["float32_rgba"] = [np.concatenate([x.astype(np.float32) / 255.0, np.ones((h, w, 1), np.float32)], axis=2) for x in u8[:12]]
+    if "float32_rgb_linear" in names:
+        c = np.arange(256) / 255.0
+        eotf = np.where(c <= 0.04045, c / 12.92, ((c + 0.055) / 1.055) ** 2.4).astype(np.float32)
+        clips["float32_rgb_linear"] = [np.ascontiguousarray(eotf[x]) for x in u8[:12]]
     fo = core.OpticalFlowOptions()
     fo.max_level = ml
+    fo.channel_weights = tuple(a.channel_weights) if a.channel_weights else None
+    fo.float_transfer = a.float_transfer
+    fo.float_transfer_gamma = a.float_gamma
+    fo.float_exposure = a.float_exposure
     vi = core.VideoInfo(w, h, 1, a.frames)
     out = {"config": a.config, "frames": a.frames, "copy_threads": os.environ.get("POLYCHASE_COPY_THREADS", "default")}
-    for name, frames in (("uint8_rgb", u8), ("float32_rgba", f32)):
+    if a.channel_weights:
+        out["channel_weights"] = a.channel_weights
+    if a.float_transfer != "none":
+        out["float_transfer"] = {"kind": a.float_transfer, "gamma": a.float_gamma, "exposure": a.float_exposure}
+    for name in names:
+        frames = clips[name]
         n = len(frames)
 
         def acc(fid):
             t = (fid - 1) % (2 * n - 2)
             return frames[t if t < n else 2 * n - 2 - t]
         core.generate_optical_flow_database(core.VideoInfo(w, h, 1, 20), acc, None, "", core.GFTTOptions(), fo)   # warm-up
-        t0 = time.perf_counter()
-        core.generate_optical_flow_database(vi, acc, None, "", core.GFTTOptions(), fo)
-        dt = time.perf_counter() - t0
-        out[name] = {"fps": a.frames / dt, "host_GBps": a.frames * frames[0].nbytes / dt / 1e9}
+        fps = []
+        for _ in range(max(1, a.repeat)):
+            t0 = time.perf_counter()
+            core.generate_optical_flow_database(vi, acc, None, "", core.GFTTOptions(), fo)
+            fps.append(a.frames / (time.perf_counter() - t0))
+        med = statistics.median(fps)
+        out[name] = {"fps": med, "host_GBps": med * frames[0].nbytes / 1e9}
+        if a.repeat > 1:
+            out[name].update(fps_min=min(fps), fps_max=max(fps), runs=len(fps))
     print(json.dumps(out))
 
 

@@ -3,6 +3,7 @@
 //     polychase_multi_gpu --gpus N --database clip.db [--width 1920 --height 1080 --frames 64 --max-level 3]
 //                         [--transport rccl|tcp] [--share-gpu] [--port 29611] [--piece-frames 16] [--frames-file clip.rgb]
 //                         [--fb-threshold PX] [--min-correlation V] [--normalize] [--affine]
+//                         [--channel-weights R G B] [--float-transfer none|srgb|gamma] [--float-gamma G] [--float-exposure STOPS]
 //
 // forks N ranks BEFORE the process touches HIP (one process per GPU; --share-gpu puts every rank on GPU 0, which RCCL
 // refuses: use it with --transport tcp, the testing aid of csrc/host/multi_gpu.h), each rank calls
@@ -78,6 +79,24 @@ int RunRank(int rank, int world, int argc, char** argv) {
     fo.min_correlation = std::atof(Arg(argc, argv, "--min-correlation", "0"));           // minimum correlation, 0 = off
     fo.normalize = Flag(argc, argv, "--normalize");                                       // brightness-normalised LK, off by default
     fo.affine_refinement = Flag(argc, argv, "--affine");                                  // affine refinement, off by default
+    // the gray conversion: the weights of the three channels; the transfer curve of float frames travels with the options (the
+    // frames of this tool are uint8, for which it does nothing)
+    for (int i = 1; i < argc; i++)
+        if (std::strcmp(argv[i], "--channel-weights") == 0) {
+            std::array<double, 3> w{};
+            for (int k = 0; k < 3; k++) {
+                char* end = nullptr;
+                if (i + 1 + k < argc) w[k] = std::strtod(argv[i + 1 + k], &end);
+                if (!end || end == argv[i + 1 + k] || *end != '\0') {
+                    std::fprintf(stderr, "--channel-weights needs three numbers R G B\n");
+                    return 2;
+                }
+            }
+            fo.channel_weights = w;
+        }
+    fo.float_transfer = Arg(argc, argv, "--float-transfer", "none");
+    fo.float_transfer_gamma = std::atof(Arg(argc, argv, "--float-gamma", "2.2"));
+    fo.float_exposure = std::atof(Arg(argc, argv, "--float-exposure", "0"));
     const size_t frame_bytes = static_cast<size_t>(w) * h * 3;
     std::ifstream in;
     if (!file.empty()) {
@@ -129,7 +148,8 @@ int main(int argc, char** argv) {
     const int world = std::atoi(Arg(argc, argv, "--gpus", "1"));
     if (world < 1 || std::string(Arg(argc, argv, "--database", "")).empty()) {
         std::fprintf(stderr, "usage: %s --gpus N --database clip.db [--width W --height H --frames n --max-level L --transport rccl|tcp "
-                             "--share-gpu --port P --piece-frames k --frames-file raw.rgb --fb-threshold px --min-correlation v --normalize --affine]\n", argv[0]);
+                             "--share-gpu --port P --piece-frames k --frames-file raw.rgb --fb-threshold px --min-correlation v --normalize --affine "
+                             "--channel-weights r g b --float-transfer none|srgb|gamma --float-gamma g --float-exposure stops]\n", argv[0]);
         return 2;
     }
     if (const char* r = std::getenv("POLYCHASE_RANK")) return RunRank(std::atoi(r), world, argc, argv);   // launched by something else
