@@ -713,6 +713,35 @@ typedef struct pc_pnp_solve_result {
 } pc_pnp_solve_result;
 int pc_pnp_solve(pc_context* ctx, pc_pnp_problem* prob, const pc_pnp_camera* initial, const pc_pnp_solve_options* options,
                  pc_pnp_solve_result* result);
+/* Diagnostics of the device-resident solver: its DECISION step -- everything lev_marq.h:146-221 does between two residual
+ * sweeps -- run on scripted sums instead of a scene.  A decision depends only on the 56 sums of a sweep ([0..44] JtJ lower
+ * triangle packed row-major, [45..53] Jtr, [54] valid count, [55] cost), so every branch of it can be reached without a mesh.
+ * One launch, one workgroup per script; the state starts as pc_pnp_solve's and pc_track_solve_frame's does and is handed
+ * round by round to the solver's own code:
+ *   mode 0  the wavefront decision of the persistent tracking launch (the default of pc_track_solve_frame),
+ *   mode 1  its one-lane cross-check (POLYCHASE_TRACK_SERIAL_DECISION=1),
+ *   mode 2  the bare one-lane decision of pc_pnp_solve: no correspondence-count rules, no round limit (max_rounds ignored).
+ * options[i].rounds_hint > 0 is script i's round limit in place of max_rounds (modes 0 and 1).
+ * states[i * n_rounds + r] is the state after round r of script i.  Once a script is done, modes 0 and 1 skip its remaining
+ * rounds as the tracking launch leaves its loop; mode 2 still makes the call, as pc_pnp_solve's rounds enqueued past
+ * convergence do, and the solver returns at once: in every mode the remaining snapshots repeat the final state.
+ * PC_E_INVALID, with nothing launched: a null pointer, mode outside 0..2, n_scripts outside 1..1024, n_rounds outside 1..16.
+ * The struct is 4-byte words only (PC_LM_DEBUG_STATE_WORDS of them): the solver's state without its configuration and its
+ * copy of the latest accepted sums. */
+#define PC_LM_DEBUG_STATE_WORDS 169
+typedef struct pc_lm_debug_state {
+    pc_pnp_camera cam, cam_new;                           /* accepted parameters, latest candidate */
+    float R[9], t[3], fx, fy, cx, cy, aspect_ratio;       /* what the next sweep evaluates (the accepted ones once done) */
+    int convention_opencv, sweep_optimize_focal, sweep_optimize_pp;
+    float JtJ[81], diag[9], Jtr[9], step[9];              /* JtJ row-major: lower triangle, clamped diagonal; the rest stays 0 */
+    float cost, initial_cost, lambda, v, grad_norm, step_norm;
+    int iterations, invalid_steps, rebuild, phase, done;
+    int n_valid, status;                                  /* modes 0, 1: 0 ok, 1 fewer than 3 correspondences, 3 round limit */
+    int optimize_focal, optimize_pp;                      /* as the solver holds them: cleared when n_valid == 3 */
+} pc_lm_debug_state;
+int pc_debug_lm_decide(pc_context* ctx, int mode, int n_scripts, int n_rounds, int max_rounds,
+                       const pc_pnp_solve_options* options /* [n_scripts] */, const pc_pnp_camera* initial /* [n_scripts] */,
+                       const float* sums /* [n_scripts][n_rounds][56] */, pc_lm_debug_state* states /* [n_scripts][n_rounds] */);
 /* ---- SolveFrame in one call (cpp/tracker.cc:36-131): the correspondences of EVERY source frame + SolvePnPIterative ----
  * Two launches and one wait per frame: one ray-cast launch over the matches of all sources (each under its own
  * camera; world points stay on the GPU, no compaction), then the whole Levenberg-Marquardt loop and the inlier pass as

@@ -652,16 +652,13 @@ int pc_pnp_solve(pc_context* ctx, pc_pnp_problem* prob, const pc_pnp_camera* ini
         prob->lm_partials4 = prob->own_lm_partials4.p;
     }
     pc::LmState& h = *prob->lm_host;
-    std::memset(&h, 0, sizeof(h));
-    fill_lm_config(o, &h.cfg);
-    fill_lm_camera(initial, &h.cam);
-    h.cam_new = h.cam;
-    h.lambda = o->initial_lambda;
-    h.v = 2.0f;
-    h.grad_norm = -1.0f;
-    h.step_norm = -1.0f;
-    h.rebuild = 1;
-    pc::lm_make_params(h.cam, h.cfg, &h.sweep);   // phase 0: evaluate the initial parameters
+    {
+        pc::LmConfig cfg;
+        pc::LmCamera cam0;
+        fill_lm_config(o, &cfg);
+        fill_lm_camera(initial, &cam0);
+        pc::lm_init_state(h, cfg, cam0);   // phase 0: evaluate the initial parameters
+    }
     PC_HIP(hipMemcpyAsync(prob->lm_state, &h, sizeof(h), hipMemcpyHostToDevice, ctx->stream));
     // every round evaluates one parameter set; the first one is the initial set, Cholesky failures take no round
     int rounds = o->rounds_hint > 0 ? o->rounds_hint : 13;
@@ -999,6 +996,52 @@ int pc_debug_llt9(pc_context* ctx, const float* a81, const float* b9, float* l81
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     (void)hipFree(d);
     if (e != hipSuccess) return fail(PC_E_HIP, "pc_debug_llt9: %s", hipGetErrorString(e));
+    return PC_OK;
+}
+
+static_assert(sizeof(pc_lm_debug_state) == sizeof(pc::LmDebugState) && sizeof(pc_lm_debug_state) == PC_LM_DEBUG_STATE_WORDS * 4,
+              "pc_lm_debug_state and LmDebugState are the same words");
+static_assert(sizeof(pc_pnp_camera) == sizeof(pc::LmCamera), "pc_pnp_camera and LmCamera are the same words");
+
+int pc_debug_lm_decide(pc_context* ctx, int mode, int n_scripts, int n_rounds, int max_rounds, const pc_pnp_solve_options* options,
+                       const pc_pnp_camera* initial, const float* sums, pc_lm_debug_state* states) {
+    // the bounds keep the kernel short and its indices inside the buffers allocated below: checked before anything is launched
+    if (!ctx || !options || !initial || !sums || !states) return fail(PC_E_INVALID, "pc_debug_lm_decide: null argument");
+    if (mode < 0 || mode > 2) return fail(PC_E_INVALID, "pc_debug_lm_decide: mode %d is not 0 (wave), 1 (serial) or 2 (bare)", mode);
+    if (n_scripts < 1 || n_scripts > 1024) return fail(PC_E_INVALID, "pc_debug_lm_decide: n_scripts %d outside 1..1024", n_scripts);
+    if (n_rounds < 1 || n_rounds > 16) return fail(PC_E_INVALID, "pc_debug_lm_decide: n_rounds %d outside 1..16", n_rounds);
+    PC_HIP(hipSetDevice(ctx->device));
+    const size_t ns = (size_t)n_scripts, n_sums = ns * (size_t)n_rounds * 56, n_states = ns * (size_t)n_rounds;
+    std::vector<pc::LmConfig> cfgs(ns);
+    std::vector<pc::LmCamera> cams(ns);
+    std::vector<int> limits(ns);
+    for (size_t i = 0; i < ns; i++) {
+        fill_lm_config(&options[i], &cfgs[i]);
+        fill_lm_camera(&initial[i], &cams[i]);
+        limits[i] = options[i].rounds_hint > 0 ? options[i].rounds_hint : max_rounds;
+    }
+    const size_t b_cfg = ns * sizeof(pc::LmConfig), b_cam = ns * sizeof(pc::LmCamera), b_lim = ns * sizeof(int),
+                 b_sums = n_sums * sizeof(float), b_states = n_states * sizeof(pc::LmDebugState);   // (every size a multiple of 4)
+    char* d = nullptr;
+    PC_HIP(hipMalloc(reinterpret_cast<void**>(&d), b_cfg + b_cam + b_lim + b_sums + b_states));
+    char *d_cfg = d, *d_cam = d_cfg + b_cfg, *d_lim = d_cam + b_cam, *d_sums = d_lim + b_lim, *d_states = d_sums + b_sums;
+    hipError_t e = hipMemcpyAsync(d_cfg, cfgs.data(), b_cfg, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_cam, cams.data(), b_cam, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_lim, limits.data(), b_lim, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_sums, sums, b_sums, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) {
+        pc::launch_lm_decide_debug(mode, n_scripts, n_rounds, reinterpret_cast<const pc::LmConfig*>(d_cfg),
+                                   reinterpret_cast<const pc::LmCamera*>(d_cam), reinterpret_cast<const int*>(d_lim),
+                                   reinterpret_cast<const float*>(d_sums), reinterpret_cast<pc::LmDebugState*>(d_states), ctx->stream);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(states, d_states, b_states, hipMemcpyDeviceToHost, ctx->stream);
+    // (the host vectors above are pageable: the copies from them have been staged by the time hipMemcpyAsync returns; waiting
+    // here before they go out of scope all the same)
+    const hipError_t e_sync = hipStreamSynchronize(ctx->stream);
+    if (e == hipSuccess) e = e_sync;
+    (void)hipFree(d);
+    if (e != hipSuccess) return fail(PC_E_HIP, "pc_debug_lm_decide: %s", hipGetErrorString(e));
     return PC_OK;
 }
 

@@ -407,6 +407,11 @@ void launch_track_lm(const TrackLmArgs& a, hipStream_t s);
 
 // lm_cholesky9 + lm_cholesky9_solve (pnp_lm.hpp) of one system on the device; all pointers device memory
 void launch_llt9_debug(const float* a81, const float* b9, float* l81, float* x9, int* ok, hipStream_t s);
+// kernels_lm_debug.hip: the product's decision step (track_consume_wave / track_consume / lm_consume: mode 0 / 1 / 2) on scripted sums, one workgroup per
+// script; cfgs, cams, max_rounds [n_scripts], sums [n_scripts][n_rounds][56], states [n_scripts][n_rounds]: device memory
+struct LmDebugState;
+void launch_lm_decide_debug(int mode, int n_scripts, int n_rounds, const LmConfig* cfgs, const LmCamera* cams, const int* max_rounds,
+                            const float* sums, LmDebugState* states, hipStream_t s);
 
 
 // ---- kernels_refiner.hip ----

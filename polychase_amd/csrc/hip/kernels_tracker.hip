@@ -804,65 +804,7 @@ __device__ __forceinline__ void track_source_camera(const LmCamera& c, const flo
     out->sign = c.convention_opencv ? 1.0f : -1.0f;
 }
 
-// the decision of one round on top of lm_consume: the correspondence count is only known once the first sweep has
-// counted the valid entries (PnPProblem's n: pnp_problem.h:34-35, solvers.cc:54-55, tracker.cc:95-97)
-__device__ __forceinline__ void track_consume(LmState& s, const float* out56, int round, int max_rounds) {
-    if (s.phase == 0) {
-        s.n_valid = (int)out56[54];
-        if (s.n_valid < 3) {   // "Not enough features" (tracker.cc:95-97): nothing is solved
-            s.status = 1;
-            lm_finish(s);
-            return;
-        }
-        if (s.n_valid == 3 && (s.cfg.optimize_focal || s.cfg.optimize_pp)) {
-            // intrinsics are only optimised with more than 3 points: evaluate the initial parameters again without
-            // their columns (the round stays phase 0)
-            s.cfg.optimize_focal = 0;
-            s.cfg.optimize_pp = 0;
-            lm_make_params(s.cam, s.cfg, &s.sweep);
-            return;
-        }
-    }
-    lm_consume(s, out56);
-    if (!s.done && round + 1 >= max_rounds) {
-        s.status = 3;
-        lm_finish(s);
-    }
-}
-
-// track_consume by the workgroup's first wavefront (lm_consume_wave, pnp_lm.hpp): the same decision, the same bits
-__device__ __forceinline__ void track_consume_wave(LmState& s, const float* out56, int round, int max_rounds, int lane) {
-    lm_wave_sync();
-    if (s.phase == 0) {
-        const int n_valid = (int)out56[54];
-        const bool drop_intrinsics = n_valid == 3 && (s.cfg.optimize_focal || s.cfg.optimize_pp);
-        lm_wave_sync();
-        if (lane == 0) {
-            s.n_valid = n_valid;
-            if (n_valid < 3) {   // "Not enough features" (tracker.cc:95-97): nothing is solved
-                s.status = 1;
-                lm_finish(s);
-            } else if (drop_intrinsics) {
-                s.cfg.optimize_focal = 0;
-                s.cfg.optimize_pp = 0;
-                lm_make_params(s.cam, s.cfg, &s.sweep);
-            }
-        }
-        lm_wave_sync();
-        if (n_valid < 3 || drop_intrinsics) return;
-    }
-    lm_consume_wave(s, out56, lane);
-    lm_wave_sync();
-    if (!s.done && round + 1 >= max_rounds) {
-        lm_wave_sync();
-        if (lane == 0) {
-            s.status = 3;
-            lm_finish(s);
-        }
-        lm_wave_sync();
-    }
-}
-
+// (track_consume / track_consume_wave, the decision of one round with the tracker's rules on top: pnp_lm.hpp)
 __global__ __launch_bounds__(256) void track_lm_kernel(TrackLmArgs a) {
     __shared__ float s_part[4][PNP_ACC];
     __shared__ float s_out[PNP_ACC];
@@ -939,20 +881,7 @@ __global__ __launch_bounds__(256) void track_lm_kernel(TrackLmArgs a) {
             __syncthreads();
             tick(2);
             if (tid < 64) {   // the workgroup's first wavefront
-                if (round == 0 && tid == 0) {
-                    LmState& h = s_state;
-                    uint32_t* z = reinterpret_cast<uint32_t*>(&h);
-                    for (int i = 0; i < (int)(sizeof(LmState) / sizeof(uint32_t)); i++) z[i] = 0u;
-                    h.cfg = a.cfg;
-                    h.cam = cam0;
-                    h.cam_new = cam0;
-                    h.lambda = a.cfg.initial_lambda;
-                    h.v = 2.0f;
-                    h.grad_norm = -1.0f;
-                    h.step_norm = -1.0f;
-                    h.rebuild = 1;
-                    lm_make_params(h.cam, h.cfg, &h.sweep);
-                }
+                if (round == 0 && tid == 0) lm_init_state(s_state, a.cfg, cam0);
                 // the decision: the 9x9 algebra dealt out over the wavefront's lanes (same operations, same order per result:
                 // the serial code's bits), or -- serial_decision, the cross-check -- on one lane
                 if (!a.serial_decision) track_consume_wave(s_state, s_out, (int)round, a.max_rounds, tid);

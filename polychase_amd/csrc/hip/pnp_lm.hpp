@@ -11,6 +11,7 @@
 #pragma once
 
 #include <cmath>
+#include <cstring>
 
 #include "kernels.hpp"
 
@@ -114,6 +115,74 @@ PC_HD void lm_make_params(const LmCamera& c, const LmConfig& cfg, PnPParams* p) 
     p->optimize_pp = cfg.optimize_pp;
     p->loss_type = cfg.loss_type;
     p->loss_scale = cfg.loss_scale;
+}
+
+// The solver's state before the first sweep (lev_marq.h:133-145): everything zero, then the configuration, the initial guess
+// and phase 0 = "evaluate the initial parameters".  ONE copy for pc_pnp_solve (host, before the upload), track_lm_kernel
+// (round 0, lane 0) and the debug kernel of pc_debug_lm_decide.  No floating-point operation besides lm_make_params.
+PC_HD void lm_init_state(LmState& h, const LmConfig& cfg, const LmCamera& cam0) {
+#ifdef __HIP_DEVICE_COMPILE__
+    uint32_t* z = reinterpret_cast<uint32_t*>(&h);
+    for (int i = 0; i < (int)(sizeof(LmState) / sizeof(uint32_t)); i++) z[i] = 0u;
+#else
+    std::memset(&h, 0, sizeof(h));
+#endif
+    h.cfg = cfg;
+    h.cam = cam0;
+    h.cam_new = cam0;
+    h.lambda = cfg.initial_lambda;
+    h.v = 2.0f;
+    h.grad_norm = -1.0f;
+    h.step_norm = -1.0f;
+    h.rebuild = 1;
+    lm_make_params(h.cam, h.cfg, &h.sweep);   // phase 0: evaluate the initial parameters
+}
+
+// pc_debug_lm_decide (include/polychase_hip.h: pc_lm_debug_state, the same words in the same order): the state after a round,
+// without cfg and the cur_* copies
+struct LmDebugState {
+    LmCamera cam, cam_new;
+    float R[9], t[3], fx, fy, cx, cy, aspect_ratio;
+    int convention_opencv, sweep_optimize_focal, sweep_optimize_pp;
+    float JtJ[81], diag[9], Jtr[9], step[9];
+    float cost, initial_cost, lambda, v, grad_norm, step_norm;
+    int iterations, invalid_steps, rebuild, phase, done, n_valid, status;
+    int optimize_focal, optimize_pp;   // as they stand in the state's configuration (the n_valid == 3 rule clears them)
+};
+PC_HD void lm_debug_snapshot(const LmState& s, LmDebugState* o) {
+    o->cam = s.cam;
+    o->cam_new = s.cam_new;
+    for (int i = 0; i < 9; i++) o->R[i] = s.sweep.R[i];
+    for (int i = 0; i < 3; i++) o->t[i] = s.sweep.t[i];
+    o->fx = s.sweep.fx;
+    o->fy = s.sweep.fy;
+    o->cx = s.sweep.cx;
+    o->cy = s.sweep.cy;
+    o->aspect_ratio = s.sweep.aspect_ratio;
+    o->convention_opencv = s.sweep.convention_opencv;
+    o->sweep_optimize_focal = s.sweep.optimize_focal;
+    o->sweep_optimize_pp = s.sweep.optimize_pp;
+    for (int i = 0; i < 81; i++) o->JtJ[i] = s.JtJ[i];
+    for (int i = 0; i < 9; i++) {
+        o->diag[i] = s.diag[i];
+        o->Jtr[i] = s.Jtr[i];
+        o->step[i] = s.step[i];
+    }
+    o->cost = s.cost;
+    o->initial_cost = s.initial_cost;
+    o->lambda = s.lambda;
+    o->v = s.v;
+    o->grad_norm = s.grad_norm;
+    o->step_norm = s.step_norm;
+    o->iterations = s.iterations;
+    o->invalid_steps = s.invalid_steps;
+    o->rebuild = s.rebuild;
+    o->phase = s.phase;
+    o->done = s.done;
+    o->n_valid = s.n_valid;
+    o->status = s.status;
+    o->optimize_focal = s.cfg.optimize_focal;
+    o->optimize_pp = s.cfg.optimize_pp;
 }
 
 // In-place lower Cholesky of a 9x9 row-major matrix, left-looking like Eigen's unblocked llt_inplace
@@ -308,8 +377,8 @@ PC_HD void lm_consume(LmState& s, const float* out56) {
 // The same decision taken by one WAVEFRONT (track_lm_kernel, round 6): lm_consume above is ~1600 dependent instructions of one
 // lane -- 4.6 us of every 16-us LM round during which 255 workgroups wait.  Here the 9x9 algebra is dealt out over lanes 0..8
 // with EVERY floating-point operation of the serial code kept, on the same operands, in the same order per result -- so the
-// bits are the serial code's (tests/test_tracker_gpu.py holds the two against each other; POLYCHASE_TRACK_SERIAL_DECISION=1
-// runs the serial one):
+// bits are the serial code's (tests/test_tracker_gpu.py holds the two against each other on a scene, tests/test_pnp_lm_decision_gpu.py
+// on scripted sums that reach every branch; POLYCHASE_TRACK_SERIAL_DECISION=1 runs the serial one):
 //   * Cholesky, left-looking: lane i owns row i of L.  Column k: every lane i >= k forms a[i][k] - sum_{j<k} a[i][j] a[k][j]
 //     (row k's entries arrive as scalars: v_readlane), lane k's value is the pivot, one square root, one division per lane --
 //     9 dependent divisions instead of 36.
@@ -495,6 +564,65 @@ __device__ __forceinline__ void lm_consume_wave(LmState& s, const float* out56, 
         }
     }
     lm_advance_wave(s, lane);
+}
+
+// the decision of one round on top of lm_consume: the correspondence count is only known once the first sweep has
+// counted the valid entries (PnPProblem's n: pnp_problem.h:34-35, solvers.cc:54-55, tracker.cc:95-97)
+__device__ __forceinline__ void track_consume(LmState& s, const float* out56, int round, int max_rounds) {
+    if (s.phase == 0) {
+        s.n_valid = (int)out56[54];
+        if (s.n_valid < 3) {   // "Not enough features" (tracker.cc:95-97): nothing is solved
+            s.status = 1;
+            lm_finish(s);
+            return;
+        }
+        if (s.n_valid == 3 && (s.cfg.optimize_focal || s.cfg.optimize_pp)) {
+            // intrinsics are only optimised with more than 3 points: evaluate the initial parameters again without
+            // their columns (the round stays phase 0)
+            s.cfg.optimize_focal = 0;
+            s.cfg.optimize_pp = 0;
+            lm_make_params(s.cam, s.cfg, &s.sweep);
+            return;
+        }
+    }
+    lm_consume(s, out56);
+    if (!s.done && round + 1 >= max_rounds) {
+        s.status = 3;
+        lm_finish(s);
+    }
+}
+
+// track_consume by the workgroup's first wavefront (lm_consume_wave, pnp_lm.hpp): the same decision, the same bits
+__device__ __forceinline__ void track_consume_wave(LmState& s, const float* out56, int round, int max_rounds, int lane) {
+    lm_wave_sync();
+    if (s.phase == 0) {
+        const int n_valid = (int)out56[54];
+        const bool drop_intrinsics = n_valid == 3 && (s.cfg.optimize_focal || s.cfg.optimize_pp);
+        lm_wave_sync();
+        if (lane == 0) {
+            s.n_valid = n_valid;
+            if (n_valid < 3) {   // "Not enough features" (tracker.cc:95-97): nothing is solved
+                s.status = 1;
+                lm_finish(s);
+            } else if (drop_intrinsics) {
+                s.cfg.optimize_focal = 0;
+                s.cfg.optimize_pp = 0;
+                lm_make_params(s.cam, s.cfg, &s.sweep);
+            }
+        }
+        lm_wave_sync();
+        if (n_valid < 3 || drop_intrinsics) return;
+    }
+    lm_consume_wave(s, out56, lane);
+    lm_wave_sync();
+    if (!s.done && round + 1 >= max_rounds) {
+        lm_wave_sync();
+        if (lane == 0) {
+            s.status = 3;
+            lm_finish(s);
+        }
+        lm_wave_sync();
+    }
 }
 #endif  // __HIPCC__
 

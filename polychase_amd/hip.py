@@ -27,7 +27,7 @@ SYMBOLS = [
     "pc_gray_default_conversion", "pc_context_set_gray_conversion", "pc_context_get_gray_conversion", "pc_float_transfer_table",
     "pc_gray_quantize_weights", "pc_float_transfer_index",
     "pc_context_enable_timing", "pc_context_get_timing", "pc_context_get_busy_time", "pc_context_reset_timing",
-    "pc_debug_lk_profile", "pc_debug_lk_x86_stats", "pc_debug_llt9",
+    "pc_debug_lk_profile", "pc_debug_lk_x86_stats", "pc_debug_llt9", "pc_debug_lm_decide",
     "pc_frame_create", "pc_frame_destroy", "pc_frame_set_rgb", "pc_frame_set_rgb_f32", "pc_frame_set_gray",
     "pc_host_buffer_alloc", "pc_host_buffer_free",
     "pc_frame_num_levels", "pc_frame_level_size", "pc_frame_download_gray", "pc_frame_download_level",
@@ -94,6 +94,29 @@ class FrameResult(C.Structure):
                 ("flow_err", C.POINTER(C.c_float))]
 
 
+_PNP_CAMERA_FIELDS = [("q_xyzw", np.float32, (4,)), ("t", np.float32, (3,)), ("fx", np.float32), ("fy", np.float32), ("cx", np.float32),
+                      ("cy", np.float32), ("aspect_ratio", np.float32), ("convention_opencv", np.int32)]
+# pc_pnp_camera, pc_pnp_solve_options and pc_lm_debug_state (include/polychase_hip.h) as numpy record types: 4-byte words only
+PNP_CAMERA_DTYPE = np.dtype(_PNP_CAMERA_FIELDS)
+PNP_SOLVE_OPTIONS_DTYPE = np.dtype(
+    [("max_iterations", np.int32), ("initial_lambda", np.float32), ("min_lambda", np.float32), ("max_lambda", np.float32),
+     ("gradient_tol", np.float32), ("step_tol", np.float32), ("loss_type", np.int32), ("loss_scale", np.float32),
+     ("optimize_focal_length", np.int32), ("optimize_principal_point", np.int32), ("f_low", np.float32), ("f_high", np.float32),
+     ("cx_low", np.float32), ("cx_high", np.float32), ("cy_low", np.float32), ("cy_high", np.float32),
+     ("max_inlier_error", np.float32), ("rounds_hint", np.int32)])
+LM_DEBUG_STATE_DTYPE = np.dtype(
+    [("cam", PNP_CAMERA_DTYPE), ("cam_new", PNP_CAMERA_DTYPE), ("R", np.float32, (9,)), ("t", np.float32, (3,)), ("fx", np.float32),
+     ("fy", np.float32), ("cx", np.float32), ("cy", np.float32), ("aspect_ratio", np.float32), ("convention_opencv", np.int32),
+     ("sweep_optimize_focal", np.int32), ("sweep_optimize_pp", np.int32), ("JtJ", np.float32, (81,)), ("diag", np.float32, (9,)),
+     ("Jtr", np.float32, (9,)), ("step", np.float32, (9,)), ("cost", np.float32), ("initial_cost", np.float32),
+     ("lambda", np.float32), ("v", np.float32), ("grad_norm", np.float32), ("step_norm", np.float32), ("iterations", np.int32),
+     ("invalid_steps", np.int32), ("rebuild", np.int32), ("phase", np.int32), ("done", np.int32), ("n_valid", np.int32),
+     ("status", np.int32), ("optimize_focal", np.int32), ("optimize_pp", np.int32)])
+LM_DEBUG_STATE_WORDS = 169                    # PC_LM_DEBUG_STATE_WORDS
+assert LM_DEBUG_STATE_DTYPE.itemsize == 4 * LM_DEBUG_STATE_WORDS and PNP_CAMERA_DTYPE.itemsize == 52
+LM_DECIDE_WAVE, LM_DECIDE_SERIAL, LM_DECIDE_BARE = 0, 1, 2
+
+
 class PolychaseHipError(RuntimeError):
     pass
 
@@ -149,6 +172,7 @@ def load():
     L.pc_debug_lk_profile.argtypes = [vp, C.POINTER(C.c_ulonglong)]
     L.pc_debug_lk_x86_stats.argtypes = [vp, C.c_int, C.POINTER(C.c_ulonglong)]
     L.pc_debug_llt9.argtypes = [vp, vp, vp, vp, vp, ip]
+    L.pc_debug_lm_decide.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
     L.pc_frame_create.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]
     L.pc_frame_destroy.argtypes = [vp]
     L.pc_frame_destroy.restype = None
@@ -376,6 +400,19 @@ class Context:
         l, x, ok = np.zeros((9, 9), np.float32), np.zeros(9, np.float32), C.c_int()
         _check(load().pc_debug_llt9(self._h, a.ctypes.data, b.ctypes.data, l.ctypes.data, x.ctypes.data, C.byref(ok)))
         return l, x, bool(ok.value)
+
+    def lm_decide(self, mode: int, options: np.ndarray, initial: np.ndarray, sums: np.ndarray, max_rounds: int = 1 << 30):
+        """the device solver's decision step on scripted sums (pc_debug_lm_decide): options PNP_SOLVE_OPTIONS_DTYPE [n],
+        initial PNP_CAMERA_DTYPE [n], sums float32 [n][rounds][56] -> LM_DEBUG_STATE_DTYPE [n][rounds], the state after each round"""
+        options = np.ascontiguousarray(options, PNP_SOLVE_OPTIONS_DTYPE)
+        initial = np.ascontiguousarray(initial, PNP_CAMERA_DTYPE)
+        sums = np.ascontiguousarray(sums, np.float32)
+        if sums.ndim != 3 or sums.shape[2] != 56 or options.shape != (sums.shape[0],) or initial.shape != (sums.shape[0],):
+            raise ValueError(f"sums must be [n][rounds][56] with n options and cameras, got {sums.shape}, {options.shape}, {initial.shape}")
+        states = np.zeros(sums.shape[:2], LM_DEBUG_STATE_DTYPE)
+        _check(load().pc_debug_lm_decide(self._h, int(mode), sums.shape[0], sums.shape[1], int(max_rounds), options.ctypes.data,
+                                         initial.ctypes.data, sums.ctypes.data, states.ctypes.data))
+        return states
 
     def busy_ms(self, kernel_class: str) -> float:
         """wall time during which at least one launch of the class was executing (launches may overlap)"""
