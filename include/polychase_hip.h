@@ -469,6 +469,48 @@ int pc_lk_track_affine(pc_context* ctx, const pc_frame* frame1, const pc_frame* 
                        float* next_xy, uint8_t* status, float* err, float* back_xy, uint8_t* back_status, float* affine_m,
                        uint8_t* affine_state);
 
+/* ---- search prepass (not in the reference, off by default) ----
+ * Pyramidal LK starts at zero displacement and reaches about a window's width per level.  Past that the rows are not dropped: they
+ * come back with status 1 and a wrong end point.  With search_radius = R > 0 ONE additional launch, directly after the forward
+ * launch, finds per (keypoint, target) pair an integer displacement d by block matching, runs LK once more from p + d and keeps
+ * whichever of the two records has the smaller stored patch error (Blender's tracker calls the brute-force search its prepass).  It
+ * is a rescue, not a check: a record is never replaced by one with a larger patch error, and a row with forward status 0 can gain
+ * status 1.  It runs before the affine refinement, the target-mask test, the correlation pass and the backward launch, which judge
+ * the chosen end points unchanged.  Every fp32 and fp64 operation is rounded on its own, every sum is an exact integer, and the
+ * arithmetic mode (pc_context_set_arithmetic) plays no part.  T = the top level both pyramids have, min(max_level, levels - 1).
+ *   level, radius  s = the smallest level >= 0 with ceil(R / 2^s) <= 16, clamped to T; r = min(16, ceil(R / 2^s)).  w_s, h_s: the
+ *              level's interior size.  The block is 8 x 8 u8 pixels of the interior planes at level s.
+ *   template   lscale = 1.f / (float)(1 << s); cx = (int)floorf(p.x * lscale + 0.5f), cy likewise; origin (ox, oy) = (cx - 4,
+ *              cy - 4).  The block is inside when 0 <= ox, ox + 8 <= w_s, 0 <= oy and oy + 8 <= h_s.  A keypoint whose block is
+ *              not inside (a non-finite or out-of-frame p included) is not searched: state 0, d = 0, record untouched.
+ *   candidates all integer (dx, dy), |dx|, |dy| <= r, whose block at (ox + dx, oy + dy) in the target's level-s plane is inside by
+ *              the same test.  No padding pixel is ever compared, and the kernel never reads outside the planes, whatever it is
+ *              handed.  SAD = the sum over the 64 pixels of |J - I|, an exact integer <= 16320.
+ *   choice     the candidate with the smallest key (SAD, dx^2 + dy^2, dy, dx), compared lexicographically.  It is accepted when
+ *              4 * SAD_best <= 3 * SAD_zero, SAD_zero the SAD of (0, 0), which is always a candidate; otherwise d = 0.
+ *              d = (dx << s, dy << s) in level-0 pixels.  d = 0: state 0, nothing more for this pair.
+ *   guided pass   for d != 0: the canonical (integer-exact) plain LK pass with the patch error, pco_lk under PCO_EMU_CANONICAL,
+ *              template at p, with ONE change: at level T the search starts at guess * lscale_T instead of p * lscale_T, guess =
+ *              (p.x + (float)d.x, p.y + (float)d.y) -- OPTFLOW_USE_INITIAL_FLOW.  Bounds tests, weights, template values, the
+ *              2 x 2 solve, the epsilon test, the oscillation exit, the level-0 error and the status rules are unchanged.
+ *              -> (q_g, err_g, status_g).
+ *   keep the better   the forward record (q_f, err_f, status_f) becomes (q_g, err_g, 1) iff status_g == 1 && (status_f == 0 ||
+ *              err_g < err_f), compared in fp32 (a NaN fails): state 1.  Otherwise it stays bit for bit: state 2.
+ *   forward-backward   rows in state 1 are tracked back by the same canonical pass from template q in the target, searched in
+ *              frame1, with level T started at (q.x - (float)d.x, q.y - (float)d.y), and judged by the d2 <= thr2 rule of
+ *              pc_lk_track_fb into the same back_xy / back_status; every other row goes through the usual backward launch.
+ * The block matching assumes brightness constancy: search_radius > 0 together with normalize == 1 is PC_E_INVALID (a gain-aware
+ * search is a follow-up), and so is a radius outside 0 .. 256.  Records, compaction, unpacking and everything downstream are
+ * unchanged (kernels_lk_search.hip; the rule restated in numpy: tests/lk_search_ref.py).
+ * pc_lk_track_search: search_radius == 0 is exactly pc_lk_track_affine (nothing else is enqueued); > 0 adds the launch, timed under
+ * PC_K_LK, and with fb_threshold > 0 one small backward launch for the rows in state 1, timed under PC_K_LK_FB.  search_d
+ * ([n_targets][N][2] int16, may be NULL) receives d of every pair, zero in state 0; search_state ([n_targets][N] bytes, may be
+ * NULL): 0 = no displacement (or search_radius == 0), 1 = record replaced, 2 = searched and record kept. */
+int pc_lk_track_search(pc_context* ctx, const pc_frame* frame1, const pc_frame* const* targets, int n_targets,
+                       const pc_flow_options* opt, int search_radius, int affine, int normalize, double min_correlation,
+                       double fb_threshold, int margin, float* next_xy, uint8_t* status, float* err, float* back_xy,
+                       uint8_t* back_status, float* affine_m, uint8_t* affine_state, int16_t* search_d, uint8_t* search_state);
+
 /* ---- analyzer: the pipelined per-clip engine behind GenerateOpticalFlowDatabase ----
  * (cpp/opticalflow.cc:209-321).  Holds a ring of resident frames (the reference's 17-frame
  * SequentialWrapper cache, cpp/opticalflow_thread.h:34-79, generalised), builds every frame's gray
@@ -565,6 +607,11 @@ int pc_analyzer_set_normalize(pc_analyzer* a, int normalize);
  * the value.  Any other value, a null analyzer, or 1 while normalize is 1: PC_E_INVALID; pc_analyzer_submit refuses a job while
  * both are 1. */
 int pc_analyzer_set_affine_refinement(pc_analyzer* a, int affine);
+/* Search prepass (pc_lk_track_search) of the jobs submitted FROM NOW ON: 0 = off (the default), 1..256 = the radius in level-0
+ * pixels; every job then runs the search launch directly after its forward launch.  Jobs already submitted keep theirs;
+ * pc_analyzer_reset keeps the value.  Any other value, a null analyzer, or > 0 while normalize is 1: PC_E_INVALID;
+ * pc_analyzer_submit refuses a job while both are set. */
+int pc_analyzer_set_search_radius(pc_analyzer* a, int search_radius);
 /* Detection mask (pc_frame_set_mask, gftt.cc:45-83) of the frames put FROM NOW ON with will_detect != 0; NULL: no mask (the
  * default).  Detection is enqueued inside pc_analyzer_put_frame, so every slot of the ring keeps a mask plane of its own: a
  * detection already enqueued keeps the mask it was enqueued with, and the mask may change from frame to frame.  A host mask

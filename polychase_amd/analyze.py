@@ -155,6 +155,8 @@ def main(argv=None) -> int:
                     help="transfer curve for float32 frames: scene-linear values through the sRGB curve or a power law (nothing for uint8 frames)")
     ap.add_argument("--float-gamma", type=float, default=2.2, metavar="G", help="--float-transfer gamma: the exponent's inverse, 1..4")
     ap.add_argument("--float-exposure", type=float, default=0.0, metavar="STOPS", help="gain in stops in front of the transfer curve, -16..16")
+    ap.add_argument("--search-radius", type=int, default=0, metavar="N",
+                    help="search prepass: block matching within N pixels (1..256) in front of a second LK pass, for fast pans and the long skips (0: off; not with --normalize)")
     ap.add_argument("--piece-frames", type=int, default=16, help="frames per piece of the record log handed to rank 0")
     ap.add_argument("--gpus", type=int, default=0, help="launch this many ranks (one per GPU) of this command")
     args = ap.parse_args(argv)
@@ -207,6 +209,7 @@ def main(argv=None) -> int:
     fopt.min_correlation = args.min_correlation
     fopt.normalize = args.normalize
     fopt.affine_refinement = args.affine
+    fopt.search_radius = args.search_radius
     fopt.channel_weights = tuple(args.channel_weights) if args.channel_weights else None
     fopt.float_transfer = args.float_transfer
     fopt.float_transfer_gamma = args.float_gamma

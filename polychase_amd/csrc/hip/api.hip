@@ -494,7 +494,7 @@ int check_fb_threshold(double fb_threshold) {
 }
 
 int run_lk_fb(pc_context* ctx, const pc_frame* frame1, const pc_frame* const* targets, int n_targets, const pc_flow_options* opt,
-              double fb_threshold, int set, float2* back_xy, uint8_t* back_status, int normalize) {
+              double fb_threshold, int set, float2* back_xy, uint8_t* back_status, int normalize, bool search) {
     hipStream_t const lk_stream = ctx->lane_stream(set);
     const int n = frame1->n_kps;
     if (n == 0) return PC_OK;
@@ -525,9 +525,20 @@ int run_lk_fb(pc_context* ctx, const pc_frame* frame1, const pc_frame* const* ta
     p.back_xy = back_xy;
     p.back_status = back_status;
     p.x86_order = (ctx->arith & PC_ARITH_LK_X86_ORDER) ? 1 : 0;
-    ScopedTimer tm(ctx, PC_K_LK_FB, lk_stream);
-    if (!(normalize ? pc::launch_lk_norm_fb(p, lk_stream) : pc::launch_lk_fb(p, lk_stream)))
-        return fail(PC_E_INVALID, "unsupported window size %d", frame1->win);
+    if (search) {
+        p.search_d = ctx->lk_search_d[set].p;
+        p.search_state = ctx->lk_search_state[set].p;
+    }
+    {
+        ScopedTimer tm(ctx, PC_K_LK_FB, lk_stream);
+        if (!(normalize ? pc::launch_lk_norm_fb(p, lk_stream) : pc::launch_lk_fb(p, lk_stream)))
+            return fail(PC_E_INVALID, "unsupported window size %d", frame1->win);
+    }
+    if (search) {
+        // the rows the search replaced: tracked back from q with the top level started at q - d
+        ScopedTimer tm(ctx, PC_K_LK_FB, lk_stream);
+        if (!pc::launch_lk_search_fb(p, lk_stream)) return fail(PC_E_INVALID, "unsupported window size %d", frame1->win);
+    }
     return PC_OK;
 }
 
@@ -565,6 +576,48 @@ int run_lk_affine(pc_context* ctx, const pc_frame* frame1, const pc_frame* const
     p.affine_state = affine_state;
     ScopedTimer tm(ctx, PC_K_LK, lk_stream);   // no class of its own: a job with the option shows two lk launches
     if (!pc::launch_lk_affine(p, lk_stream)) return fail(PC_E_INVALID, "unsupported window size %d", frame1->win);
+    return PC_OK;
+}
+
+int check_search_radius(int search_radius, int normalize) {
+    if (search_radius < 0 || search_radius > 256) return fail(PC_E_INVALID, "search_radius must be 0 (off) or 1..256, got %d", search_radius);
+    if (search_radius > 0 && normalize == 1) return fail(PC_E_INVALID, "the search prepass assumes brightness constancy: not together with normalize");
+    return PC_OK;
+}
+
+int run_lk_search(pc_context* ctx, const pc_frame* frame1, const pc_frame* const* targets, int n_targets, const pc_flow_options* opt,
+                  int search_radius, int set) {
+    hipStream_t const lk_stream = ctx->lane_stream(set);
+    const int n = frame1->n_kps;
+    if (n == 0) return PC_OK;
+    const size_t rows = (size_t)n * n_targets;
+    PC_HIP(ctx->lk_search_d[set].ensure(rows));
+    PC_HIP(ctx->lk_search_state[set].ensure(rows));
+    pc::SearchParams p;
+    std::memset(&p, 0, sizeof(p));
+    int max_level = std::min(opt->max_level, frame1->nlevels - 1);   // as in run_lk
+    for (int t = 0; t < n_targets; t++) max_level = std::min(max_level, targets[t]->nlevels - 1);
+    if (max_level < 0) max_level = 0;
+    for (int l = 0; l <= max_level; l++) {
+        p.src[l] = frame1->levels[l];
+        for (int t = 0; t < n_targets; t++) p.tgt[t][l] = targets[t]->levels[l].img;
+    }
+    p.n_targets = n_targets;
+    p.max_level = max_level;
+    p.n = n;
+    p.win = frame1->win;
+    pc::search_level_radius(search_radius, max_level, &p.s, &p.r);
+    p.max_iters = std::min(std::max(opt->term_max_iters, 0), 100);
+    const double eps = std::min(std::max(opt->term_epsilon, 0.), 10.);
+    p.eps_sq = eps * eps;
+    p.min_eig_thr = (float)opt->min_eigen_threshold;
+    p.pts = frame1->d_kps;
+    p.perm = frame1->perm_valid ? frame1->d_perm : ctx->lk_perm.p;   // the order run_lk visited the keypoints in
+    p.rec = ctx->lk_rec[set].p;
+    p.search_d = ctx->lk_search_d[set].p;
+    p.search_state = ctx->lk_search_state[set].p;
+    ScopedTimer tm(ctx, PC_K_LK, lk_stream);   // no class of its own, as the affine refinement
+    if (!pc::launch_lk_search(p, lk_stream)) return fail(PC_E_INVALID, "unsupported window size %d", frame1->win);
     return PC_OK;
 }
 
@@ -960,6 +1013,8 @@ void pc_context_destroy(pc_context* c) {
     c->lk_corr.release();
     c->lk_affine_m.release();
     c->lk_affine_state.release();
+    for (auto& b : c->lk_search_d) b.release();
+    for (auto& b : c->lk_search_state) b.release();
     c->lk_cidx.release();
     for (auto& b : c->lk_block_counts) b.release();
     c->lk_perm.release();
@@ -1517,10 +1572,12 @@ int pc_frame_set_keypoints(pc_context* ctx, pc_frame* f, const float* xy, int n)
 static int lk_track_impl(pc_context* ctx, const pc_frame* frame1, const pc_frame* const* targets, int n_targets,
                          const pc_flow_options* opt, double fb_threshold, int margin, float* next_xy, uint8_t* status, float* err,
                          float* back_xy, uint8_t* back_status, double min_correlation = 0.0, float* corr = nullptr, int normalize = 0,
-                         int affine = 0, float* affine_m = nullptr, uint8_t* affine_state = nullptr) {
+                         int affine = 0, float* affine_m = nullptr, uint8_t* affine_state = nullptr, int search_radius = 0,
+                         int16_t* search_d = nullptr, uint8_t* search_state = nullptr) {
     int rc = check_target_margin(margin, true);   // first: a margin is refused whatever the handles
     if (rc != PC_OK) return rc;
     if ((rc = check_normalize(normalize)) != PC_OK) return rc;   // ... and so is a switch that is neither off nor on
+    if ((rc = check_search_radius(search_radius, normalize)) != PC_OK) return rc;
     if ((rc = check_affine(affine, normalize)) != PC_OK) return rc;
     if ((rc = check_min_correlation(min_correlation)) != PC_OK) return rc;   // ... and so is a correlation
     if ((rc = check_lk_args(ctx, frame1, targets, n_targets, opt)) != PC_OK) return rc;
@@ -1531,6 +1588,16 @@ static int lk_track_impl(pc_context* ctx, const pc_frame* frame1, const pc_frame
     rc = run_lk(ctx, frame1, targets, n_targets, opt, 0, normalize);
     if (rc != PC_OK) return rc;
     const size_t rows = (size_t)frame1->n_kps * n_targets;
+    if (rows > 0 && !search_radius) {
+        if (search_d) std::memset(search_d, 0, rows * sizeof(short2));
+        if (search_state) std::memset(search_state, 0, rows);
+    }
+    if (rows > 0 && search_radius) {
+        // search prepass: directly after the forward launch, in front of the refinement and of every check
+        if ((rc = run_lk_search(ctx, frame1, targets, n_targets, opt, search_radius, 0)) != PC_OK) return rc;
+        if (search_d) PC_HIP(hipMemcpyAsync(search_d, ctx->lk_search_d[0].p, rows * sizeof(short2), hipMemcpyDeviceToHost, ctx->stream));
+        if (search_state) PC_HIP(hipMemcpyAsync(search_state, ctx->lk_search_state[0].p, rows, hipMemcpyDeviceToHost, ctx->stream));
+    }
     if (rows > 0 && !affine) {
         if (affine_m) std::memset(affine_m, 0, rows * sizeof(float4));
         if (affine_state) std::memset(affine_state, 0, rows);
@@ -1586,7 +1653,7 @@ static int lk_track_impl(pc_context* ctx, const pc_frame* frame1, const pc_frame
         if (back_xy) PC_HIP(ctx->lk_back_xy.ensure(rows));
         if (back_status) PC_HIP(ctx->lk_back_status.ensure(rows));
         rc = run_lk_fb(ctx, frame1, targets, n_targets, opt, fb_threshold, 0, back_xy ? ctx->lk_back_xy.p : nullptr,
-                       back_status ? ctx->lk_back_status.p : nullptr, normalize);
+                       back_status ? ctx->lk_back_status.p : nullptr, normalize, search_radius > 0);
         if (rc != PC_OK) return rc;
         if (back_xy) PC_HIP(hipMemcpyAsync(back_xy, ctx->lk_back_xy.p, rows * sizeof(float2), hipMemcpyDeviceToHost, ctx->stream));
         if (back_status) PC_HIP(hipMemcpyAsync(back_status, ctx->lk_back_status.p, rows, hipMemcpyDeviceToHost, ctx->stream));
@@ -1642,6 +1709,14 @@ int pc_lk_track_affine(pc_context* ctx, const pc_frame* frame1, const pc_frame* 
                        uint8_t* affine_state) {
     return lk_track_impl(ctx, frame1, targets, n_targets, opt, fb_threshold, margin, next_xy, status, err, back_xy, back_status,
                          min_correlation, nullptr, normalize, affine, affine_m, affine_state);
+}
+
+int pc_lk_track_search(pc_context* ctx, const pc_frame* frame1, const pc_frame* const* targets, int n_targets,
+                       const pc_flow_options* opt, int search_radius, int affine, int normalize, double min_correlation, double fb_threshold,
+                       int margin, float* next_xy, uint8_t* status, float* err, float* back_xy, uint8_t* back_status, float* affine_m,
+                       uint8_t* affine_state, int16_t* search_d, uint8_t* search_state) {
+    return lk_track_impl(ctx, frame1, targets, n_targets, opt, fb_threshold, margin, next_xy, status, err, back_xy, back_status,
+                         min_correlation, nullptr, normalize, affine, affine_m, affine_state, search_radius, search_d, search_state);
 }
 
 static int lk_track_filtered_impl(pc_context* ctx, const pc_frame* frame1, const pc_frame* const* targets, int n_targets,

@@ -106,6 +106,7 @@ struct pc_analyzer {
     double fb_threshold = 0.0;           // forward-backward check of the jobs submitted from now on (0: off)
     double min_correlation = 0.0;        // minimum correlation of the jobs submitted from now on (0: off)
     int normalize = 0;                   // brightness-normalised LK for the jobs submitted from now on (0: off)
+    int search_radius = 0;               // search prepass of the jobs submitted from now on (0: off); submit refuses > 0 beside normalize
     int affine = 0;                      // affine refinement of the jobs submitted from now on (0: off); submit refuses 1 beside normalize
     // Target-side masks (pc_analyzer_set_target_mask_margin): -1 off, else the margin of the frames put from now on.  While it is
     // >= 0 and a mask is in force every frame put takes the mask -- pc_frame::target_margin is the frame's role as a target,
@@ -446,6 +447,7 @@ int pc_analyzer_submit(pc_analyzer* a, int32_t frame1, const int32_t* targets, i
     if (n_targets < 0 || n_targets > PC_MAX_TARGETS) return fail(PC_E_INVALID, "n_targets must be in [0,%d]", PC_MAX_TARGETS);
     if (a->job_count == a->jobs.size()) return fail(PC_E_STATE, "%zu jobs already in flight: call pc_analyzer_collect", a->job_count);
     if (int arc = check_affine(a->affine, a->normalize)) return arc;   // normalize may have been switched on after the refinement
+    if (int src = check_search_radius(a->search_radius, a->normalize)) return src;   // ... or after the search
     pc_context* ctx = a->ctx;
     PC_HIP(hipSetDevice(ctx->device));
     HelperPriorityScope prio_scope(a->prio.hi);
@@ -533,6 +535,8 @@ int pc_analyzer_submit(pc_analyzer* a, int32_t frame1, const int32_t* targets, i
             a->gate_armed = true;
         }
         if ((rc = run_lk(ctx, s1->frame, tg, n_targets, &a->fopt, lane, a->normalize)) != PC_OK) return rc;
+        // search prepass: directly after the forward launch on the same lane, in front of the refinement and of every check
+        if (a->search_radius > 0 && (rc = run_lk_search(ctx, s1->frame, tg, n_targets, &a->fopt, a->search_radius, lane)) != PC_OK) return rc;
         // affine refinement: the launch follows the forward one on the same lane; everything below judges the refined end points
         if (a->affine && (rc = run_lk_affine(ctx, s1->frame, tg, n_targets, &a->fopt, lane)) != PC_OK) return rc;
         // target-side masks: rows that end where their target's plane is off are dropped before the backward launch looks at them
@@ -546,7 +550,7 @@ int pc_analyzer_submit(pc_analyzer* a, int32_t frame1, const int32_t* targets, i
         if (a->min_correlation > 0.0 && (rc = run_lk_corr(ctx, s1->frame, tg, n_targets, a->min_correlation, lane)) != PC_OK) return rc;
         // forward-backward check: the backward launch follows on the same lane and rewrites the status of the records the
         // compaction below filters; the gate is the forward launch's alone
-        if (a->fb_threshold > 0.0 && (rc = run_lk_fb(ctx, s1->frame, tg, n_targets, &a->fopt, a->fb_threshold, lane, nullptr, nullptr, a->normalize)) != PC_OK) return rc;
+        if (a->fb_threshold > 0.0 && (rc = run_lk_fb(ctx, s1->frame, tg, n_targets, &a->fopt, a->fb_threshold, lane, nullptr, nullptr, a->normalize, a->search_radius > 0)) != PC_OK) return rc;
     }
     SlowSection ss_post("submit/post enqueue");
     uint8_t* const pack = ctx->lk_pack[lane].p;
@@ -644,6 +648,14 @@ int pc_analyzer_set_normalize(pc_analyzer* a, int normalize) {
     if (int rc = check_normalize(normalize)) return rc;   // first: a value is refused whatever the handle
     if (!a) return fail(PC_E_INVALID, "null analyzer");
     a->normalize = normalize;
+    return PC_OK;
+}
+
+int pc_analyzer_set_search_radius(pc_analyzer* a, int search_radius) {
+    if (int rc = check_search_radius(search_radius, 0)) return rc;   // first: a value is refused whatever the handle
+    if (!a) return fail(PC_E_INVALID, "null analyzer");
+    if (int rc = check_search_radius(search_radius, a->normalize)) return rc;
+    a->search_radius = search_radius;
     return PC_OK;
 }
 

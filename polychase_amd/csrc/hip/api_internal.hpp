@@ -82,8 +82,16 @@ int run_lk(pc_context* ctx, const pc_frame* frame1, const pc_frame* const* targe
 // forward-backward check on the records run_lk has just left in set `set`, on the same lane (fb_threshold > 0);
 // back_xy / back_status: device arrays [n_targets][n] or null
 int check_fb_threshold(double fb_threshold);
+// search: run_lk_search has run on the set; the rows it replaced are tracked back by a launch of their own (timed under PC_K_LK_FB too)
 int run_lk_fb(pc_context* ctx, const pc_frame* frame1, const pc_frame* const* targets, int n_targets, const pc_flow_options* opt,
-              double fb_threshold, int set = 0, float2* back_xy = nullptr, uint8_t* back_status = nullptr, int normalize = 0);
+              double fb_threshold, int set = 0, float2* back_xy = nullptr, uint8_t* back_status = nullptr, int normalize = 0,
+              bool search = false);
+// search prepass (include/polychase_hip.h: pc_lk_track_search) on the records run_lk has just left in set `set`, on the same lane,
+// before run_lk_affine and everything after it.  check_search_radius: 0 .. 256, and > 0 not together with normalize.  The
+// displacements and states stay in pc_context::lk_search_d / lk_search_state of the set, [target][n], for run_lk_fb
+int check_search_radius(int search_radius, int normalize);
+int run_lk_search(pc_context* ctx, const pc_frame* frame1, const pc_frame* const* targets, int n_targets, const pc_flow_options* opt,
+                  int search_radius, int set = 0);
 // affine refinement (include/polychase_hip.h: pc_lk_track_affine) of the records run_lk has just left in set `set`, on the same
 // lane, before run_lk_target_mask, run_lk_corr and run_lk_fb, which then judge the refined end points.  check_affine: 0 or 1, and
 // not together with normalize; affine_m / affine_state: device arrays [target][n], zeroed by the caller, or null

@@ -216,6 +216,8 @@ struct pc_context {
     DevBuf<float> lk_corr;                 // pc_lk_track_correlated: the scores, [target][n]
     DevBuf<float4> lk_affine_m;            // pc_lk_track_affine: the matrices and the states, [target][n]
     DevBuf<uint8_t> lk_affine_state;
+    DevBuf<short2> lk_search_d[2];         // pc_lk_track_search: the displacements and the states of a job, [target][n], one set
+    DevBuf<uint8_t> lk_search_state[2];    // per job lane (the backward launches read them)
     DevBuf<uint8_t> lk_choked;             // pc_lk_track_masked, pc_frame_download_choked_mask: the targets' choked planes
     DevBuf<uint32_t> lk_cidx, lk_block_counts[2], lk_perm, lk_hist;
     DevBuf<uint32_t> lk_gate;              // LKParams::gate of the analyzer's launches (one word)

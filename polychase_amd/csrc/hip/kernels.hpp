@@ -267,6 +267,10 @@ struct LKFBParams {
     float2* back_xy;                       // [target][n] in keypoint order, (0, 0) where status_f == 0; or null
     uint8_t* back_status;                  // [target][n]; or null
     int x86_order;                         // PC_ARITH_LK_X86_ORDER
+    // search prepass (kernels_lk_search.hip), both null when it is off: SearchParams::search_d / search_state of the forward side.
+    // launch_lk_fb leaves the rows in state 1 alone, launch_lk_search_fb tracks exactly those back, started at q - d
+    const short2* search_d;
+    const uint8_t* search_state;
 };
 // false: window or target count out of range (nothing enqueued)
 bool launch_lk_fb(const LKFBParams& p, hipStream_t s);
@@ -314,6 +318,35 @@ struct AffineParams {
 };
 // false: window or target count out of range (nothing enqueued)
 bool launch_lk_affine(const AffineParams& p, hipStream_t s);
+
+// ---- kernels_lk_search.hip ----
+// Search prepass (include/polychase_hip.h: pc_lk_track_search has the rule): per (keypoint, target) pair an integer displacement d
+// by block matching at level s within radius r, the canonical plain LK pass once more from p + d, and the record of the forward
+// launch replaced when the guided result has status 1 and the smaller patch error (or the forward status is 0).  One launch per
+// frame1 job, directly after the forward launch.
+struct SearchParams {
+    Level src[kMaxLevels];              // frame1 levels 0 .. max_level
+    const uint8_t* tgt[8][kMaxLevels];  // [target][level] interior origins of the targets' u8 planes (frame1's geometry)
+    int n_targets;
+    int max_level;                      // effective (min over pyramids), as in the forward launch
+    int n;                              // keypoints
+    int win;                            // 3 .. PC_MAX_WINDOW, the padding of the planes
+    int s, r;                           // search_level_radius(search_radius, max_level)
+    int max_iters;                      // TermCriteria clamps and threshold of the forward launch
+    double eps_sq;
+    float min_eig_thr;
+    const float2* pts;                  // frame1's keypoints
+    const uint32_t* perm;               // visiting order of the forward launch (slot -> keypoint) or null
+    float4* rec;                        // the forward launch's records, LKParams::out_rec
+    short2* search_d;                   // [target][n] in keypoint order: d in level-0 pixels, (0, 0) in state 0; or null
+    uint8_t* search_state;              // [target][n]: 0 no displacement found, 1 record replaced, 2 record kept; or null
+};
+// the level the blocks are matched at and the radius there: s = the smallest level with ceil(R / 2^s) <= 16, at most top_level
+void search_level_radius(int search_radius, int top_level, int* s, int* r);
+// false: window, target count, level or radius out of range (nothing enqueued)
+bool launch_lk_search(const SearchParams& p, hipStream_t s);
+// the backward pass of the rows in state 1 (LKFBParams::search_d / search_state, both required); canonical whatever x86_order says
+bool launch_lk_search_fb(const LKFBParams& p, hipStream_t s);
 
 // ---- kernels_lk_norm.hip ----
 // Brightness-normalised LK (include/polychase_hip.h: pc_lk_track_normalized has the rule): what launch_lk / launch_lk_fb are

@@ -24,8 +24,10 @@ __global__ __launch_bounds__(256) void lk_fb_kernel(const LKFBParams p) {
     const bool tgt_active = grp < p.n_targets;
     float4 rec = make_float4(0.f, 0.f, 0.f, 0.f);
     if (tgt_active) rec = p.rec[(size_t)slot * kRecStride + grp];
-    const bool fwd_ok = tgt_active && __float_as_uint(rec.w) == 1u;   // uniform in the group
     const int feat = p.perm ? (int)p.perm[slot] : slot;
+    // search prepass: a row it replaced (state 1) is lk_search_fb_kernel's, this launch neither tracks nor writes it
+    const bool guided = p.search_state && tgt_active && p.search_state[(size_t)grp * (size_t)p.n + (size_t)feat] == 1;
+    const bool fwd_ok = tgt_active && !guided && __float_as_uint(rec.w) == 1u;   // uniform in the group
 
     float nx = 0.f, ny = 0.f;
     bool status = false;
@@ -41,7 +43,7 @@ __global__ __launch_bounds__(256) void lk_fb_kernel(const LKFBParams p) {
         status = r.status;
     }
 
-    if (lg == 0 && tgt_active) {
+    if (lg == 0 && tgt_active && !guided) {
         if (fwd_ok) {
             const float2 pt = p.pts[feat];
             const float dx = nx - pt.x, dy = ny - pt.y;

@@ -78,9 +78,13 @@ __device__ __forceinline__ float group8_exact_sum_i64(long long v) {
 // c < 4 of the group is vector lane c -- columns c, c + 4, ... below SIMD_W = (win / 8) * 8, row by row --, lane 4 the scalar
 // accumulator over the remaining columns, lanes 5-7 idle.  Otherwise lane l owns columns l, l + 8, ... and the sums are exact integers.
 // ERR: also the level-0 patch error; without it only that error's bounds test, which decides the status like any other.
-template <bool X86, bool ERR, class LevelOf>
+// GUESS: the search of the top level starts at (guess_x, guess_y) * lscale instead of at the template's position -- OpenCV's
+// OPTFLOW_USE_INITIAL_FLOW, the guided pass of the search prepass (kernels_lk_search.hip); nothing else changes, and without it
+// the two arguments are not looked at.
+template <bool X86, bool ERR, bool GUESS = false, class LevelOf>
 __device__ __forceinline__ PlainLKResult plain_lk_pair(const LevelOf& level_of, float start_x, float start_y, int win, int lg, int max_level,
-                                                       int max_iters, double eps_sq, float min_eig_thr, uint2* const tm) {
+                                                       int max_iters, double eps_sq, float min_eig_thr, uint2* const tm,
+                                                       float guess_x = 0.f, float guess_y = 0.f) {
     const int simd_w = (win / 8) * 8;
     const float half_win = (float)(win - 1) * 0.5f;
     const float FLT_SCALE = 1.f / (float)(1 << 20);
@@ -96,8 +100,13 @@ __device__ __forceinline__ PlainLKResult plain_lk_pair(const LevelOf& level_of, 
         float px = start_x * lscale, py = start_y * lscale;
         float qx, qy;
         if (level == max_level) {
-            qx = px;
-            qy = py;
+            if constexpr (GUESS) {
+                qx = guess_x * lscale;
+                qy = guess_y * lscale;
+            } else {
+                qx = px;
+                qy = py;
+            }
         } else {
             qx = nx * 2.f;
             qy = ny * 2.f;

@@ -57,6 +57,11 @@ struct OpticalFlowOptions {
     // row is refined at level 0 under a 6-parameter warp of the window, so that it survives the roll and zoom between frames up
     // to 8 apart (Blender's tracker calls it the affine motion model).  Not together with normalize.
     bool affine_refinement = false;
+    // not in the reference: search prepass (include/polychase_hip.h: pc_lk_track_search).  0: off; 1..256: per (keypoint, target)
+    // pair an integer displacement within that many pixels is found by block matching, LK runs once more from it, and the row
+    // with the smaller patch error stays -- flow rows that survive fast pans and the long skips (Blender's tracker calls the
+    // search its prepass).  Not together with normalize.
+    int search_radius = 0;
     // not in the reference: gray conversion (include/polychase_hip.h: pc_gray_conversion).  channel_weights: nothing = the
     // reference's RGB2GRAY; (r, g, b), finite, >= 0, not all zero = the weights of the three channels in the gray plane that is
     // detected and tracked (Blender's tracker has R / G / B switches), for u8 and float frames.  float_transfer: "none" = float
@@ -73,6 +78,10 @@ inline void CheckOpticalFlowOptions(const OpticalFlowOptions& o) {
         throw std::invalid_argument("target_mask_margin must be -1 (off) or 0..31, got " + std::to_string(o.target_mask_margin));
     if (!(o.min_correlation >= 0.0 && o.min_correlation <= 1.0))   // a NaN fails
         throw std::invalid_argument("min_correlation must be in [0, 1] (0 = off), got " + std::to_string(o.min_correlation));
+    if (o.search_radius < 0 || o.search_radius > 256)
+        throw std::invalid_argument("search_radius must be 0 (off) or 1..256, got " + std::to_string(o.search_radius));
+    if (o.search_radius > 0 && o.normalize)
+        throw std::invalid_argument("search_radius assumes brightness constancy: it cannot be combined with normalize");
     if (o.affine_refinement && o.normalize)
         throw std::invalid_argument("affine_refinement assumes brightness constancy: it cannot be combined with normalize");
     if (o.channel_weights) {

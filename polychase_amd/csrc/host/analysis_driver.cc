@@ -435,6 +435,8 @@ static void RunAnalysis(const VideoInfo& video_info, FrameAccessorFunction frame
     if (pc_analyzer_set_min_correlation(eng.an, flow_options.min_correlation) != PC_OK) ThrowHip("pc_analyzer_set_min_correlation");
     // ... the brightness normalisation ...
     if (pc_analyzer_set_normalize(eng.an, flow_options.normalize ? 1 : 0) != PC_OK) ThrowHip("pc_analyzer_set_normalize");
+    // ... the search prepass (after the normalisation it excludes, like the refinement below) ...
+    if (pc_analyzer_set_search_radius(eng.an, flow_options.search_radius) != PC_OK) ThrowHip("pc_analyzer_set_search_radius");
     // ... the affine refinement (after the normalisation it excludes: a parked engine may hold either from its last run) ...
     if (pc_analyzer_set_affine_refinement(eng.an, flow_options.affine_refinement ? 1 : 0) != PC_OK) ThrowHip("pc_analyzer_set_affine_refinement");
     // ... the gray conversion, the default included (a per-run call: it may wait for the engine's idle streams) ...

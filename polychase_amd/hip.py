@@ -38,6 +38,7 @@ SYMBOLS = [
     "pc_lk_track_correlated", "pc_analyzer_set_min_correlation",
     "pc_lk_track_normalized", "pc_analyzer_set_normalize",
     "pc_lk_track_affine", "pc_analyzer_set_affine_refinement",
+    "pc_lk_track_search", "pc_analyzer_set_search_radius",
     "pc_lk_track", "pc_lk_track_filtered", "pc_lk_track_fb", "pc_lk_track_filtered_fb",
     "pc_analyzer_create", "pc_analyzer_destroy", "pc_analyzer_reset", "pc_analyzer_put_frame", "pc_analyzer_put_frame_f32",
     "pc_analyzer_has_frame", "pc_analyzer_frame_ingested",
@@ -209,6 +210,8 @@ def load():
                                          vp, vp, vp, vp, vp]
     L.pc_lk_track_affine.argtypes = [vp, vp, C.POINTER(vp), C.c_int, C.POINTER(FlowOptions), C.c_int, C.c_int, C.c_double, C.c_double, C.c_int,
                                      vp, vp, vp, vp, vp, vp, vp]
+    L.pc_lk_track_search.argtypes = [vp, vp, C.POINTER(vp), C.c_int, C.POINTER(FlowOptions), C.c_int, C.c_int, C.c_int, C.c_double, C.c_double,
+                                     C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.pc_analyzer_create.argtypes = [vp, C.c_int, C.c_int, C.POINTER(GfttOptions), C.POINTER(FlowOptions), C.c_int,
                                      C.c_int, C.POINTER(vp)]
     L.pc_analyzer_destroy.argtypes = [vp]
@@ -233,6 +236,7 @@ def load():
     L.pc_analyzer_set_min_correlation.argtypes = [vp, C.c_double]
     L.pc_analyzer_set_normalize.argtypes = [vp, C.c_int]
     L.pc_analyzer_set_affine_refinement.argtypes = [vp, C.c_int]
+    L.pc_analyzer_set_search_radius.argtypes = [vp, C.c_int]
     L.pc_peer_buffer_alloc.argtypes = [C.c_int, C.c_size_t, C.POINTER(vp)]
     L.pc_peer_buffer_free.argtypes = [C.c_int, vp]
     L.pc_peer_buffer_export.argtypes = [C.c_int, vp, C.c_char_p]
@@ -729,6 +733,32 @@ def lk_track_affine(ctx: Context, frame1: Frame, targets: list[Frame], affine: i
     return xy, st, err, bxy, bst, am, ast
 
 
+def lk_track_search(ctx: Context, frame1: Frame, targets: list[Frame], search_radius: int, affine: int = 0, normalize: int = 0,
+                    min_correlation: float = 0.0, fb_threshold: float = 0.0, margin: int = -1, opt: FlowOptions | None = None):
+    """search prepass of the forward rows (include/polychase_hip.h: pc_lk_track_search): with search_radius 1..256 one more launch
+    directly after the forward one finds an integer displacement per (keypoint, target) pair by block matching, runs LK once more
+    from it and keeps the record with the smaller patch error; with 0 it is lk_track_affine.  A radius with normalize 1 is refused.
+    -> next_xy [T,N,2], final status [T,N], err [T,N], back_xy [T,N,2], back_status [T,N], affine_m [T,N,4], affine_state [T,N],
+    search_d [T,N,2] int16 (level-0 pixels), search_state [T,N] (0 no displacement, 1 record replaced, 2 record kept)."""
+    opt = opt or flow_options()
+    n, t = frame1.num_keypoints, len(targets)
+    xy = np.zeros((t, n, 2), np.float32)
+    st = np.zeros((t, n), np.uint8)
+    err = np.zeros((t, n), np.float32)
+    bxy = np.zeros((t, n, 2), np.float32)
+    bst = np.zeros((t, n), np.uint8)
+    am = np.zeros((t, n, 4), np.float32)
+    ast = np.zeros((t, n), np.uint8)
+    sd = np.zeros((t, n, 2), np.int16)
+    sst = np.zeros((t, n), np.uint8)
+    arr = (C.c_void_p * t)(*[f._h for f in targets])
+    _check(load().pc_lk_track_search(ctx._h, frame1._h, arr, t, C.byref(opt), int(search_radius), int(affine), int(normalize),
+                                     float(min_correlation), float(fb_threshold), int(margin), xy.ctypes.data, st.ctypes.data,
+                                     err.ctypes.data, bxy.ctypes.data, bst.ctypes.data, am.ctypes.data, ast.ctypes.data, sd.ctypes.data,
+                                     sst.ctypes.data))
+    return xy, st, err, bxy, bst, am, ast, sd, sst
+
+
 def lk_track_filtered_fb(ctx: Context, frame1: Frame, targets: list[Frame], fb_threshold: float, opt: FlowOptions | None = None):
     """lk_track_filtered on the final status of the forward-backward check (pc_lk_track_filtered_fb)."""
     opt = opt or flow_options()
@@ -849,6 +879,11 @@ class Analyzer:
         """affine refinement for the jobs submitted from now on; 0 / False = off, 1 / True = on, refused while normalize is on
         (pc_analyzer_set_affine_refinement)"""
         _check(load().pc_analyzer_set_affine_refinement(self._h, int(affine)))
+
+    def set_search_radius(self, search_radius: int):
+        """search prepass for the jobs submitted from now on; 0 = off, 1..256 = the radius in pixels, refused while normalize is on
+        (pc_analyzer_set_search_radius)"""
+        _check(load().pc_analyzer_set_search_radius(self._h, int(search_radius)))
 
     def set_target_mask_margin(self, margin: int):
         """target-side masks for the frames put from now on: -1 = off, 0..31 = the margin (pc_analyzer_set_target_mask_margin);

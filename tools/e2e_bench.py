@@ -4,6 +4,7 @@ addon experiences), next to bench.py's HBM-resident number.  Not the headline me
 
   python tools/e2e_bench.py [--config c2|c3] [--frames 60] [--mask-fraction F [--mask-polygon] [--mask-outline N]
                              [--target-mask-margin R]] [--min-correlation V] [--normalize] [--affine]
+                             [--search-radius N] [--pan PX]
 
 Modes: frames as torch CUDA tensors / host numpy arrays (PCIe upload included), with and without the
 SQLite insert.  --mask-fraction F: every run takes detection_mask = a centred rectangle of the frame's aspect covering F of
@@ -22,7 +23,9 @@ then also report the mean number of flow rows per frame.  --min-correlation V: O
 of the per-class pass (class "lk_corr") -- rows whose reference and matched windows correlate below V are dropped (0, the default:
 off); the SQLite modes then report the mean number of flow rows per frame too.  --normalize: OpticalFlowOptions.normalize of every
 run, and of the per-class pass (the normalised launch is timed under class "lk").  --affine: OpticalFlowOptions.affine_refinement of
-every run, and of the per-class pass (the refinement launch is timed under class "lk" too: two launches per step)."""
+every run, and of the per-class pass (the refinement launch is timed under class "lk" too: two launches per step).  --search-radius N: OpticalFlowOptions.search_radius of
+every run, and of the per-class pass (the search launch is timed under class "lk" as well).  --pan PX: instead of the benchmark clip,
+frame t is frame 0 rolled by t * PX pixels in x -- a pan the plain search loses on the long skips."""
 import argparse
 import json
 import os
@@ -34,7 +37,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
-def per_class_ms(w, h, ml, frames, mask, steps=40, polygons=None, target_margin=-1, min_correlation=0.0, normalize=False, affine=False):
+def per_class_ms(w, h, ml, frames, mask, steps=40, polygons=None, target_margin=-1, min_correlation=0.0, normalize=False, affine=False, search_radius=0):
     """one pipelined pass (polychase_amd.pipeline.ClipAnalyzer) with every kernel class timed: 20 untimed steps, then `steps`"""
     from polychase_amd import hip
     from polychase_amd.pipeline import ClipAnalyzer
@@ -49,6 +52,7 @@ def per_class_ms(w, h, ml, frames, mask, steps=40, polygons=None, target_margin=
     an.an.set_min_correlation(min_correlation)
     an.an.set_normalize(normalize)
     an.an.set_affine_refinement(affine)
+    an.an.set_search_radius(search_radius)
     steps = min(steps, len(frames) - 9 - 29)
     an.run(range(9, 29), None)
     ctx.synchronize()
@@ -75,6 +79,8 @@ def main():
     ap.add_argument("--min-correlation", type=float, default=0.0)
     ap.add_argument("--normalize", action="store_true")
     ap.add_argument("--affine", action="store_true")
+    ap.add_argument("--search-radius", type=int, default=0)
+    ap.add_argument("--pan", type=int, default=0)
     a = ap.parse_args()
     import torch
     from polychase_amd import synth
@@ -84,6 +90,8 @@ def main():
     w, h, ml = {"c2": (1920, 1080, 3), "c3": (3840, 2160, 4)}[a.config]
     clip = synth.NoiseClip(w, h, max(a.frames, 30), device="cuda")
     dev = [clip.frame_torch(t) for t in range(a.frames)]
+    if a.pan:
+        dev = [torch.roll(dev[0], t * a.pan, 1).contiguous() for t in range(a.frames)]
     torch.cuda.synchronize()
     host = [f.cpu().numpy() for f in dev]
     fo = core.OpticalFlowOptions()
@@ -92,6 +100,7 @@ def main():
     fo.min_correlation = a.min_correlation
     fo.normalize = a.normalize
     fo.affine_refinement = a.affine
+    fo.search_radius = a.search_radius
     vi = core.VideoInfo(w, h, 1, a.frames)
     out = {}
     mask = None
@@ -133,10 +142,15 @@ def main():
         out["normalize"] = True
     if a.affine:
         out["affine_refinement"] = True
+    if a.search_radius:
+        out["search_radius"] = a.search_radius
+    if a.pan:
+        out["pan_px_per_frame"] = a.pan
     if a.frames >= 39:
         out["gpu_ms_per_step"] = per_class_ms(w, h, ml, dev, mask, polygons=polygons,
                                               target_margin=a.target_mask_margin if a.mask_fraction is not None else -1,
-                                              min_correlation=a.min_correlation, normalize=a.normalize, affine=a.affine)
+                                              min_correlation=a.min_correlation, normalize=a.normalize, affine=a.affine,
+                                              search_radius=a.search_radius)
     else:
         out["gpu_ms_per_step"] = {"skipped": "the per-class pass needs --frames 39 or more (20 untimed steps, then at least one)"}
     with tempfile.TemporaryDirectory() as td:

@@ -7,7 +7,7 @@ C ABI, then `pc_lk_track` is repeated: the LK class is timed with HIP events by 
 the average launch time and a checksum of the raw outputs (equal checksums <=> bit-identical
 results, the way kernel variants are compared: POLYCHASE_HIP_LIB selects the library).
 
-    python tools/lk_bench.py [--config c2|c3] [--reps 20] [--fb PX] [--min-correlation V] [--normalize] [--affine]
+    python tools/lk_bench.py [--config c2|c3] [--reps 20] [--fb PX] [--min-correlation V] [--normalize] [--affine] [--search-radius N]
 
 --fb PX also times the forward-backward check (pc_lk_track_fb, threshold PX): the forward launch and the backward launch of
 the same call, and as the baseline the same backward work through the calls that existed before it -- per target,
@@ -18,6 +18,8 @@ correlation launch of the same call, and the share of rows the check drops.
 launch measured above; with --fb PX the normalised backward launch beside it, against the plain backward launch.
 --affine also times the affine refinement (pc_lk_track_affine, affine = 1): its launch is timed under the forward launch's class, so
 the figure is the class total of the calls with the option minus that of the same number of calls without it.
+--search-radius N also times the search prepass (pc_lk_track_search, search_radius = N), the same way as --affine; --shift DX DY
+tracks into targets that are frame1 shifted by whole pixels (k * DX / 8, k * DY / 8 for the k-th skip), where the search has work.
 
 (Parity against the CPU oracle is the test suite's business: tests/test_gpu_parity.py, tests/test_fullsize_gpu.py.)
 """
@@ -152,6 +154,34 @@ def affine_timing(ctx, hip, f1, targets, fopt, reps, xy, st, err):
             "median_move_px": float(np.median(moved)) if accepted else None, "sha256": hsh.hexdigest()[:16]}
 
 
+def search_timing(ctx, hip, f1, targets, fopt, reps, radius, xy, st, err):
+    """forward + search launch of pc_lk_track_search against the forward launch alone (search_radius = 0) in alternating rounds; both
+    launches are timed under class "lk", so the search's time is the difference of the class totals"""
+    res = hip.lk_track_search(ctx, f1, targets, radius, opt=fopt)      # warm-up + the output that is compared
+    off = hip.lk_track_search(ctx, f1, targets, 0, opt=fopt)
+    assert np.array_equal(off[0], xy) and np.array_equal(off[1], st) and np.array_equal(off[2], err), "search_radius = 0 changed a forward value"
+    hsh = hashlib.sha256()
+    for a in res:
+        hsh.update(np.ascontiguousarray(a).tobytes())
+    ms, launches = {0: 0.0, 1: 0.0}, {0: 0, 1: 0}
+    ctx.enable_timing(["lk"])
+    for _ in range(reps):
+        for flag in (0, 1):
+            ctx.reset_timing()
+            again = hip.lk_track_search(ctx, f1, targets, radius * flag, opt=fopt)
+            t = ctx.timing()["lk"]
+            launches[flag] += t[0]
+            ms[flag] += t[1]
+    ctx.enable_timing(False)
+    assert all(np.array_equal(a, b) for a, b in zip(again, res)), "results vary between launches"
+    assert launches[0] == reps and launches[1] == 2 * reps, launches
+    fwd_ms, search_ms = ms[0] / reps, (ms[1] - ms[0]) / reps
+    state = res[8]
+    return {"search_radius": radius, "forward_ms": fwd_ms, "search_ms": search_ms, "search_over_forward": search_ms / fwd_ms if fwd_ms else None,
+            "pairs": int(state.size), "state_0": int((state == 0).sum()), "state_1": int((state == 1).sum()), "state_2": int((state == 2).sum()),
+            "forward_rows": int((st == 1).sum()), "rows_with_search": int((res[1] == 1).sum()), "sha256": hsh.hexdigest()[:16]}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", default="c2", choices=sorted(CONFIGS))
@@ -165,6 +195,9 @@ def main():
     ap.add_argument("--min-correlation", type=float, default=0.0, metavar="V", help="also time the minimum-correlation check at this threshold")
     ap.add_argument("--normalize", action="store_true", help="also time the brightness-normalised launch (with --fb: and its backward launch)")
     ap.add_argument("--affine", action="store_true", help="also time the affine refinement launch beside the forward launch")
+    ap.add_argument("--search-radius", type=int, default=0, metavar="N", help="also time the search prepass launch at this radius beside the forward launch")
+    ap.add_argument("--shift", type=int, nargs=2, default=None, metavar=("DX", "DY"),
+                    help="targets = frame1 rolled by whole pixels, (k DX / 8, k DY / 8) for skip k, instead of the clip's frames")
     args = ap.parse_args()
 
     import torch
@@ -180,7 +213,10 @@ def main():
     frames = {}
     for s in (0,) + SKIPS:
         f = hip.Frame(ctx, w, h, args.window, max_level)
-        f.set_rgb(clip.frame_torch(args.frame + s))
+        img = clip.frame_torch(args.frame + (0 if args.shift else s))
+        if args.shift and s:
+            img = torch.roll(img, (s * args.shift[1] // 8, s * args.shift[0] // 8), (0, 1))
+        f.set_rgb(img)
         frames[s] = f
     f1 = frames[0]
     f1.detect()
@@ -223,6 +259,8 @@ def main():
         out["normalize"] = norm_timing(ctx, hip, f1, targets, fopt, args.fb, args.reps, ms / max(1, launches), st)
     if args.affine:
         out["affine"] = affine_timing(ctx, hip, f1, targets, fopt, args.reps, xy, st, err)
+    if args.search_radius > 0:
+        out["search"] = search_timing(ctx, hip, f1, targets, fopt, args.reps, args.search_radius, xy, st, err)
     if args.min_correlation > 0:      # (before --fb: that one leaves other keypoints on the target frames)
         out["min_correlation"] = corr_timing(ctx, hip, f1, targets, fopt, args.min_correlation, args.reps, xy, st, err)
     if args.fb > 0:

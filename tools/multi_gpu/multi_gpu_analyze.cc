@@ -2,7 +2,7 @@
 //
 //     polychase_multi_gpu --gpus N --database clip.db [--width 1920 --height 1080 --frames 64 --max-level 3]
 //                         [--transport rccl|tcp] [--share-gpu] [--port 29611] [--piece-frames 16] [--frames-file clip.rgb]
-//                         [--fb-threshold PX] [--min-correlation V] [--normalize] [--affine]
+//                         [--fb-threshold PX] [--min-correlation V] [--normalize] [--affine] [--search-radius N]
 //                         [--channel-weights R G B] [--float-transfer none|srgb|gamma] [--float-gamma G] [--float-exposure STOPS]
 //
 // forks N ranks BEFORE the process touches HIP (one process per GPU; --share-gpu puts every rank on GPU 0, which RCCL
@@ -79,6 +79,7 @@ int RunRank(int rank, int world, int argc, char** argv) {
     fo.min_correlation = std::atof(Arg(argc, argv, "--min-correlation", "0"));           // minimum correlation, 0 = off
     fo.normalize = Flag(argc, argv, "--normalize");                                       // brightness-normalised LK, off by default
     fo.affine_refinement = Flag(argc, argv, "--affine");                                  // affine refinement, off by default
+    fo.search_radius = std::atoi(Arg(argc, argv, "--search-radius", "0"));                // search prepass, 0 = off, 1..256 pixels
     // the gray conversion: the weights of the three channels; the transfer curve of float frames travels with the options (the
     // frames of this tool are uint8, for which it does nothing)
     for (int i = 1; i < argc; i++)
@@ -148,7 +149,7 @@ int main(int argc, char** argv) {
     const int world = std::atoi(Arg(argc, argv, "--gpus", "1"));
     if (world < 1 || std::string(Arg(argc, argv, "--database", "")).empty()) {
         std::fprintf(stderr, "usage: %s --gpus N --database clip.db [--width W --height H --frames n --max-level L --transport rccl|tcp "
-                             "--share-gpu --port P --piece-frames k --frames-file raw.rgb --fb-threshold px --min-correlation v --normalize --affine "
+                             "--share-gpu --port P --piece-frames k --frames-file raw.rgb --fb-threshold px --min-correlation v --normalize --affine --search-radius n "
                              "--channel-weights r g b --float-transfer none|srgb|gamma --float-gamma g --float-exposure stops]\n", argv[0]);
         return 2;
     }
