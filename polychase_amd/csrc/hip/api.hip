@@ -1,6 +1,6 @@
 // api.hip -- implementation of the C ABI declared in include/polychase_hip.h: context, frames, the stage-level
-// detect / LK calls, and the helpers the analyzer shares (api_internal.hpp).  The pipelined analyzer lives in
-// api_analyzer.hip, the tracking / refinement entry points in api_tracker.hip.
+// detect calls, and the helpers the analyzer shares (api_internal.hpp).  The LK stage lives in api_lk.hip, the pipelined
+// analyzer in api_analyzer.hip, the tracking / refinement entry points in api_tracker.hip.
 //
 // Host-side orchestration only: HBM plane layout, stream ordering, read-backs, and the two pieces of
 // GoodFeaturesToTrack that are sequential by definition (greedy min-distance suppression,
@@ -409,269 +409,6 @@ int order_keypoints_spatially(pc_context* ctx, pc_frame* f, DevBuf<uint32_t>& hi
     PC_HIP(hist.ensure((size_t)pc::bin_num_tiles(f->w, f->h) + 1));
     pc::launch_spatial_bins(f->d_kps, n, nullptr, f->w, f->h, hist.p, f->d_perm, f->d_perm + f->perm_cap, ctx->work);
     f->perm_valid = true;
-    return PC_OK;
-}
-
-int check_lk_args(pc_context* ctx, const pc_frame* frame1, const pc_frame* const* targets, int n_targets,
-                  const pc_flow_options* opt) {
-    if (!ctx || !frame1 || !targets || !opt) return fail(PC_E_INVALID, "null argument");
-    if (n_targets < 1 || n_targets > PC_MAX_TARGETS) return fail(PC_E_INVALID, "n_targets must be in [1,%d]", PC_MAX_TARGETS);
-    if (frame1->n_kps < 0) return fail(PC_E_STATE, "frame1 has no keypoints (call pc_frame_detect or pc_frame_set_keypoints)");
-    if (opt->window_size != frame1->win) return fail(PC_E_INVALID, "window_size %d differs from the frame's pyramid padding %d", opt->window_size, frame1->win);
-    for (int t = 0; t < n_targets; t++) {
-        if (!targets[t]) return fail(PC_E_INVALID, "null target");
-        // cv::calcOpticalFlowPyrLK asserts equal level sizes/types (CV_Assert in lkpyramid.cpp)
-        if (targets[t]->w != frame1->w || targets[t]->h != frame1->h || targets[t]->win != frame1->win)
-            return fail(PC_E_INVALID, "target %d geometry differs from frame1", t);
-    }
-    return PC_OK;
-}
-
-int run_lk(pc_context* ctx, const pc_frame* frame1, const pc_frame* const* targets, int n_targets,
-           const pc_flow_options* opt, int set, int normalize) {
-    hipStream_t const lk_stream = ctx->lane_stream(set);
-    const int n = frame1->n_kps;
-    const size_t rows = (size_t)n * n_targets;
-    (void)rows;
-    PC_HIP(ctx->lk_rec[set].ensure(((size_t)n + 1) * pc::kRecStride));
-    ctx->lk_slot_of[set] = nullptr;
-    if (n == 0) return PC_OK;
-    pc::LKParams p;
-    std::memset(&p, 0, sizeof(p));
-    int max_level = std::min(opt->max_level, frame1->nlevels - 1);
-    for (int t = 0; t < n_targets; t++) max_level = std::min(max_level, targets[t]->nlevels - 1);
-    if (max_level < 0) max_level = 0;
-    for (int l = 0; l <= max_level; l++) {
-        p.src[l] = frame1->levels[l];
-        for (int t = 0; t < n_targets; t++) {
-            p.tgt[t][l] = targets[t]->levels[l].img;
-            p.tgt16[t][l] = targets[t]->levels[l].img16;
-        }
-    }
-    p.n_targets = n_targets;
-    p.max_level = max_level;
-    p.n = n;
-    p.pts = frame1->d_kps;
-    // visiting order: keypoints binned by image tile (they are stored by corner response); the analyzer
-    // prepares it together with the keypoints, the stage-level calls compute it here
-    if (frame1->perm_valid) {
-        p.perm = frame1->d_perm;
-        ctx->lk_slot_of[set] = frame1->d_perm + frame1->perm_cap;
-    } else {
-        PC_HIP(ctx->lk_perm.ensure((size_t)n * 2));
-        PC_HIP(ctx->lk_hist.ensure((size_t)pc::bin_num_tiles(frame1->w, frame1->h) + 1));
-        pc::launch_spatial_bins(frame1->d_kps, n, nullptr, frame1->w, frame1->h, ctx->lk_hist.p, ctx->lk_perm.p, ctx->lk_perm.p + n, lk_stream);
-        p.perm = ctx->lk_perm.p;
-        ctx->lk_slot_of[set] = ctx->lk_perm.p + n;
-    }
-    // TermCriteria clamps of calcOpticalFlowPyrLK
-    p.max_iters = std::min(std::max(opt->term_max_iters, 0), 100);
-    const double eps = std::min(std::max(opt->term_epsilon, 0.), 10.);
-    p.eps_sq = eps * eps;
-    p.min_eig_thr = (float)opt->min_eigen_threshold;
-    p.out_rec = ctx->lk_rec[set].p;
-    p.prof = nullptr;
-    p.x86_order = (ctx->arith & PC_ARITH_LK_X86_ORDER) ? 1 : 0;
-    p.x86_stats = ctx->lk_x86_stats.p;
-    p.gate = ctx->lk_gate_next ? ctx->lk_gate.p : nullptr;
-    p.gate_value = ctx->lk_gate_next;
-    ctx->lk_gate_next = 0;
-    if (pc::lk_profile_enabled()) {   // diagnostics build: 16 words per wavefront, the latest launch only
-        ctx->lk_prof_rows = (size_t)n / 2 + 1;
-        PC_HIP(ctx->lk_prof.ensure(ctx->lk_prof_rows * PC_LK_PROFILE_SLOTS));
-        PC_HIP(hipMemsetAsync(ctx->lk_prof.p, 0, ctx->lk_prof_rows * PC_LK_PROFILE_SLOTS * sizeof(unsigned long long), lk_stream));
-        p.prof = ctx->lk_prof.p;
-    }
-    ScopedTimer tm(ctx, PC_K_LK, lk_stream);
-    if (!(normalize ? pc::launch_lk_norm(p, frame1->win, lk_stream) : pc::launch_lk(p, frame1->win, lk_stream)))
-        return fail(PC_E_INVALID, "unsupported window size %d", frame1->win);
-    return PC_OK;
-}
-
-int check_fb_threshold(double fb_threshold) {
-    if (!(fb_threshold >= 0.0) || std::isinf(fb_threshold)) return fail(PC_E_INVALID, "fb_threshold must be finite and >= 0");
-    return PC_OK;
-}
-
-int run_lk_fb(pc_context* ctx, const pc_frame* frame1, const pc_frame* const* targets, int n_targets, const pc_flow_options* opt,
-              double fb_threshold, int set, float2* back_xy, uint8_t* back_status, int normalize, bool search) {
-    hipStream_t const lk_stream = ctx->lane_stream(set);
-    const int n = frame1->n_kps;
-    if (n == 0) return PC_OK;
-    pc::LKFBParams p;
-    std::memset(&p, 0, sizeof(p));
-    int max_level = std::min(opt->max_level, frame1->nlevels - 1);
-    for (int t = 0; t < n_targets; t++) max_level = std::min(max_level, targets[t]->nlevels - 1);
-    if (max_level < 0) max_level = 0;
-    for (int l = 0; l <= max_level; l++) {
-        p.f1[l] = frame1->levels[l];
-        for (int t = 0; t < n_targets; t++) {
-            p.timg[t][l] = targets[t]->levels[l].img;
-            p.tder[t][l] = targets[t]->levels[l].der;
-        }
-    }
-    p.n_targets = n_targets;
-    p.max_level = max_level;
-    p.n = n;
-    p.win = frame1->win;
-    p.pts = frame1->d_kps;
-    p.perm = frame1->perm_valid ? frame1->d_perm : ctx->lk_perm.p;   // the order run_lk visited the keypoints in
-    p.max_iters = std::min(std::max(opt->term_max_iters, 0), 100);
-    const double eps = std::min(std::max(opt->term_epsilon, 0.), 10.);
-    p.eps_sq = eps * eps;
-    p.min_eig_thr = (float)opt->min_eigen_threshold;
-    p.thr2 = (float)(fb_threshold * fb_threshold);
-    p.rec = ctx->lk_rec[set].p;
-    p.back_xy = back_xy;
-    p.back_status = back_status;
-    p.x86_order = (ctx->arith & PC_ARITH_LK_X86_ORDER) ? 1 : 0;
-    if (search) {
-        p.search_d = ctx->lk_search_d[set].p;
-        p.search_state = ctx->lk_search_state[set].p;
-    }
-    {
-        ScopedTimer tm(ctx, PC_K_LK_FB, lk_stream);
-        if (!(normalize ? pc::launch_lk_norm_fb(p, lk_stream) : pc::launch_lk_fb(p, lk_stream)))
-            return fail(PC_E_INVALID, "unsupported window size %d", frame1->win);
-    }
-    if (search) {
-        // the rows the search replaced: tracked back from q with the top level started at q - d
-        ScopedTimer tm(ctx, PC_K_LK_FB, lk_stream);
-        if (!pc::launch_lk_search_fb(p, lk_stream)) return fail(PC_E_INVALID, "unsupported window size %d", frame1->win);
-    }
-    return PC_OK;
-}
-
-int check_normalize(int normalize) {
-    if (normalize != 0 && normalize != 1) return fail(PC_E_INVALID, "normalize must be 0 or 1, got %d", normalize);
-    return PC_OK;
-}
-
-int check_affine(int affine, int normalize) {
-    if (affine != 0 && affine != 1) return fail(PC_E_INVALID, "affine must be 0 or 1, got %d", affine);
-    if (affine == 1 && normalize == 1) return fail(PC_E_INVALID, "affine refinement assumes brightness constancy: not together with normalize");
-    return PC_OK;
-}
-
-int run_lk_affine(pc_context* ctx, const pc_frame* frame1, const pc_frame* const* targets, int n_targets, const pc_flow_options* opt,
-                  int set, float4* affine_m, uint8_t* affine_state) {
-    hipStream_t const lk_stream = ctx->lane_stream(set);
-    const int n = frame1->n_kps;
-    if (n == 0) return PC_OK;
-    pc::AffineParams p;
-    std::memset(&p, 0, sizeof(p));
-    p.f1 = frame1->levels[0];
-    for (int t = 0; t < n_targets; t++) p.timg[t] = targets[t]->levels[0].img;
-    p.n_targets = n_targets;
-    p.n = n;
-    p.win = frame1->win;
-    // TermCriteria clamps of calcOpticalFlowPyrLK, as in run_lk
-    p.max_iters = std::min(std::max(opt->term_max_iters, 0), 100);
-    const double eps = std::min(std::max(opt->term_epsilon, 0.), 10.);
-    p.eps_sq = eps * eps;
-    p.pts = frame1->d_kps;
-    p.perm = frame1->perm_valid ? frame1->d_perm : ctx->lk_perm.p;   // the order run_lk visited the keypoints in
-    p.rec = ctx->lk_rec[set].p;
-    p.affine_m = affine_m;
-    p.affine_state = affine_state;
-    ScopedTimer tm(ctx, PC_K_LK, lk_stream);   // no class of its own: a job with the option shows two lk launches
-    if (!pc::launch_lk_affine(p, lk_stream)) return fail(PC_E_INVALID, "unsupported window size %d", frame1->win);
-    return PC_OK;
-}
-
-int check_search_radius(int search_radius, int normalize) {
-    if (search_radius < 0 || search_radius > 256) return fail(PC_E_INVALID, "search_radius must be 0 (off) or 1..256, got %d", search_radius);
-    if (search_radius > 0 && normalize == 1) return fail(PC_E_INVALID, "the search prepass assumes brightness constancy: not together with normalize");
-    return PC_OK;
-}
-
-int run_lk_search(pc_context* ctx, const pc_frame* frame1, const pc_frame* const* targets, int n_targets, const pc_flow_options* opt,
-                  int search_radius, int set) {
-    hipStream_t const lk_stream = ctx->lane_stream(set);
-    const int n = frame1->n_kps;
-    if (n == 0) return PC_OK;
-    const size_t rows = (size_t)n * n_targets;
-    PC_HIP(ctx->lk_search_d[set].ensure(rows));
-    PC_HIP(ctx->lk_search_state[set].ensure(rows));
-    pc::SearchParams p;
-    std::memset(&p, 0, sizeof(p));
-    int max_level = std::min(opt->max_level, frame1->nlevels - 1);   // as in run_lk
-    for (int t = 0; t < n_targets; t++) max_level = std::min(max_level, targets[t]->nlevels - 1);
-    if (max_level < 0) max_level = 0;
-    for (int l = 0; l <= max_level; l++) {
-        p.src[l] = frame1->levels[l];
-        for (int t = 0; t < n_targets; t++) p.tgt[t][l] = targets[t]->levels[l].img;
-    }
-    p.n_targets = n_targets;
-    p.max_level = max_level;
-    p.n = n;
-    p.win = frame1->win;
-    pc::search_level_radius(search_radius, max_level, &p.s, &p.r);
-    p.max_iters = std::min(std::max(opt->term_max_iters, 0), 100);
-    const double eps = std::min(std::max(opt->term_epsilon, 0.), 10.);
-    p.eps_sq = eps * eps;
-    p.min_eig_thr = (float)opt->min_eigen_threshold;
-    p.pts = frame1->d_kps;
-    p.perm = frame1->perm_valid ? frame1->d_perm : ctx->lk_perm.p;   // the order run_lk visited the keypoints in
-    p.rec = ctx->lk_rec[set].p;
-    p.search_d = ctx->lk_search_d[set].p;
-    p.search_state = ctx->lk_search_state[set].p;
-    ScopedTimer tm(ctx, PC_K_LK, lk_stream);   // no class of its own, as the affine refinement
-    if (!pc::launch_lk_search(p, lk_stream)) return fail(PC_E_INVALID, "unsupported window size %d", frame1->win);
-    return PC_OK;
-}
-
-int check_min_correlation(double min_correlation) {
-    if (!(min_correlation >= 0.0 && min_correlation <= 1.0)) return fail(PC_E_INVALID, "min_correlation must be in [0, 1]");   // a NaN fails
-    return PC_OK;
-}
-
-int run_lk_corr(pc_context* ctx, const pc_frame* frame1, const pc_frame* const* targets, int n_targets, double min_correlation, int set,
-                float* corr) {
-    hipStream_t const lk_stream = ctx->lane_stream(set);
-    const int n = frame1->n_kps;
-    if (n == 0) return PC_OK;
-    pc::CorrParams p;
-    std::memset(&p, 0, sizeof(p));
-    p.f1 = frame1->levels[0];
-    for (int t = 0; t < n_targets; t++) p.timg[t] = targets[t]->levels[0].img;
-    p.n_targets = n_targets;
-    p.n = n;
-    p.win = frame1->win;
-    p.drop = min_correlation > 0.0 ? 1 : 0;
-    p.pts = frame1->d_kps;
-    p.perm = frame1->perm_valid ? frame1->d_perm : ctx->lk_perm.p;   // the order run_lk visited the keypoints in
-    p.t2 = min_correlation * min_correlation;
-    p.rec = ctx->lk_rec[set].p;
-    p.corr = corr;
-    ScopedTimer tm(ctx, PC_K_LK_CORR, lk_stream);
-    if (!pc::launch_lk_corr(p, lk_stream)) return fail(PC_E_INVALID, "unsupported window size %d", frame1->win);
-    return PC_OK;
-}
-
-int check_target_margin(int margin, bool allow_off) {
-    if (margin < (allow_off ? -1 : 0) || margin > PC_TARGET_MASK_MAX_MARGIN)
-        return fail(PC_E_INVALID, "margin %d, %d..%d allowed", margin, allow_off ? -1 : 0, PC_TARGET_MASK_MAX_MARGIN);
-    return PC_OK;
-}
-
-int run_lk_target_mask(pc_context* ctx, const pc_frame* frame1, const uint8_t* const* plane, int n_targets, int set) {
-    const int n = frame1->n_kps;
-    pc::TargetMaskParams p;
-    std::memset(&p, 0, sizeof(p));
-    bool any = false;
-    for (int t = 0; t < n_targets; t++) {
-        p.plane[t] = plane[t];
-        any = any || plane[t] != nullptr;
-    }
-    if (!any || n <= 0) return PC_OK;
-    p.rec = ctx->lk_rec[set].p;
-    p.n = n;
-    p.n_targets = n_targets;
-    p.w = frame1->w;
-    p.h = frame1->h;
-    pc::launch_lk_target_mask(p, ctx->lane_stream(set));
-    PC_HIP(hipGetLastError());
     return PC_OK;
 }
 
@@ -1566,210 +1303,6 @@ int pc_frame_set_keypoints(pc_context* ctx, pc_frame* f, const float* xy, int n)
     f->n_kps = n;
     f->perm_valid = false;
     return PC_OK;
-}
-
-// ---------------------------------------------------------------------------------------------
-static int lk_track_impl(pc_context* ctx, const pc_frame* frame1, const pc_frame* const* targets, int n_targets,
-                         const pc_flow_options* opt, double fb_threshold, int margin, float* next_xy, uint8_t* status, float* err,
-                         float* back_xy, uint8_t* back_status, double min_correlation = 0.0, float* corr = nullptr, int normalize = 0,
-                         int affine = 0, float* affine_m = nullptr, uint8_t* affine_state = nullptr, int search_radius = 0,
-                         int16_t* search_d = nullptr, uint8_t* search_state = nullptr) {
-    int rc = check_target_margin(margin, true);   // first: a margin is refused whatever the handles
-    if (rc != PC_OK) return rc;
-    if ((rc = check_normalize(normalize)) != PC_OK) return rc;   // ... and so is a switch that is neither off nor on
-    if ((rc = check_search_radius(search_radius, normalize)) != PC_OK) return rc;
-    if ((rc = check_affine(affine, normalize)) != PC_OK) return rc;
-    if ((rc = check_min_correlation(min_correlation)) != PC_OK) return rc;   // ... and so is a correlation
-    if ((rc = check_lk_args(ctx, frame1, targets, n_targets, opt)) != PC_OK) return rc;
-    if (!next_xy || !status || !err) return fail(PC_E_INVALID, "null output");
-    if ((rc = check_fb_threshold(fb_threshold)) != PC_OK) return rc;
-    PC_HIP(hipSetDevice(ctx->device));
-    if (int jrc = join_prep(ctx)) return jrc;
-    rc = run_lk(ctx, frame1, targets, n_targets, opt, 0, normalize);
-    if (rc != PC_OK) return rc;
-    const size_t rows = (size_t)frame1->n_kps * n_targets;
-    if (rows > 0 && !search_radius) {
-        if (search_d) std::memset(search_d, 0, rows * sizeof(short2));
-        if (search_state) std::memset(search_state, 0, rows);
-    }
-    if (rows > 0 && search_radius) {
-        // search prepass: directly after the forward launch, in front of the refinement and of every check
-        if ((rc = run_lk_search(ctx, frame1, targets, n_targets, opt, search_radius, 0)) != PC_OK) return rc;
-        if (search_d) PC_HIP(hipMemcpyAsync(search_d, ctx->lk_search_d[0].p, rows * sizeof(short2), hipMemcpyDeviceToHost, ctx->stream));
-        if (search_state) PC_HIP(hipMemcpyAsync(search_state, ctx->lk_search_state[0].p, rows, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    if (rows > 0 && !affine) {
-        if (affine_m) std::memset(affine_m, 0, rows * sizeof(float4));
-        if (affine_state) std::memset(affine_state, 0, rows);
-    }
-    if (rows > 0 && affine) {
-        // affine refinement: directly after the forward launch, so that every check below judges the refined end points
-        if (affine_m) {
-            PC_HIP(ctx->lk_affine_m.ensure(rows));
-            PC_HIP(hipMemsetAsync(ctx->lk_affine_m.p, 0, rows * sizeof(float4), ctx->stream));
-        }
-        if (affine_state) {
-            PC_HIP(ctx->lk_affine_state.ensure(rows));
-            PC_HIP(hipMemsetAsync(ctx->lk_affine_state.p, 0, rows, ctx->stream));
-        }
-        rc = run_lk_affine(ctx, frame1, targets, n_targets, opt, 0, affine_m ? ctx->lk_affine_m.p : nullptr,
-                           affine_state ? ctx->lk_affine_state.p : nullptr);
-        if (rc != PC_OK) return rc;
-        if (affine_m) PC_HIP(hipMemcpyAsync(affine_m, ctx->lk_affine_m.p, rows * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream));
-        if (affine_state) PC_HIP(hipMemcpyAsync(affine_state, ctx->lk_affine_state.p, rows, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    if (margin >= 0 && rows > 0) {
-        // target-side masks: each masked target's plane -- choked into the context's scratch when there is a margin -- judges
-        // the rows that end in it, before the backward launch
-        const size_t plane_bytes = ((size_t)frame1->w * frame1->h + 15) & ~(size_t)15;
-        const uint8_t* plane[PC_MAX_TARGETS] = {};
-        int masked = 0;
-        for (int t = 0; t < n_targets; t++) masked += targets[t]->mask_on ? 1 : 0;
-        if (margin > 0 && masked > 0) PC_HIP(ctx->lk_choked.ensure((size_t)masked * plane_bytes + 16));
-        for (int t = 0, k = 0; t < n_targets; t++) {
-            if (!targets[t]->mask_on) continue;
-            plane[t] = targets[t]->d_mask;
-            if (margin > 0) {
-                uint8_t* const choked = ctx->lk_choked.p + (size_t)(k++) * plane_bytes;
-                pc::launch_mask_choke(targets[t]->d_mask, choked, frame1->w, frame1->h, margin, ctx->stream);
-                plane[t] = choked;
-            }
-        }
-        PC_HIP(hipGetLastError());
-        if ((rc = run_lk_target_mask(ctx, frame1, plane, n_targets)) != PC_OK) return rc;
-    }
-    if (rows > 0 && (min_correlation > 0.0 || corr)) {
-        // minimum correlation: after the mask test, before the backward launch
-        if (corr) PC_HIP(ctx->lk_corr.ensure(rows));
-        if ((rc = run_lk_corr(ctx, frame1, targets, n_targets, min_correlation, 0, corr ? ctx->lk_corr.p : nullptr)) != PC_OK) return rc;
-        if (corr) PC_HIP(hipMemcpyAsync(corr, ctx->lk_corr.p, rows * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-    }
-    const bool fb = fb_threshold > 0.0;
-    if (rows > 0 && !fb) {
-        if (back_xy) std::memset(back_xy, 0, rows * sizeof(float2));
-        if (back_status) std::memset(back_status, 0, rows);
-    }
-    if (rows > 0 && fb) {
-        if (back_xy) PC_HIP(ctx->lk_back_xy.ensure(rows));
-        if (back_status) PC_HIP(ctx->lk_back_status.ensure(rows));
-        rc = run_lk_fb(ctx, frame1, targets, n_targets, opt, fb_threshold, 0, back_xy ? ctx->lk_back_xy.p : nullptr,
-                       back_status ? ctx->lk_back_status.p : nullptr, normalize, search_radius > 0);
-        if (rc != PC_OK) return rc;
-        if (back_xy) PC_HIP(hipMemcpyAsync(back_xy, ctx->lk_back_xy.p, rows * sizeof(float2), hipMemcpyDeviceToHost, ctx->stream));
-        if (back_status) PC_HIP(hipMemcpyAsync(back_status, ctx->lk_back_status.p, rows, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    if (rows > 0) {
-        // the kernel's records are in visiting order: bring them into the [target][n] arrays of the call
-        PC_HIP(ctx->lk_cxy.ensure(rows));
-        PC_HIP(ctx->lk_cerr.ensure(rows));
-        PC_HIP(ctx->lk_ustatus.ensure(rows));
-        pc::launch_unpack_records(ctx->lk_rec[0].p, ctx->lk_slot_of[0], frame1->n_kps, n_targets, ctx->lk_cxy.p,
-                                  ctx->lk_ustatus.p, ctx->lk_cerr.p, ctx->stream);
-        PC_HIP(hipMemcpyAsync(next_xy, ctx->lk_cxy.p, rows * sizeof(float2), hipMemcpyDeviceToHost, ctx->stream));
-        PC_HIP(hipMemcpyAsync(status, ctx->lk_ustatus.p, rows, hipMemcpyDeviceToHost, ctx->stream));
-        PC_HIP(hipMemcpyAsync(err, ctx->lk_cerr.p, rows * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-    }
-    PC_HIP(hipStreamSynchronize(ctx->stream));
-    return PC_OK;
-}
-
-int pc_lk_track(pc_context* ctx, const pc_frame* frame1, const pc_frame* const* targets, int n_targets,
-                const pc_flow_options* opt, float* next_xy, uint8_t* status, float* err) {
-    return lk_track_impl(ctx, frame1, targets, n_targets, opt, 0.0, -1, next_xy, status, err, nullptr, nullptr);
-}
-
-int pc_lk_track_fb(pc_context* ctx, const pc_frame* frame1, const pc_frame* const* targets, int n_targets,
-                   const pc_flow_options* opt, double fb_threshold, float* next_xy, uint8_t* status, float* err,
-                   float* back_xy, uint8_t* back_status) {
-    return lk_track_impl(ctx, frame1, targets, n_targets, opt, fb_threshold, -1, next_xy, status, err, back_xy, back_status);
-}
-
-int pc_lk_track_masked(pc_context* ctx, const pc_frame* frame1, const pc_frame* const* targets, int n_targets,
-                       const pc_flow_options* opt, double fb_threshold, int margin, float* next_xy, uint8_t* status, float* err) {
-    return lk_track_impl(ctx, frame1, targets, n_targets, opt, fb_threshold, margin, next_xy, status, err, nullptr, nullptr);
-}
-
-int pc_lk_track_correlated(pc_context* ctx, const pc_frame* frame1, const pc_frame* const* targets, int n_targets,
-                           const pc_flow_options* opt, double min_correlation, double fb_threshold, int margin, float* next_xy,
-                           uint8_t* status, float* err, float* corr) {
-    return lk_track_impl(ctx, frame1, targets, n_targets, opt, fb_threshold, margin, next_xy, status, err, nullptr, nullptr,
-                         min_correlation, corr);
-}
-
-int pc_lk_track_normalized(pc_context* ctx, const pc_frame* frame1, const pc_frame* const* targets, int n_targets,
-                           const pc_flow_options* opt, int normalize, double min_correlation, double fb_threshold, int margin,
-                           float* next_xy, uint8_t* status, float* err, float* back_xy, uint8_t* back_status) {
-    return lk_track_impl(ctx, frame1, targets, n_targets, opt, fb_threshold, margin, next_xy, status, err, back_xy, back_status,
-                         min_correlation, nullptr, normalize);
-}
-
-int pc_lk_track_affine(pc_context* ctx, const pc_frame* frame1, const pc_frame* const* targets, int n_targets,
-                       const pc_flow_options* opt, int affine, int normalize, double min_correlation, double fb_threshold, int margin,
-                       float* next_xy, uint8_t* status, float* err, float* back_xy, uint8_t* back_status, float* affine_m,
-                       uint8_t* affine_state) {
-    return lk_track_impl(ctx, frame1, targets, n_targets, opt, fb_threshold, margin, next_xy, status, err, back_xy, back_status,
-                         min_correlation, nullptr, normalize, affine, affine_m, affine_state);
-}
-
-int pc_lk_track_search(pc_context* ctx, const pc_frame* frame1, const pc_frame* const* targets, int n_targets,
-                       const pc_flow_options* opt, int search_radius, int affine, int normalize, double min_correlation, double fb_threshold,
-                       int margin, float* next_xy, uint8_t* status, float* err, float* back_xy, uint8_t* back_status, float* affine_m,
-                       uint8_t* affine_state, int16_t* search_d, uint8_t* search_state) {
-    return lk_track_impl(ctx, frame1, targets, n_targets, opt, fb_threshold, margin, next_xy, status, err, back_xy, back_status,
-                         min_correlation, nullptr, normalize, affine, affine_m, affine_state, search_radius, search_d, search_state);
-}
-
-static int lk_track_filtered_impl(pc_context* ctx, const pc_frame* frame1, const pc_frame* const* targets, int n_targets,
-                                  const pc_flow_options* opt, double fb_threshold, uint32_t* src_indices, float* tgt_xy,
-                                  float* flow_err, int64_t* row_offset) {
-    int rc = check_lk_args(ctx, frame1, targets, n_targets, opt);
-    if (rc != PC_OK) return rc;
-    if (!row_offset) return fail(PC_E_INVALID, "null row_offset");
-    if ((rc = check_fb_threshold(fb_threshold)) != PC_OK) return rc;
-    PC_HIP(hipSetDevice(ctx->device));
-    if (int jrc = join_prep(ctx)) return jrc;
-    rc = run_lk(ctx, frame1, targets, n_targets, opt);
-    if (rc != PC_OK) return rc;
-    if (fb_threshold > 0.0 && (rc = run_lk_fb(ctx, frame1, targets, n_targets, opt, fb_threshold)) != PC_OK) return rc;
-    const int n = frame1->n_kps;
-    const size_t rows = (size_t)n * n_targets;
-    PC_HIP(ctx->lk_cxy.ensure(rows + 1));
-    PC_HIP(ctx->lk_cerr.ensure(rows + 1));
-    PC_HIP(ctx->lk_cidx.ensure(rows + 1));
-    if (n > pc::kCompactMaxKeypoints) return fail(PC_E_CAPACITY, "%d keypoints: more than the compaction handles (%d)", n, pc::kCompactMaxKeypoints);
-    const size_t scratch_cap_before = ctx->lk_block_counts[0].cap;   // a reallocation changes the capacity (the address may repeat)
-    PC_HIP(ctx->lk_block_counts[0].ensure(pc::compact_scratch_words(n, n_targets)));
-    PC_HIP(ctx->lk_row_offset.ensure(PC_MAX_TARGETS + 1));
-    PC_HIP(ctx->h_row_offset.ensure(PC_MAX_TARGETS + 1));
-    {
-        ScopedTimer t(ctx, PC_K_COMPACT);
-        pc::launch_compact(ctx->lk_rec[0].p, ctx->lk_slot_of[0], n, n_targets, ctx->lk_block_counts[0].p,
-                           ctx->lk_block_counts[0].cap != scratch_cap_before, ctx->lk_row_offset.p, ctx->lk_cidx.p, ctx->lk_cxy.p, ctx->lk_cerr.p, ctx->stream);
-    }
-    PC_HIP(hipMemcpyAsync(ctx->h_row_offset.p, ctx->lk_row_offset.p, (size_t)(n_targets + 1) * sizeof(long long), hipMemcpyDeviceToHost, ctx->stream));
-    PC_HIP(hipStreamSynchronize(ctx->stream));
-    for (int t = 0; t <= n_targets; t++) row_offset[t] = (int64_t)ctx->h_row_offset.p[t];
-    const size_t total = (size_t)row_offset[n_targets];
-    if (total > 0) {
-        if (!src_indices || !tgt_xy || !flow_err) return fail(PC_E_INVALID, "null output");
-        PC_HIP(hipMemcpyAsync(src_indices, ctx->lk_cidx.p, total * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-        PC_HIP(hipMemcpyAsync(tgt_xy, ctx->lk_cxy.p, total * sizeof(float2), hipMemcpyDeviceToHost, ctx->stream));
-        PC_HIP(hipMemcpyAsync(flow_err, ctx->lk_cerr.p, total * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-        PC_HIP(hipStreamSynchronize(ctx->stream));
-    }
-    return PC_OK;
-}
-
-int pc_lk_track_filtered(pc_context* ctx, const pc_frame* frame1, const pc_frame* const* targets, int n_targets,
-                         const pc_flow_options* opt, uint32_t* src_indices, float* tgt_xy, float* flow_err,
-                         int64_t* row_offset) {
-    return lk_track_filtered_impl(ctx, frame1, targets, n_targets, opt, 0.0, src_indices, tgt_xy, flow_err, row_offset);
-}
-
-int pc_lk_track_filtered_fb(pc_context* ctx, const pc_frame* frame1, const pc_frame* const* targets, int n_targets,
-                            const pc_flow_options* opt, double fb_threshold, uint32_t* src_indices, float* tgt_xy,
-                            float* flow_err, int64_t* row_offset) {
-    return lk_track_filtered_impl(ctx, frame1, targets, n_targets, opt, fb_threshold, src_indices, tgt_xy, flow_err, row_offset);
 }
 
 }  // extern "C"

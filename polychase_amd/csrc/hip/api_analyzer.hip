@@ -534,23 +534,13 @@ int pc_analyzer_submit(pc_analyzer* a, int32_t frame1, const int32_t* targets, i
             if (ctx->lk_gate_next == 0) ctx->lk_gate_next = ++ctx->lk_gate_seq;
             a->gate_armed = true;
         }
-        if ((rc = run_lk(ctx, s1->frame, tg, n_targets, &a->fopt, lane, a->normalize)) != PC_OK) return rc;
-        // search prepass: directly after the forward launch on the same lane, in front of the refinement and of every check
-        if (a->search_radius > 0 && (rc = run_lk_search(ctx, s1->frame, tg, n_targets, &a->fopt, a->search_radius, lane)) != PC_OK) return rc;
-        // affine refinement: the launch follows the forward one on the same lane; everything below judges the refined end points
-        if (a->affine && (rc = run_lk_affine(ctx, s1->frame, tg, n_targets, &a->fopt, lane)) != PC_OK) return rc;
-        // target-side masks: rows that end where their target's plane is off are dropped before the backward launch looks at them
-        {
-            const uint8_t* plane[PC_MAX_TARGETS] = {};
-            for (int t = 0; t < n_targets; t++)
-                if (tg[t]->target_margin >= 0) plane[t] = tg[t]->target_margin > 0 ? tg[t]->d_choked : tg[t]->d_mask;
-            if ((rc = run_lk_target_mask(ctx, s1->frame, plane, n_targets, lane)) != PC_OK) return rc;
-        }
-        // minimum correlation: rows whose windows correlate below the value are dropped before the backward launch looks at them
-        if (a->min_correlation > 0.0 && (rc = run_lk_corr(ctx, s1->frame, tg, n_targets, a->min_correlation, lane)) != PC_OK) return rc;
-        // forward-backward check: the backward launch follows on the same lane and rewrites the status of the records the
-        // compaction below filters; the gate is the forward launch's alone
-        if (a->fb_threshold > 0.0 && (rc = run_lk_fb(ctx, s1->frame, tg, n_targets, &a->fopt, a->fb_threshold, lane, nullptr, nullptr, a->normalize, a->search_radius > 0)) != PC_OK) return rc;
+        // the launches follow each other on the lane; the gate is the forward launch's alone, and the compaction below filters
+        // on the status the last pass leaves
+        LkPasses passes{.search_radius = a->search_radius, .affine = a->affine, .normalize = a->normalize,
+                        .min_correlation = a->min_correlation, .fb_threshold = a->fb_threshold};
+        for (int t = 0; t < n_targets; t++)
+            if (tg[t]->target_margin >= 0) passes.plane[t] = tg[t]->target_margin > 0 ? tg[t]->d_choked : tg[t]->d_mask;
+        if ((rc = run_lk_job(ctx, s1->frame, tg, n_targets, &a->fopt, passes, lane)) != PC_OK) return rc;
     }
     SlowSection ss_post("submit/post enqueue");
     uint8_t* const pack = ctx->lk_pack[lane].p;

@@ -1,4 +1,4 @@
-// api_internal.hpp -- helpers shared by the C-ABI translation units (api.hip, api_analyzer.hip, api_tracker.hip).
+// api_internal.hpp -- helpers shared by the C-ABI translation units (api.hip, api_lk.hip, api_analyzer.hip, api_tracker.hip).
 #pragma once
 
 #include <chrono>
@@ -72,45 +72,41 @@ int detect_finish(pc_context* ctx, pc_frame* f, const pc::GfttGrid& grid, const 
 // orders `stream` behind everything queued on the side streams so far
 int join_prep(pc_context* ctx);
 int order_keypoints_spatially(pc_context* ctx, pc_frame* f, DevBuf<uint32_t>& hist);
+// --- the LK stage (api_lk.hip) ---
+// argument checks of the stage calls and of the analyzer's setters, each refusing with the message the C ABI documents:
+// normalize and affine 0 or 1, search_radius 0 .. 256, affine and search not together with normalize, 0 <= min_correlation <= 1,
+// fb_threshold finite and >= 0, margin -1 (only with allow_off) .. 31
 int check_lk_args(pc_context* ctx, const pc_frame* frame1, const pc_frame* const* targets, int n_targets,
                   const pc_flow_options* opt);
-// LK launch into output set `set` on job lane `set` (0: the context's main stream); normalize (check_normalize: 0 or 1): the
-// brightness-normalised kernels (include/polychase_hip.h: pc_lk_track_normalized) instead, here and in run_lk_fb
 int check_normalize(int normalize);
-int run_lk(pc_context* ctx, const pc_frame* frame1, const pc_frame* const* targets, int n_targets, const pc_flow_options* opt,
-           int set = 0, int normalize = 0);
-// forward-backward check on the records run_lk has just left in set `set`, on the same lane (fb_threshold > 0);
-// back_xy / back_status: device arrays [n_targets][n] or null
 int check_fb_threshold(double fb_threshold);
-// search: run_lk_search has run on the set; the rows it replaced are tracked back by a launch of their own (timed under PC_K_LK_FB too)
-int run_lk_fb(pc_context* ctx, const pc_frame* frame1, const pc_frame* const* targets, int n_targets, const pc_flow_options* opt,
-              double fb_threshold, int set = 0, float2* back_xy = nullptr, uint8_t* back_status = nullptr, int normalize = 0,
-              bool search = false);
-// search prepass (include/polychase_hip.h: pc_lk_track_search) on the records run_lk has just left in set `set`, on the same lane,
-// before run_lk_affine and everything after it.  check_search_radius: 0 .. 256, and > 0 not together with normalize.  The
-// displacements and states stay in pc_context::lk_search_d / lk_search_state of the set, [target][n], for run_lk_fb
 int check_search_radius(int search_radius, int normalize);
-int run_lk_search(pc_context* ctx, const pc_frame* frame1, const pc_frame* const* targets, int n_targets, const pc_flow_options* opt,
-                  int search_radius, int set = 0);
-// affine refinement (include/polychase_hip.h: pc_lk_track_affine) of the records run_lk has just left in set `set`, on the same
-// lane, before run_lk_target_mask, run_lk_corr and run_lk_fb, which then judge the refined end points.  check_affine: 0 or 1, and
-// not together with normalize; affine_m / affine_state: device arrays [target][n], zeroed by the caller, or null
 int check_affine(int affine, int normalize);
-int run_lk_affine(pc_context* ctx, const pc_frame* frame1, const pc_frame* const* targets, int n_targets, const pc_flow_options* opt,
-                  int set = 0, float4* affine_m = nullptr, uint8_t* affine_state = nullptr);
-// minimum correlation (include/polychase_hip.h: pc_lk_track_correlated) on the records run_lk has just left in set `set`, on the
-// same lane, between run_lk_target_mask and run_lk_fb.  check_min_correlation: 0 <= v <= 1; run_lk_corr drops the rows below
-// min_correlation (0: none) and, with `corr` (device, [target][n]), writes the scores
 int check_min_correlation(double min_correlation);
-int run_lk_corr(pc_context* ctx, const pc_frame* frame1, const pc_frame* const* targets, int n_targets, double min_correlation, int set = 0,
-                float* corr = nullptr);
-// target-side masks (include/polychase_hip.h: pc_lk_track_masked).  check_target_margin: -1 (only with allow_off) .. 31;
-// ensure_choked_plane allocates pc_frame::d_choked (once); run_lk_target_mask drops, on the lane of set `set`, the records
-// run_lk has just left there that end where the plane of their target is off (plane[t] null: target t keeps its rows; all null:
-// nothing is enqueued)
 int check_target_margin(int margin, bool allow_off);
+// What follows the forward launch of an LK job (include/polychase_hip.h: pc_lk_track_search and the entry points before it).
+// Value-initialised: the forward launch only.  The side arrays are device memory, [target][n], null where nobody asks.
+struct LkPasses {
+    int search_radius;          // > 0: the search prepass
+    int affine;                 // 1: the affine refinement
+    int normalize;              // 1: the brightness-normalised forward and backward kernels
+    double min_correlation;     // > 0: rows that correlate below it are dropped
+    double fb_threshold;        // > 0: the forward-backward check
+    const uint8_t* plane[PC_MAX_TARGETS];   // target-side mask of target t (choked by the caller), null: it keeps its rows
+    float4* affine_m;           // the refinement's matrices and states
+    uint8_t* affine_state;
+    float* corr;                // the correlation scores: the pass then runs whatever min_correlation
+    float2* back_xy;            // the backward end points and status
+    uint8_t* back_status;
+};
+// Enqueues a whole job into output set `set` on job lane `set` (0: the context's main stream): the forward launch and the passes,
+// in the one order they have.  Afterwards pc_context::lk_rec / lk_slot_of of the set hold the records and the inverse visiting
+// order, and with a search radius lk_search_d / lk_search_state of the set the displacements and states.  Consumes
+// pc_context::lk_gate_next.  The arguments have passed the checks above
+int run_lk_job(pc_context* ctx, const pc_frame* frame1, const pc_frame* const* targets, int n_targets, const pc_flow_options* opt,
+               const LkPasses& passes, int set);
+// target-side masks: ensure_choked_plane allocates pc_frame::d_choked (once)
 int ensure_choked_plane(pc_frame* f);
-int run_lk_target_mask(pc_context* ctx, const pc_frame* frame1, const uint8_t* const* plane, int n_targets, int set = 0);
 // gray (+ pyramid) of a frame from u8 gray / u8 RGB / float32 RGB(A) pixels, host or device, on the work stream
 // `clear` (may be null): clear_words words zeroed in front of the frame's kernels (by the level-0 kernel where there is one)
 int set_image(pc_context* ctx, pc_frame* f, const uint8_t* src, size_t row_pitch, int on_device, int channels, int elem_size = 1,

@@ -223,7 +223,7 @@ struct pc_context {
     DevBuf<uint32_t> lk_gate;              // LKParams::gate of the analyzer's launches (one word)
     PinBuf<uint32_t> lk_gate_timed_out;    // raised by a gate kernel that gave up (its stream shares a hardware queue with the other lane)
     uint32_t lk_gate_seq = 0;              // value the latest gated launch stores
-    uint32_t lk_gate_next = 0;             // run_lk: value for the coming launch (0: not gated)
+    uint32_t lk_gate_next = 0;             // run_lk_job: value for the coming forward launch (0: not gated)
     bool lk_gate_on = true;                // POLYCHASE_LK_GATE=0 switches the gate off
     DevBuf<unsigned long long> lk_prof;    // pc_debug_lk_profile: 16 words per wavefront of the latest launch
     size_t lk_prof_rows = 0;

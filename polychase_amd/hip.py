@@ -610,21 +610,28 @@ class Frame:
         _check(load().pc_frame_set_keypoints(self.ctx._h, self._h, xy.ctypes.data, len(xy)))
 
 
-def lk_track(ctx: Context, frame1: Frame, targets: list[Frame], opt: FlowOptions | None = None):
-    """Raw LK outputs: next_xy [T,N,2], status [T,N], err [T,N]."""
+# the [T,N,...] output arrays of the pc_lk_track* calls: trailing shape and type by name
+_LK_OUT = {"xy": ((2,), np.float32), "st": ((), np.uint8), "err": ((), np.float32), "bxy": ((2,), np.float32), "bst": ((), np.uint8),
+           "corr": ((), np.float32), "am": ((4,), np.float32), "ast": ((), np.uint8), "sd": ((2,), np.int16), "sst": ((), np.uint8)}
+
+
+def _target_handles(targets):
+    return (C.c_void_p * len(targets))(*[f._h for f in targets])
+
+
+def _lk_call(symbol: str, ctx: Context, frame1: Frame, targets: list[Frame], opt, options: tuple, names: tuple):
+    """One pc_lk_track* call: `options` follow the flow options, then the zeroed output arrays `names` (None: a null pointer).
+    -> the arrays as a tuple, None where the name is."""
     opt = opt or flow_options()
     n, t = frame1.num_keypoints, len(targets)
-    xy = np.zeros((t, n, 2), np.float32)
-    st = np.zeros((t, n), np.uint8)
-    err = np.zeros((t, n), np.float32)
-    arr = (C.c_void_p * t)(*[f._h for f in targets])
-    _check(load().pc_lk_track(ctx._h, frame1._h, arr, t, C.byref(opt), xy.ctypes.data, st.ctypes.data,
-                              err.ctypes.data))
-    return xy, st, err
+    out = tuple(None if k is None else np.zeros((t, n) + _LK_OUT[k][0], _LK_OUT[k][1]) for k in names)
+    _check(getattr(load(), symbol)(ctx._h, frame1._h, _target_handles(targets), t, C.byref(opt), *options,
+                                   *[None if a is None else a.ctypes.data for a in out]))
+    return out
 
 
-def lk_track_filtered(ctx: Context, frame1: Frame, targets: list[Frame], opt: FlowOptions | None = None):
-    """status==1 rows per target: list of (src_indices u32 [M], tgt_xy f32 [M,2], err f32 [M])."""
+def _lk_call_filtered(symbol: str, ctx: Context, frame1: Frame, targets: list[Frame], opt, options: tuple):
+    """One pc_lk_track_filtered* call -> per target (src_indices u32 [M], tgt_xy f32 [M,2], err f32 [M])."""
     opt = opt or flow_options()
     n, t = frame1.num_keypoints, len(targets)
     rows = max(1, n * t)
@@ -632,45 +639,32 @@ def lk_track_filtered(ctx: Context, frame1: Frame, targets: list[Frame], opt: Fl
     xy = np.zeros((rows, 2), np.float32)
     err = np.zeros(rows, np.float32)
     off = np.zeros(t + 1, np.int64)
-    arr = (C.c_void_p * t)(*[f._h for f in targets])
-    _check(load().pc_lk_track_filtered(ctx._h, frame1._h, arr, t, C.byref(opt), idx.ctypes.data, xy.ctypes.data,
-                                       err.ctypes.data, off.ctypes.data))
-    out = []
-    for k in range(t):
-        a, b = int(off[k]), int(off[k + 1])
-        out.append((idx[a:b].copy(), xy[a:b].copy(), err[a:b].copy()))
-    return out
+    _check(getattr(load(), symbol)(ctx._h, frame1._h, _target_handles(targets), t, C.byref(opt), *options, idx.ctypes.data, xy.ctypes.data,
+                                   err.ctypes.data, off.ctypes.data))
+    return [(idx[a:b].copy(), xy[a:b].copy(), err[a:b].copy()) for a, b in zip(off[:-1].tolist(), off[1:].tolist())]
+
+
+def lk_track(ctx: Context, frame1: Frame, targets: list[Frame], opt: FlowOptions | None = None):
+    """Raw LK outputs: next_xy [T,N,2], status [T,N], err [T,N]."""
+    return _lk_call("pc_lk_track", ctx, frame1, targets, opt, (), ("xy", "st", "err"))
+
+
+def lk_track_filtered(ctx: Context, frame1: Frame, targets: list[Frame], opt: FlowOptions | None = None):
+    """status==1 rows per target: list of (src_indices u32 [M], tgt_xy f32 [M,2], err f32 [M])."""
+    return _lk_call_filtered("pc_lk_track_filtered", ctx, frame1, targets, opt, ())
 
 
 def lk_track_fb(ctx: Context, frame1: Frame, targets: list[Frame], fb_threshold: float, opt: FlowOptions | None = None):
     """lk_track with the forward-backward check (include/polychase_hip.h: pc_lk_track_fb): next_xy [T,N,2], final status
     [T,N], err [T,N], back_xy [T,N,2], back_status [T,N].  fb_threshold == 0: lk_track and zeros."""
-    opt = opt or flow_options()
-    n, t = frame1.num_keypoints, len(targets)
-    xy = np.zeros((t, n, 2), np.float32)
-    st = np.zeros((t, n), np.uint8)
-    err = np.zeros((t, n), np.float32)
-    bxy = np.zeros((t, n, 2), np.float32)
-    bst = np.zeros((t, n), np.uint8)
-    arr = (C.c_void_p * t)(*[f._h for f in targets])
-    _check(load().pc_lk_track_fb(ctx._h, frame1._h, arr, t, C.byref(opt), float(fb_threshold), xy.ctypes.data, st.ctypes.data,
-                                 err.ctypes.data, bxy.ctypes.data, bst.ctypes.data))
-    return xy, st, err, bxy, bst
+    return _lk_call("pc_lk_track_fb", ctx, frame1, targets, opt, (float(fb_threshold),), ("xy", "st", "err", "bxy", "bst"))
 
 
 def lk_track_masked(ctx: Context, frame1: Frame, targets: list[Frame], fb_threshold: float, margin: int, opt: FlowOptions | None = None):
     """lk_track_fb without the back outputs, plus the target-side mask test (include/polychase_hip.h: pc_lk_track_masked): a row
     whose end point lies where the choked mask of its target is off gets status 0; a target without a mask keeps its rows.
     margin -1: lk_track_fb.  -> next_xy [T,N,2], final status [T,N], err [T,N]."""
-    opt = opt or flow_options()
-    n, t = frame1.num_keypoints, len(targets)
-    xy = np.zeros((t, n, 2), np.float32)
-    st = np.zeros((t, n), np.uint8)
-    err = np.zeros((t, n), np.float32)
-    arr = (C.c_void_p * t)(*[f._h for f in targets])
-    _check(load().pc_lk_track_masked(ctx._h, frame1._h, arr, t, C.byref(opt), float(fb_threshold), int(margin), xy.ctypes.data,
-                                     st.ctypes.data, err.ctypes.data))
-    return xy, st, err
+    return _lk_call("pc_lk_track_masked", ctx, frame1, targets, opt, (float(fb_threshold), int(margin)), ("xy", "st", "err"))
 
 
 def lk_track_correlated(ctx: Context, frame1: Frame, targets: list[Frame], min_correlation: float, fb_threshold: float = 0.0,
@@ -679,16 +673,8 @@ def lk_track_correlated(ctx: Context, frame1: Frame, targets: list[Frame], min_c
     and matched windows correlate below min_correlation gets status 0; 0 = no filter.  corr=True also returns the scores (0 where
     the record reached the pass with status 0); corr=False with min_correlation 0 is lk_track_masked.
     -> next_xy [T,N,2], final status [T,N], err [T,N], corr [T,N] or None."""
-    opt = opt or flow_options()
-    n, t = frame1.num_keypoints, len(targets)
-    xy = np.zeros((t, n, 2), np.float32)
-    st = np.zeros((t, n), np.uint8)
-    err = np.zeros((t, n), np.float32)
-    sc = np.zeros((t, n), np.float32) if corr else None
-    arr = (C.c_void_p * t)(*[f._h for f in targets])
-    _check(load().pc_lk_track_correlated(ctx._h, frame1._h, arr, t, C.byref(opt), float(min_correlation), float(fb_threshold), int(margin),
-                                         xy.ctypes.data, st.ctypes.data, err.ctypes.data, sc.ctypes.data if corr else None))
-    return xy, st, err, sc
+    return _lk_call("pc_lk_track_correlated", ctx, frame1, targets, opt, (float(min_correlation), float(fb_threshold), int(margin)),
+                    ("xy", "st", "err", "corr" if corr else None))
 
 
 def lk_track_normalized(ctx: Context, frame1: Frame, targets: list[Frame], normalize: int = 1, min_correlation: float = 0.0,
@@ -697,17 +683,8 @@ def lk_track_normalized(ctx: Context, frame1: Frame, targets: list[Frame], norma
     backward launch where fb_threshold > 0, track g (J - mean J) against (I - mean I); with 0 it is lk_track_correlated without
     scores plus the back outputs of lk_track_fb.
     -> next_xy [T,N,2], final status [T,N], err [T,N], back_xy [T,N,2], back_status [T,N]."""
-    opt = opt or flow_options()
-    n, t = frame1.num_keypoints, len(targets)
-    xy = np.zeros((t, n, 2), np.float32)
-    st = np.zeros((t, n), np.uint8)
-    err = np.zeros((t, n), np.float32)
-    bxy = np.zeros((t, n, 2), np.float32)
-    bst = np.zeros((t, n), np.uint8)
-    arr = (C.c_void_p * t)(*[f._h for f in targets])
-    _check(load().pc_lk_track_normalized(ctx._h, frame1._h, arr, t, C.byref(opt), int(normalize), float(min_correlation), float(fb_threshold),
-                                         int(margin), xy.ctypes.data, st.ctypes.data, err.ctypes.data, bxy.ctypes.data, bst.ctypes.data))
-    return xy, st, err, bxy, bst
+    return _lk_call("pc_lk_track_normalized", ctx, frame1, targets, opt,
+                    (int(normalize), float(min_correlation), float(fb_threshold), int(margin)), ("xy", "st", "err", "bxy", "bst"))
 
 
 def lk_track_affine(ctx: Context, frame1: Frame, targets: list[Frame], affine: int = 1, normalize: int = 0, min_correlation: float = 0.0,
@@ -717,20 +694,9 @@ def lk_track_affine(ctx: Context, frame1: Frame, targets: list[Frame], affine: i
     refined rows; with 0 it is lk_track_normalized.  affine 1 with normalize 1 is refused.
     -> next_xy [T,N,2], final status [T,N], err [T,N], back_xy [T,N,2], back_status [T,N], affine_m [T,N,4] (m11, m12, m21, m22),
     affine_state [T,N] (0 not run, 1 accepted, 2 left unchanged)."""
-    opt = opt or flow_options()
-    n, t = frame1.num_keypoints, len(targets)
-    xy = np.zeros((t, n, 2), np.float32)
-    st = np.zeros((t, n), np.uint8)
-    err = np.zeros((t, n), np.float32)
-    bxy = np.zeros((t, n, 2), np.float32)
-    bst = np.zeros((t, n), np.uint8)
-    am = np.zeros((t, n, 4), np.float32)
-    ast = np.zeros((t, n), np.uint8)
-    arr = (C.c_void_p * t)(*[f._h for f in targets])
-    _check(load().pc_lk_track_affine(ctx._h, frame1._h, arr, t, C.byref(opt), int(affine), int(normalize), float(min_correlation),
-                                     float(fb_threshold), int(margin), xy.ctypes.data, st.ctypes.data, err.ctypes.data, bxy.ctypes.data,
-                                     bst.ctypes.data, am.ctypes.data, ast.ctypes.data))
-    return xy, st, err, bxy, bst, am, ast
+    return _lk_call("pc_lk_track_affine", ctx, frame1, targets, opt,
+                    (int(affine), int(normalize), float(min_correlation), float(fb_threshold), int(margin)),
+                    ("xy", "st", "err", "bxy", "bst", "am", "ast"))
 
 
 def lk_track_search(ctx: Context, frame1: Frame, targets: list[Frame], search_radius: int, affine: int = 0, normalize: int = 0,
@@ -740,42 +706,14 @@ def lk_track_search(ctx: Context, frame1: Frame, targets: list[Frame], search_ra
     from it and keeps the record with the smaller patch error; with 0 it is lk_track_affine.  A radius with normalize 1 is refused.
     -> next_xy [T,N,2], final status [T,N], err [T,N], back_xy [T,N,2], back_status [T,N], affine_m [T,N,4], affine_state [T,N],
     search_d [T,N,2] int16 (level-0 pixels), search_state [T,N] (0 no displacement, 1 record replaced, 2 record kept)."""
-    opt = opt or flow_options()
-    n, t = frame1.num_keypoints, len(targets)
-    xy = np.zeros((t, n, 2), np.float32)
-    st = np.zeros((t, n), np.uint8)
-    err = np.zeros((t, n), np.float32)
-    bxy = np.zeros((t, n, 2), np.float32)
-    bst = np.zeros((t, n), np.uint8)
-    am = np.zeros((t, n, 4), np.float32)
-    ast = np.zeros((t, n), np.uint8)
-    sd = np.zeros((t, n, 2), np.int16)
-    sst = np.zeros((t, n), np.uint8)
-    arr = (C.c_void_p * t)(*[f._h for f in targets])
-    _check(load().pc_lk_track_search(ctx._h, frame1._h, arr, t, C.byref(opt), int(search_radius), int(affine), int(normalize),
-                                     float(min_correlation), float(fb_threshold), int(margin), xy.ctypes.data, st.ctypes.data,
-                                     err.ctypes.data, bxy.ctypes.data, bst.ctypes.data, am.ctypes.data, ast.ctypes.data, sd.ctypes.data,
-                                     sst.ctypes.data))
-    return xy, st, err, bxy, bst, am, ast, sd, sst
+    return _lk_call("pc_lk_track_search", ctx, frame1, targets, opt,
+                    (int(search_radius), int(affine), int(normalize), float(min_correlation), float(fb_threshold), int(margin)),
+                    ("xy", "st", "err", "bxy", "bst", "am", "ast", "sd", "sst"))
 
 
 def lk_track_filtered_fb(ctx: Context, frame1: Frame, targets: list[Frame], fb_threshold: float, opt: FlowOptions | None = None):
     """lk_track_filtered on the final status of the forward-backward check (pc_lk_track_filtered_fb)."""
-    opt = opt or flow_options()
-    n, t = frame1.num_keypoints, len(targets)
-    rows = max(1, n * t)
-    idx = np.zeros(rows, np.uint32)
-    xy = np.zeros((rows, 2), np.float32)
-    err = np.zeros(rows, np.float32)
-    off = np.zeros(t + 1, np.int64)
-    arr = (C.c_void_p * t)(*[f._h for f in targets])
-    _check(load().pc_lk_track_filtered_fb(ctx._h, frame1._h, arr, t, C.byref(opt), float(fb_threshold), idx.ctypes.data,
-                                          xy.ctypes.data, err.ctypes.data, off.ctypes.data))
-    out = []
-    for k in range(t):
-        a, b = int(off[k]), int(off[k + 1])
-        out.append((idx[a:b].copy(), xy[a:b].copy(), err[a:b].copy()))
-    return out
+    return _lk_call_filtered("pc_lk_track_filtered_fb", ctx, frame1, targets, opt, (float(fb_threshold),))
 
 
 class Analyzer:
