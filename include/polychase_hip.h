@@ -511,6 +511,49 @@ int pc_lk_track_search(pc_context* ctx, const pc_frame* frame1, const pc_frame* 
                        double fb_threshold, int margin, float* next_xy, uint8_t* status, float* err, float* back_xy,
                        uint8_t* back_status, float* affine_m, uint8_t* affine_state, int16_t* search_d, uint8_t* search_state);
 
+/* ---- masked windows (Blender's use_mask; not in the reference, off by default) ----
+ * A detection mask decides which keypoints exist and a target-side mask which rows survive; neither decides what a row's window
+ * looks at.  A keypoint inside the mask but closer than half a window to its outline builds its template partly from pixels outside
+ * the mask -- another layer, moving differently -- and its translational fit is a compromise between two motions.  With
+ * mask_windows = 1 the template pixels outside the mask carry no weight.  on(x, y): the frame's mask byte is non-zero
+ * (pc_frame_set_mask / _polygons); a frame without a mask on has no weights and is tracked exactly as without the option.
+ *   weight planes   one per pyramid level.  M_0 = on.  For level l >= 1 of size (w_l, h_l): M_l(x, y) = the AND over dx, dy in
+ *              -2 .. 2 of M_{l-1}(r(2x + dx, w_{l-1}), r(2y + dy, h_{l-1})), r the BORDER_REFLECT_101 index map -- exactly the pixels
+ *              pyrDown read to make that pixel: a level pixel is on only if no off pixel contributed to it.  W_l(x, y) = the AND of
+ *              M_l over |dx|, |dy| <= 1, the Scharr support; neighbours outside the level count as on, and every position outside
+ *              the level (the padding) is on (kernels_mask.hip; pc_frame_download_window_weights).
+ *   sample weight   the template sample (x, y) of the window with integer origin (ipx, ipy) reads the four taps (ipx + x + {0, 1},
+ *              ipy + y + {0, 1}); it is on iff all four are on in W_l.  The bilinear weights do not enter the test.  n_on = the
+ *              number of on samples of the window.
+ *   the pass   the plain pass -- pco_lk of the oracle, lk_plain.hpp's plain_lk_pair -- with four changes, everything else the same
+ *              fp32 and integer expression in the same order, canonical or PC_ARITH_LK_X86_ORDER:
+ *              1. ix and iy of an off sample are 0 (ival is kept), so off samples add exact zeros to the A and b sums in either
+ *                 accumulation order;
+ *              2. if 4 * n_on < win * win the level fails like the min-eig test: status 0 at level 0, level skipped otherwise;
+ *              3. the min-eig divisor is (float)(2 * n_on);
+ *              4. the level-0 patch error sums |diff| over the on samples only and divides by (float)(32 * n_on).
+ *              With every sample on every expression is the plain pass's: a window that touches no off sample gives its bits.
+ *   which weights   those of the template image: frame1's in the forward pass; in the backward pass of the forward-backward check
+ *              the target's, if the target has a mask on -- otherwise the plain backward pass.
+ * A keypoint is TOUCHED when, at some level that passes the bounds test, its template window has an off sample.  One more launch
+ * directly after the forward launch tracks the touched keypoints again under the rule and overwrites their records
+ * (kernels_lk_wmask.hip; timed under PC_K_LK); the records of every other keypoint are the product kernel's, bit for bit.  With
+ * fb_threshold > 0 and a masked target the weighted backward launch replaces the plain one (timed under PC_K_LK_FB).
+ * fb_threshold and the target-side margin compose with the option.  normalize, the affine refinement, the search prepass and a
+ * minimum correlation do not weight their windows: an analyzer or a job with one of them and mask_windows = 1 is PC_E_INVALID,
+ * before anything is launched, and so is a mask_windows other than 0 or 1.  (The rule restated in numpy:
+ * tests/lk_window_mask_ref.py.)
+ * pc_lk_track_window_masked: mask_windows == 0 is exactly pc_lk_track_masked plus the back outputs of pc_lk_track_fb (nothing
+ * else is enqueued).  touched ([N] bytes, may be NULL) receives 1 for the touched keypoints, 0 elsewhere and everywhere when the
+ * option is off or frame1 has no mask on. */
+int pc_lk_track_window_masked(pc_context* ctx, const pc_frame* frame1, const pc_frame* const* targets, int n_targets,
+                              const pc_flow_options* opt, int mask_windows, double fb_threshold, int margin, float* next_xy,
+                              uint8_t* status, float* err, float* back_xy, uint8_t* back_status, uint8_t* touched);
+/* tests, debugging: the weight plane W_level of the frame's current mask with its padding, (w_l + 2 win) x (h_l + 2 win) bytes,
+ * 255 / 0, the layout of pc_frame_download_level.  Makes the planes if the mask changed since they were made.  PC_E_STATE when the
+ * frame has no mask on, PC_E_INVALID for a level the frame does not have. */
+int pc_frame_download_window_weights(pc_context* ctx, pc_frame* f, int level, uint8_t* out_padded);
+
 /* ---- analyzer: the pipelined per-clip engine behind GenerateOpticalFlowDatabase ----
  * (cpp/opticalflow.cc:209-321).  Holds a ring of resident frames (the reference's 17-frame
  * SequentialWrapper cache, cpp/opticalflow_thread.h:34-79, generalised), builds every frame's gray
@@ -639,6 +682,17 @@ int pc_analyzer_set_mask_polygons(pc_analyzer* a, const float* xy, const int32_t
  * enqueues what it always did.  pc_analyzer_reset keeps the margin (like the forward-backward threshold) and clears the mask.
  * Null analyzer, or a margin outside -1..PC_TARGET_MASK_MAX_MARGIN: PC_E_INVALID. */
 int pc_analyzer_set_target_mask_margin(pc_analyzer* a, int margin);
+/* Masked windows (pc_lk_track_window_masked) for the frames put and the jobs submitted FROM NOW ON: 0 = off (the default), 1 = on.
+ * While it is on and a mask is in force (pc_analyzer_set_mask / _polygons), every frame put takes the mask into its slot's plane
+ * whatever will_detect is -- as under a target-side margin, and as little a reason for its detection to read the mask -- and gets
+ * its weight planes, made on the preparation stream in front of the frame's "image ready" event.  A job submitted while it is on
+ * runs the masked launch behind its forward launch when frame1 was put that way, and, with a forward-backward threshold, the
+ * weighted backward launch when a target was; a frame put without a mask in force, or with the option off, has no weights.  The
+ * planes are allocated by the first call that needs them: an analyzer that never sees the switch together with a mask allocates
+ * and enqueues what it always did.  pc_analyzer_reset keeps the switch and clears the mask.  A value other than 0 or 1, a null
+ * analyzer, or 1 while normalize, the affine refinement, a search radius or a minimum correlation is set: PC_E_INVALID;
+ * pc_analyzer_submit refuses a job while the switch and one of them are set (they may have been switched on afterwards). */
+int pc_analyzer_set_mask_windows(pc_analyzer* a, int mask_windows);
 /* Wait for the oldest submitted job.  Pointers stay valid until the job slot is reused, i.e. for
  * the next max_jobs-1 submits. */
 int pc_analyzer_collect(pc_analyzer* a, pc_frame_result* out);

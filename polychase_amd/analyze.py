@@ -57,7 +57,7 @@ def log_capacity(n_frames: int, width: int, height: int, n_targets: int = 8, key
 
 def analyze(width: int, height: int, first_frame: int, num_frames: int, frame_accessor, database_path: str,
             detector_options=None, flow_options=None, callback=None, group=None, device=None, piece_frames: int = 16,
-            keypoints_per_frame: int | None = None):
+            keypoints_per_frame: int | None = None, detection_mask=None):
     """Analyze frames first_frame .. first_frame + num_frames - 1 with all ranks of `group` (default: the world; one rank
     when torch.distributed is not initialised) and store the flow database at `database_path` (written by rank 0).
     frame_accessor(frame_id) -> H x W x 3 uint8 (numpy, or a torch tensor on this rank's GPU), or float32 H x W x 3|4.
@@ -67,6 +67,8 @@ def analyze(width: int, height: int, first_frame: int, num_frames: int, frame_ac
     travel to rank 0 over RCCL in frame order (csrc/host/multi_gpu.cc) and are stored as they arrive.  GPU and
     host memory are bounded by the pieces in flight, whatever the length of the clip.  An existing database must hold
     the same analysis (write_optical_flow_records refuses other keypoints).
+    detection_mask: as for polychase_core.generate_optical_flow_database (an array, a PolygonMask, a dict or a callable); every
+    rank passes the same one.
     Returns a dict of per-phase seconds and counts (on every rank)."""
     import torch
     import torch.distributed as dist
@@ -85,7 +87,7 @@ def analyze(width: int, height: int, first_frame: int, num_frames: int, frame_ac
     out = {"rank": rank, "world": world, "shard": [begin, end], "frames": end - begin}
     if world == 1:
         st = core.generate_optical_flow_shard(vi, frame_accessor, callback, database_path, begin, end, detector_options=gopt,
-                                              flow_options=fopt)["stats"]
+                                              flow_options=fopt, detection_mask=detection_mask)["stats"]
         t1 = time.perf_counter()
         out.update(seconds_analysis=t1 - t0, seconds_stitch=0.0, seconds_database=st.seconds_db, seconds_total=t1 - t0, log_bytes=0,
                    frames_processed=st.frames_processed, cancelled=False,
@@ -99,7 +101,7 @@ def analyze(width: int, height: int, first_frame: int, num_frames: int, frame_ac
         vi, frame_accessor, callback, database_path, world, rank, master_addr=os.environ.get("MASTER_ADDR", "127.0.0.1"), master_port=port,
         device=dev.index or 0, piece_frames=piece_frames,
         transport="tcp" if share_gpu else "rccl",     # (RCCL refuses two ranks on one device: the one-GPU testing aid moves the pieces over TCP)
-        keypoints_per_frame=keypoints_per_frame or 0, detector_options=gopt, flow_options=fopt)
+        keypoints_per_frame=keypoints_per_frame or 0, detector_options=gopt, flow_options=fopt, detection_mask=detection_mask)
     st = res["stats"]
     out.update(seconds_analysis=res["seconds_analysis"], seconds_stitch=res["seconds_blocked"], seconds_database=st.seconds_db,
                log_bytes=int(res["bytes_moved"]), frames_processed=st.frames_processed, pieces=int(res["pieces"]), cancelled=bool(res["cancelled"]),
@@ -157,6 +159,11 @@ def main(argv=None) -> int:
     ap.add_argument("--float-exposure", type=float, default=0.0, metavar="STOPS", help="gain in stops in front of the transfer curve, -16..16")
     ap.add_argument("--search-radius", type=int, default=0, metavar="N",
                     help="search prepass: block matching within N pixels (1..256) in front of a second LK pass, for fast pans and the long skips (0: off; not with --normalize)")
+    ap.add_argument("--mask-polygon", type=float, nargs="+", default=None, metavar="X Y",
+                    help="detection mask: one closed polygon, x y x y ... in pixels (at least three vertices), rasterised on the GPU")
+    ap.add_argument("--mask-windows", action="store_true",
+                    help="masked windows: template pixels outside the mask carry no weight, so keypoints near the outline follow the "
+                         "masked object (off by default; needs --mask-polygon; not with --normalize, --affine, --search-radius, --min-correlation)")
     ap.add_argument("--piece-frames", type=int, default=16, help="frames per piece of the record log handed to rank 0")
     ap.add_argument("--gpus", type=int, default=0, help="launch this many ranks (one per GPU) of this command")
     args = ap.parse_args(argv)
@@ -210,6 +217,14 @@ def main(argv=None) -> int:
     fopt.normalize = args.normalize
     fopt.affine_refinement = args.affine
     fopt.search_radius = args.search_radius
+    fopt.mask_windows = args.mask_windows
+    mask = None
+    if args.mask_polygon is not None:
+        if len(args.mask_polygon) < 6 or len(args.mask_polygon) % 2:
+            sys.exit("polychase_amd.analyze: --mask-polygon takes x y pairs, three vertices at least")
+        mask = core.PolygonMask([np.array(args.mask_polygon, np.float32).reshape(-1, 2)])
+    elif args.mask_windows:
+        sys.exit("polychase_amd.analyze: --mask-windows needs a mask (--mask-polygon)")
     fopt.channel_weights = tuple(args.channel_weights) if args.channel_weights else None
     fopt.float_transfer = args.float_transfer
     fopt.float_transfer_gamma = args.float_gamma
@@ -219,7 +234,7 @@ def main(argv=None) -> int:
     if world > 1:
         dist.barrier()
     out = analyze(w, h, args.first_frame, n, accessor, args.database, core.GFTTOptions(), fopt, device=dev,
-                  piece_frames=args.piece_frames)
+                  piece_frames=args.piece_frames, detection_mask=mask)
     import json
     sys.stdout.write(json.dumps(out) + "\n")     # ONE write per rank: the ranks share the launcher's stdout
     sys.stdout.flush()

@@ -747,6 +747,7 @@ void pc_context_destroy(pc_context* c) {
     c->lk_back_xy.release();
     c->lk_back_status.release();
     c->lk_choked.release();
+    c->lk_touched.release();
     c->lk_corr.release();
     c->lk_affine_m.release();
     c->lk_affine_state.release();
@@ -939,6 +940,7 @@ void pc_frame_destroy(pc_frame* f) {
     if (f->d_perm) (void)hipFree(f->d_perm);
     if (f->d_mask) (void)hipFree(f->d_mask);
     if (f->d_choked) (void)hipFree(f->d_choked);
+    if (f->d_weights) (void)hipFree(f->d_weights);
     delete f;
 }
 
@@ -963,6 +965,55 @@ int pc_api::upload_mask(pc_frame* f, const uint8_t* mask, size_t row_pitch, int 
     PC_HIP(hipMemcpy2DAsync(f->d_mask, (size_t)f->w, mask, row_pitch, (size_t)f->w, (size_t)f->h,
                             on_device == 1 ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
     f->mask_on = true;
+    f->weights_valid = false;
+    return PC_OK;
+}
+
+int pc_api::alloc_window_weights(pc_frame* f, hipStream_t s) {
+    if (f->d_weights) return PC_OK;
+    size_t total = 0, wt_off[PC_MAX_LEVELS], wm_off[PC_MAX_LEVELS];
+    for (int l = 0; l < f->nlevels; l++) {
+        const pc::Level& L = f->levels[l];
+        wt_off[l] = total;
+        total += align_up(((size_t)L.h + 2 * f->win) * L.pitch, 256);
+    }
+    for (int l = 1; l < f->nlevels; l++) {
+        wm_off[l] = total;
+        total += align_up((size_t)f->levels[l].w * f->levels[l].h, 256);
+    }
+    PC_HIP(hipMalloc(reinterpret_cast<void**>(&f->d_weights), total));
+    // once: the padding is on, and the launches write the interiors only
+    PC_HIP(hipMemsetAsync(f->d_weights, 255, total, s));
+    for (int l = 0; l < f->nlevels; l++) {
+        f->wt[l] = f->d_weights + wt_off[l] + (size_t)f->win * f->levels[l].pitch + pc::kPadX;
+        f->wm[l] = l ? f->d_weights + wm_off[l] : nullptr;
+    }
+    f->weights_valid = false;
+    return PC_OK;
+}
+
+int pc_api::ensure_window_weights(pc_frame* f, hipStream_t s) {
+    if (!f->mask_on) return fail(PC_E_STATE, "the frame has no mask on");
+    return make_window_weights(f, s);
+}
+
+int pc_api::make_window_weights(pc_frame* f, hipStream_t s) {
+    if (int rc = alloc_window_weights(f, s)) return rc;
+    if (f->weights_valid) return PC_OK;
+    pc::WindowWeightParams p;
+    std::memset(&p, 0, sizeof(p));
+    p.mask = f->d_mask;
+    p.nlevels = f->nlevels;
+    for (int l = 0; l < f->nlevels; l++) {
+        p.m[l] = f->wm[l];
+        p.wt[l] = f->wt[l];
+        p.w[l] = f->levels[l].w;
+        p.h[l] = f->levels[l].h;
+        p.pitch[l] = f->levels[l].pitch;
+    }
+    pc::launch_window_weights(p, s);
+    PC_HIP(hipGetLastError());
+    f->weights_valid = true;
     return PC_OK;
 }
 
@@ -1002,6 +1053,7 @@ int pc_api::fill_mask_polygons(pc_frame* f, const int32_t* d_poly, int n_vertice
     pc::launch_polygon_mask(d_poly, n_vertices, n_polygons, invert ? 1 : 0, f->d_mask, f->w, f->h, s);
     PC_HIP(hipGetLastError());
     f->mask_on = true;
+    f->weights_valid = false;
     return PC_OK;
 }
 
@@ -1183,6 +1235,22 @@ int pc_frame_download_choked_mask(pc_context* ctx, const pc_frame* f, int margin
     pc::launch_mask_choke(f->d_mask, ctx->lk_choked.p, f->w, f->h, margin, ctx->stream);
     PC_HIP(hipGetLastError());
     PC_HIP(hipMemcpyAsync(out, ctx->lk_choked.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    PC_HIP(hipStreamSynchronize(ctx->stream));
+    return PC_OK;
+}
+
+int pc_frame_download_window_weights(pc_context* ctx, pc_frame* f, int level, uint8_t* out) {
+    if (!ctx || !f || !out) return fail(PC_E_INVALID, "null argument");
+    if (f->ctx != ctx) return fail(PC_E_INVALID, "frame belongs to another context");
+    if (level < 0 || level >= f->nlevels) return fail(PC_E_INVALID, "bad level");
+    if (!f->mask_on) return fail(PC_E_STATE, "the frame has no mask on");
+    PC_HIP(hipSetDevice(ctx->device));
+    if (int jrc = join_prep(ctx)) return jrc;
+    if (int rc = ensure_window_weights(f, ctx->stream)) return rc;
+    const pc::Level& L = f->levels[level];
+    const int win = f->win;
+    const uint8_t* src = f->wt[level] - (ptrdiff_t)win * L.pitch - win;
+    PC_HIP(hipMemcpy2DAsync(out, L.w + 2 * win, src, L.pitch, L.w + 2 * win, L.h + 2 * win, hipMemcpyDeviceToHost, ctx->stream));
     PC_HIP(hipStreamSynchronize(ctx->stream));
     return PC_OK;
 }

@@ -112,6 +112,9 @@ struct pc_analyzer {
     // >= 0 and a mask is in force every frame put takes the mask -- pc_frame::target_margin is the frame's role as a target,
     // beside mask_on, which stays the detection's -- and with a margin > 0 its choked plane too.
     int target_margin = -1;
+    // Masked windows (pc_analyzer_set_mask_windows) of the frames put and the jobs submitted from now on.  While it is on and a
+    // mask is in force every frame put takes the mask and gets its weight planes: pc_frame::window_weights, beside mask_on.
+    int mask_windows = 0;
     // Detection mask of the frames put from now on with will_detect (pc_analyzer_set_mask).  The mask a detection reads is the
     // plane of its own slot's frame, filled on the preparation stream when the frame is put: a detection already enqueued keeps
     // the mask it was enqueued with.  A host mask is copied at once into one of kMaskGens pinned buffers, used in turn, so that
@@ -316,6 +319,7 @@ int pc_analyzer_reset(pc_analyzer* a) {
         if (s.frame) {
             s.frame->mask_on = false;
             s.frame->target_margin = -1;
+            s.frame->window_weights = false;
         }
     }
     a->mask_kind = 0;
@@ -359,10 +363,13 @@ static int analyzer_put(pc_analyzer* a, int32_t frame_id, const uint8_t* rgb, si
     // the mask of this frame's detection, into the slot's own plane, in front of img_ready: pc_analyzer_frame_ingested then
     // also says that a device mask has been read
     // With a target-side margin every frame takes the mask, as a target; its detection reads the plane as before: iff will_detect.
+    // ... and so it does with the masked windows, whose planes follow the mask in front of img_ready
     const bool as_target = a->target_margin >= 0 && a->mask_kind != 0;
-    const bool take_mask = will_detect || as_target;
+    const bool weighted = a->mask_windows == 1 && a->mask_kind != 0;
+    const bool take_mask = will_detect || as_target || weighted;
     s.frame->mask_on = false;
     s.frame->target_margin = -1;
+    s.frame->window_weights = false;
     if (take_mask && a->mask_kind == 1) {
         // TODO(mask-upload): a static mask is uploaded again for every detected frame (w * h bytes; measured -16 % on a whole
         // 1080p call for an all-on mask, DESIGN.md section 7 "Open follow-ups"): skip the copy when the slot's plane holds this mask
@@ -384,6 +391,11 @@ static int analyzer_put(pc_analyzer* a, int32_t frame_id, const uint8_t* rgb, si
             PC_HIP(hipGetLastError());
         }
         s.frame->target_margin = a->target_margin;
+    }
+    if (weighted) {   // (the slot's weight planes exist: ensure_target_planes ran when switch and mask met)
+        if ((rc = make_window_weights(s.frame, a->ctx->prep_stream)) != PC_OK) return rc;
+        s.frame->mask_on = will_detect != 0;   // the detection's alone, as under a margin
+        s.frame->window_weights = true;
     }
     PC_HIP(hipEventRecord(s.img_ready, a->ctx->prep_stream));
     s.frame_id = frame_id;
@@ -448,6 +460,7 @@ int pc_analyzer_submit(pc_analyzer* a, int32_t frame1, const int32_t* targets, i
     if (a->job_count == a->jobs.size()) return fail(PC_E_STATE, "%zu jobs already in flight: call pc_analyzer_collect", a->job_count);
     if (int arc = check_affine(a->affine, a->normalize)) return arc;   // normalize may have been switched on after the refinement
     if (int src = check_search_radius(a->search_radius, a->normalize)) return src;   // ... or after the search
+    if (int wrc = check_mask_windows(a->mask_windows, a->normalize, a->affine, a->search_radius, a->min_correlation)) return wrc;
     pc_context* ctx = a->ctx;
     PC_HIP(hipSetDevice(ctx->device));
     HelperPriorityScope prio_scope(a->prio.hi);
@@ -537,9 +550,13 @@ int pc_analyzer_submit(pc_analyzer* a, int32_t frame1, const int32_t* targets, i
         // the launches follow each other on the lane; the gate is the forward launch's alone, and the compaction below filters
         // on the status the last pass leaves
         LkPasses passes{.search_radius = a->search_radius, .affine = a->affine, .normalize = a->normalize,
-                        .min_correlation = a->min_correlation, .fb_threshold = a->fb_threshold};
+                        .min_correlation = a->min_correlation, .fb_threshold = a->fb_threshold, .mask_windows = a->mask_windows};
         for (int t = 0; t < n_targets; t++)
             if (tg[t]->target_margin >= 0) passes.plane[t] = tg[t]->target_margin > 0 ? tg[t]->d_choked : tg[t]->d_mask;
+        if (a->mask_windows) {
+            passes.weights_f1 = s1->frame->window_weights;
+            for (int t = 0; t < n_targets; t++) passes.weights_tgt[t] = tg[t]->window_weights;
+        }
         if ((rc = run_lk_job(ctx, s1->frame, tg, n_targets, &a->fopt, passes, lane)) != PC_OK) return rc;
     }
     SlowSection ss_post("submit/post enqueue");
@@ -658,11 +675,27 @@ int pc_analyzer_set_affine_refinement(pc_analyzer* a, int affine) {
 }
 
 // the choked planes of every slot, when frames put from now on will need them: an allocation inside the running pipeline would stall it
+// ... and likewise the weight planes of the masked windows
 static int ensure_target_planes(pc_analyzer* a) {
-    if (a->target_margin <= 0 || a->mask_kind == 0) return PC_OK;
-    for (auto& s : a->slots)
-        if (int rc = ensure_choked_plane(s.frame)) return rc;
+    if (a->mask_kind == 0) return PC_OK;
+    if (a->target_margin > 0)
+        for (auto& s : a->slots)
+            if (int rc = ensure_choked_plane(s.frame)) return rc;
+    if (a->mask_windows == 1) {
+        PrepScope prep(a->ctx);
+        for (auto& s : a->slots)
+            if (int rc = alloc_window_weights(s.frame, a->ctx->prep_stream)) return rc;
+    }
     return PC_OK;
+}
+
+int pc_analyzer_set_mask_windows(pc_analyzer* a, int mask_windows) {
+    if (int rc = check_mask_windows(mask_windows, 0, 0, 0, 0.0)) return rc;   // first: a value is refused whatever the handle
+    if (!a) return fail(PC_E_INVALID, "null analyzer");
+    if (int rc = check_mask_windows(mask_windows, a->normalize, a->affine, a->search_radius, a->min_correlation)) return rc;
+    a->mask_windows = mask_windows;
+    if (mask_windows == 1 && a->mask_kind != 0) PC_HIP(hipSetDevice(a->ctx->device));
+    return ensure_target_planes(a);
 }
 
 int pc_analyzer_set_target_mask_margin(pc_analyzer* a, int margin) {

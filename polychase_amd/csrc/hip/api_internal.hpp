@@ -84,6 +84,8 @@ int check_search_radius(int search_radius, int normalize);
 int check_affine(int affine, int normalize);
 int check_min_correlation(double min_correlation);
 int check_target_margin(int margin, bool allow_off);
+// mask_windows 0 or 1, and 1 not together with normalize, affine, a search radius or a minimum correlation
+int check_mask_windows(int mask_windows, int normalize, int affine, int search_radius, double min_correlation);
 // What follows the forward launch of an LK job (include/polychase_hip.h: pc_lk_track_search and the entry points before it).
 // Value-initialised: the forward launch only.  The side arrays are device memory, [target][n], null where nobody asks.
 struct LkPasses {
@@ -98,6 +100,13 @@ struct LkPasses {
     float* corr;                // the correlation scores: the pass then runs whatever min_correlation
     float2* back_xy;            // the backward end points and status
     uint8_t* back_status;
+    // 1: the masked windows.  weights_f1 / weights_tgt[t]: that frame has weight planes (pc_frame::wt, ready in stream order when
+    // the job starts) -- frame1's weight the forward windows, a target's those of its backward pass; touched: which keypoints the
+    // forward weights touched, [n] (zeroed by the job), or null
+    int mask_windows;
+    bool weights_f1;
+    bool weights_tgt[PC_MAX_TARGETS];
+    uint8_t* touched;
 };
 // Enqueues a whole job into output set `set` on job lane `set` (0: the context's main stream): the forward launch and the passes,
 // in the one order they have.  Afterwards pc_context::lk_rec / lk_slot_of of the set hold the records and the inverse visiting
@@ -107,6 +116,13 @@ int run_lk_job(pc_context* ctx, const pc_frame* frame1, const pc_frame* const* t
                const LkPasses& passes, int set);
 // target-side masks: ensure_choked_plane allocates pc_frame::d_choked (once)
 int ensure_choked_plane(pc_frame* f);
+// masked windows: the weight planes (pc_frame::wt) of the mask in the frame's plane, allocated the first time
+// (alloc_window_weights, which also sets the padding, on stream `s`) and made on stream `s` unless they are those of that mask
+// (make_window_weights; an analyzer's frame holds its mask as a target whether or not its detection reads it).
+// ensure_window_weights: the same for a frame of the stage calls, PC_E_STATE when it has no mask on
+int alloc_window_weights(pc_frame* f, hipStream_t s);
+int make_window_weights(pc_frame* f, hipStream_t s);
+int ensure_window_weights(pc_frame* f, hipStream_t s);
 // gray (+ pyramid) of a frame from u8 gray / u8 RGB / float32 RGB(A) pixels, host or device, on the work stream
 // `clear` (may be null): clear_words words zeroed in front of the frame's kernels (by the level-0 kernel where there is one)
 int set_image(pc_context* ctx, pc_frame* f, const uint8_t* src, size_t row_pitch, int on_device, int channels, int elem_size = 1,

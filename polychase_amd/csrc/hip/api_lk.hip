@@ -56,6 +56,13 @@ int check_target_margin(int margin, bool allow_off) {
     return PC_OK;
 }
 
+int check_mask_windows(int mask_windows, int normalize, int affine, int search_radius, double min_correlation) {
+    if (mask_windows != 0 && mask_windows != 1) return fail(PC_E_INVALID, "mask_windows must be 0 or 1, got %d", mask_windows);
+    if (mask_windows == 1 && (normalize == 1 || affine == 1 || search_radius > 0 || min_correlation > 0.0))
+        return fail(PC_E_INVALID, "normalize, affine refinement, the search prepass and the minimum correlation do not weight their windows: not together with mask_windows");
+    return PC_OK;
+}
+
 namespace {
 
 // What every launch of one job shares, derived once (lk_job_begin): a pass that derived any of it for itself could pair the
@@ -197,6 +204,33 @@ int lk_affine(pc_context* ctx, const LkJob& j, float4* affine_m, uint8_t* affine
     return PC_OK;
 }
 
+// masked windows (include/polychase_hip.h: pc_lk_track_window_masked): the keypoints frame1's weights touch are tracked again
+// under the rule, their records overwritten; touched: device array [n], zeroed, or null
+int lk_window_mask(pc_context* ctx, const LkJob& j, uint8_t* touched) {
+    pc::LKWMaskParams p;
+    std::memset(&p, 0, sizeof(p));
+    for (int l = 0; l <= j.max_level; l++) {
+        p.src[l] = j.frame1->levels[l];
+        p.swt[l] = j.frame1->wt[l];
+        for (int t = 0; t < j.n_targets; t++) p.tgt[t][l] = j.targets[t]->levels[l].img;
+    }
+    p.n_targets = j.n_targets;
+    p.max_level = j.max_level;
+    p.n = j.n;
+    p.win = j.win;
+    p.pts = j.frame1->d_kps;
+    p.perm = j.perm;
+    p.max_iters = j.max_iters;
+    p.eps_sq = j.eps_sq;
+    p.min_eig_thr = j.min_eig_thr;
+    p.rec = j.rec;
+    p.touched = touched;
+    p.x86_order = j.x86_order;
+    ScopedTimer tm(ctx, PC_K_LK, j.stream);   // no class of its own, as the affine refinement
+    if (!pc::launch_lk_wmask(p, j.stream)) return unsupported_window(j);
+    return PC_OK;
+}
+
 // target-side masks (include/polychase_hip.h: pc_lk_track_masked): drops the records that end where the plane of their target
 // is off (plane[t] null: target t keeps its rows; all null: nothing is enqueued)
 int lk_target_mask(const LkJob& j, const uint8_t* const* plane) {
@@ -267,7 +301,17 @@ int lk_backward(pc_context* ctx, const LkJob& j, const LkPasses& passes, const s
     p.x86_order = j.x86_order;
     p.search_d = search_d;
     p.search_state = search_state;
-    {
+    bool weighted = false;   // masked windows: a target with weights swaps the weighted launch in
+    for (int t = 0; t < j.n_targets; t++) weighted = weighted || (passes.mask_windows && passes.weights_tgt[t]);
+    if (weighted) {
+        pc::LKWMaskFBParams q;
+        std::memset(&q, 0, sizeof(q));
+        q.fb = p;
+        for (int t = 0; t < j.n_targets; t++)
+            for (int l = 0; l <= j.max_level && passes.weights_tgt[t]; l++) q.twt[t][l] = j.targets[t]->wt[l];
+        ScopedTimer tm(ctx, PC_K_LK_FB, j.stream);
+        if (!pc::launch_lk_wmask_fb(q, j.stream)) return unsupported_window(j);
+    } else {
         ScopedTimer tm(ctx, PC_K_LK_FB, j.stream);
         if (!(passes.normalize ? pc::launch_lk_norm_fb(p, j.stream) : pc::launch_lk_fb(p, j.stream))) return unsupported_window(j);
     }
@@ -288,6 +332,12 @@ int run_lk_job(pc_context* ctx, const pc_frame* frame1, const pc_frame* const* t
     if (rc != PC_OK || j.n == 0) return rc;
     const size_t rows = (size_t)j.n * n_targets;
     if ((rc = lk_forward(ctx, j, passes.normalize)) != PC_OK) return rc;
+    // masked windows: directly after the forward launch (none of the passes it is refused with follows); frame1 without weights:
+    // nothing to weight, nothing enqueued but the zeros of `touched`
+    if (passes.mask_windows) {
+        if (passes.touched) PC_HIP(hipMemsetAsync(passes.touched, 0, (size_t)j.n, j.stream));
+        if (passes.weights_f1 && (rc = lk_window_mask(ctx, j, passes.touched)) != PC_OK) return rc;
+    }
     // search prepass: directly after the forward launch, in front of the refinement and of every check, which then see the
     // records it replaced
     short2* search_d = nullptr;
@@ -331,6 +381,7 @@ struct LkHostOut {
     uint8_t* affine_state;
     int16_t* search_d;
     uint8_t* search_state;
+    uint8_t* touched;        // [n]
 };
 
 // ... and of a filtered one: the status-1 rows of all targets back to back, row_offset[n_targets + 1] (required) delimits them
@@ -374,11 +425,22 @@ int lk_track_impl(pc_context* ctx, const pc_frame* frame1, const pc_frame* const
     if ((rc = check_search_radius(passes.search_radius, passes.normalize)) != PC_OK) return rc;
     if ((rc = check_affine(passes.affine, passes.normalize)) != PC_OK) return rc;
     if ((rc = check_min_correlation(passes.min_correlation)) != PC_OK) return rc;   // ... and so is a correlation
+    if ((rc = check_mask_windows(passes.mask_windows, passes.normalize, passes.affine, passes.search_radius, passes.min_correlation)) != PC_OK)
+        return rc;
     if ((rc = check_lk_args(ctx, frame1, targets, n_targets, opt)) != PC_OK) return rc;
     if (!out.next_xy || !out.status || !out.err) return fail(PC_E_INVALID, "null output");
     if ((rc = check_fb_threshold(passes.fb_threshold)) != PC_OK) return rc;
     PC_HIP(hipSetDevice(ctx->device));
     if (int jrc = join_prep(ctx)) return jrc;
+    if (passes.mask_windows) {
+        // masked windows: the weight planes of every frame that has a mask on (a cache of the frame, made when the mask changed)
+        passes.weights_f1 = frame1->mask_on;
+        if (frame1->mask_on && (rc = ensure_window_weights(const_cast<pc_frame*>(frame1), ctx->stream)) != PC_OK) return rc;
+        for (int t = 0; t < n_targets && passes.fb_threshold > 0.0; t++) {
+            passes.weights_tgt[t] = targets[t]->mask_on;
+            if (targets[t]->mask_on && (rc = ensure_window_weights(const_cast<pc_frame*>(targets[t]), ctx->stream)) != PC_OK) return rc;
+        }
+    }
     const size_t rows = (size_t)frame1->n_kps * n_targets;
     if (rows == 0) {   // nothing to launch and nothing to write
         if ((rc = run_lk_job(ctx, frame1, targets, n_targets, opt, passes, 0)) != PC_OK) return rc;
@@ -407,6 +469,7 @@ int lk_track_impl(pc_context* ctx, const pc_frame* frame1, const pc_frame* const
         PC_HIP(hipGetLastError());
     }
     if ((rc = side_reserve(ctx->lk_corr, out.corr, rows, &passes.corr)) != PC_OK) return rc;
+    if (passes.mask_windows && (rc = side_reserve(ctx->lk_touched, out.touched, (size_t)frame1->n_kps, &passes.touched)) != PC_OK) return rc;
     if (passes.fb_threshold > 0.0) {
         if ((rc = side_reserve(ctx->lk_back_xy, out.back_xy, rows, &passes.back_xy)) != PC_OK) return rc;
         if ((rc = side_reserve(ctx->lk_back_status, out.back_status, rows, &passes.back_status)) != PC_OK) return rc;
@@ -418,6 +481,7 @@ int lk_track_impl(pc_context* ctx, const pc_frame* frame1, const pc_frame* const
     if ((rc = side_download(ctx, out.affine_m, passes.affine_m, rows)) != PC_OK) return rc;
     if ((rc = side_download(ctx, out.affine_state, passes.affine_state, rows)) != PC_OK) return rc;
     if ((rc = side_download(ctx, out.corr, passes.corr, rows)) != PC_OK) return rc;
+    if ((rc = side_download(ctx, out.touched, passes.touched, (size_t)frame1->n_kps)) != PC_OK) return rc;
     if ((rc = side_download(ctx, out.back_xy, passes.back_xy, rows)) != PC_OK) return rc;
     if ((rc = side_download(ctx, out.back_status, passes.back_status, rows)) != PC_OK) return rc;
     // the kernel's records are in visiting order: bring them into the [target][n] arrays of the call
@@ -527,6 +591,14 @@ int pc_lk_track_search(pc_context* ctx, const pc_frame* frame1, const pc_frame* 
                           .fb_threshold = fb_threshold},
                          {.next_xy = next_xy, .status = status, .err = err, .back_xy = back_xy, .back_status = back_status,
                           .affine_m = affine_m, .affine_state = affine_state, .search_d = search_d, .search_state = search_state});
+}
+
+int pc_lk_track_window_masked(pc_context* ctx, const pc_frame* frame1, const pc_frame* const* targets, int n_targets,
+                              const pc_flow_options* opt, int mask_windows, double fb_threshold, int margin, float* next_xy, uint8_t* status,
+                              float* err, float* back_xy, uint8_t* back_status, uint8_t* touched) {
+    return lk_track_impl(ctx, frame1, targets, n_targets, opt, margin, {.fb_threshold = fb_threshold, .mask_windows = mask_windows},
+                         {.next_xy = next_xy, .status = status, .err = err, .back_xy = back_xy, .back_status = back_status,
+                          .touched = touched});
 }
 
 int pc_lk_track_filtered(pc_context* ctx, const pc_frame* frame1, const pc_frame* const* targets, int n_targets,

@@ -218,6 +218,7 @@ struct pc_context {
     DevBuf<uint8_t> lk_affine_state;
     DevBuf<short2> lk_search_d[2];         // pc_lk_track_search: the displacements and the states of a job, [target][n], one set
     DevBuf<uint8_t> lk_search_state[2];    // per job lane (the backward launches read them)
+    DevBuf<uint8_t> lk_touched;            // pc_lk_track_window_masked: the keypoints the weights touched, [n]
     DevBuf<uint8_t> lk_choked;             // pc_lk_track_masked, pc_frame_download_choked_mask: the targets' choked planes
     DevBuf<uint32_t> lk_cidx, lk_block_counts[2], lk_perm, lk_hist;
     DevBuf<uint32_t> lk_gate;              // LKParams::gate of the analyzer's launches (one word)
@@ -264,5 +265,14 @@ struct pc_frame {
     // or -1: the frame keeps every row.  d_choked is allocated the first time an analyzer needs it.
     int target_margin = -1;
     uint8_t* d_choked = nullptr;
+    // masked windows (pc_lk_track_window_masked): the weight planes W_l of the mask, one per level in the level's image geometry
+    // (wt[l]: interior origin; the padding is on), and behind them the packed M_l of the levels >= 1.  One allocation, made the
+    // first time the frame needs its weights; weights_valid: the planes are those of the mask in d_mask (every change of the mask
+    // clears it).  An analyzer's frame: window_weights says that the frame was put with the option and a mask in force.
+    uint8_t* d_weights = nullptr;
+    uint8_t* wt[PC_MAX_LEVELS] = {nullptr};
+    uint8_t* wm[PC_MAX_LEVELS] = {nullptr};
+    bool weights_valid = false;
+    bool window_weights = false;
 };
 

@@ -277,6 +277,52 @@ bool launch_lk_fb(const LKFBParams& p, hipStream_t s);
 // keypoints -> packed record buffer (both 16-byte aligned)
 void launch_copy_keypoints(const float2* src, float2* dst, int n, hipStream_t s);
 
+// ---- kernels_mask.hip (the weight planes), kernels_lk_wmask.hip ----
+// Masked windows (include/polychase_hip.h: pc_lk_track_window_masked has the rule).  launch_window_weights: the weight planes
+// W_l of a frame, all levels, from its mask plane.  mask: the packed w x h plane M_0 (any non-zero byte is on); level l >= 1 keeps
+// its M_l in m[l] (packed w_l x h_l bytes, 255 / 0; m[0] is not looked at); wt[l]: the INTERIOR origin of W_l, a plane of the
+// level's image geometry (pitch, win rows and the columns of the padding) whose padding the caller has set to 255 once: the
+// launches write the interior only, 255 / 0.  nlevels - 1 launches down the chain and one for the weights of every level.
+struct WindowWeightParams {
+    const uint8_t* mask;
+    uint8_t* m[kMaxLevels];
+    uint8_t* wt[kMaxLevels];
+    int w[kMaxLevels], h[kMaxLevels], pitch[kMaxLevels];
+    int nlevels;
+    int hi_prio;    // filled in by the launcher
+};
+void launch_window_weights(WindowWeightParams p, hipStream_t s);
+// launch_lk_wmask: directly after the forward launch.  A keypoint whose template window has an off sample at some level that
+// passes the bounds test is tracked again into every target under the rule (plain_lk_pair, MASKED) and its records are
+// overwritten; the wavefront of any other keypoint leaves after the test and writes nothing.  touched ([n] bytes in keypoint
+// order, zeroed by the caller; or null) receives 1 for the former.
+struct LKWMaskParams {
+    Level src[kMaxLevels];                 // frame1 levels
+    const uint8_t* swt[kMaxLevels];        // ... and their weight planes (interior origins, the levels' geometry)
+    const uint8_t* tgt[8][kMaxLevels];     // [target][level] interior origins of the targets' u8 planes
+    int n_targets;
+    int max_level;                         // effective (min over pyramids), as in the forward launch
+    int n;                                 // keypoints
+    int win;                               // 3 .. PC_MAX_WINDOW
+    const float2* pts;
+    const uint32_t* perm;                  // visiting order of the forward launch (slot -> keypoint) or null
+    int max_iters;
+    double eps_sq;
+    float min_eig_thr;
+    float4* rec;                           // the forward launch's records, LKParams::out_rec
+    uint8_t* touched;
+    int x86_order;                         // PC_ARITH_LK_X86_ORDER
+};
+// false: window or target count out of range (nothing enqueued)
+bool launch_lk_wmask(const LKWMaskParams& p, hipStream_t s);
+// launch_lk_wmask_fb: what launch_lk_fb is replaced by when a target of the job has weights: the backward pass of target t runs
+// under the rule with the planes twt[t] (null for every level: the plain pass, bit for bit).  fb.search_d / search_state: null.
+struct LKWMaskFBParams {
+    LKFBParams fb;
+    const uint8_t* twt[8][kMaxLevels];     // [target][level] interior origins of the targets' weight planes, or null
+};
+bool launch_lk_wmask_fb(const LKWMaskFBParams& p, hipStream_t s);
+
 // ---- kernels_lk_corr.hip ----
 // Minimum correlation (include/polychase_hip.h: pc_lk_track_correlated): for every record of the forward launch with status 1 the
 // normalised cross-correlation of the level-0 windows LK compared -- I at keypoint - half in frame1's u8 plane, J at end point -

@@ -1,6 +1,7 @@
 // kernels_mask.hip -- the detection mask's plane (kernels_gftt.hip: the MASKED variants read it) rasterised on gfx950 from
 // polygon outlines (include/polychase_hip.h: pc_frame_set_mask_polygons states the fill rule; DESIGN.md section 4 "Polygon
-// masks").  Further down: the choked plane of a mask and the test of the forward records against it ("Target-side masks").
+// masks").  Further down: the choked plane of a mask and the test of the forward records against it ("Target-side masks"), and
+// the weight planes of the masked windows ("Masked windows").
 //
 // The rule is integer.  Vertices arrive snapped to sixteenths of a pixel (|X|, |Y| <= 2^19); pixel (px, py) is the point
 // P = (16 px, 16 py).  An edge A -> B is crossed at P when (Ay <= Py) != (By <= Py), and lies to the right of P when
@@ -243,6 +244,72 @@ void launch_lk_target_mask(TargetMaskParams p, hipStream_t s) {
     p.hi_prio = helper_prio_arg();
     const size_t lanes = (size_t)p.n * kRecStride;
     hipLaunchKernelGGL(lk_target_mask_kernel, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, s, p);
+}
+
+// ---- masked windows: the weight planes of a frame (DESIGN.md section 4 "Masked windows") ----
+//
+// mask_down_kernel: M_l from M_{l-1}, one lane per pixel of level l: the AND of the 5 x 5 pixels pyrDown read to make it, through
+// the REFLECT_101 index map.  Both planes are packed; any non-zero byte of the input is on (level 1 reads the mask plane itself).
+// window_weight_kernel: W_l of every level in one launch (blockIdx.z = level), one lane per 4 adjacent pixels: the AND of M_l over
+// the Scharr support, neighbours outside the level counting as on, written to the interior of the padded plane.  Every read is
+// bounds-tested against the level, every write against its interior; no lane waits for another.
+__global__ __launch_bounds__(256) void mask_down_kernel(const uint8_t* __restrict__ in, int pw, int ph, uint8_t* __restrict__ out, int w, int h,
+                                                        int hi_prio) {
+    helper_priority(hi_prio);
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (x >= w || y >= h) return;
+    bool on = true;
+#pragma unroll
+    for (int dy = -2; dy <= 2; dy++) {
+        const uint8_t* const row = in + (size_t)reflect101(2 * y + dy, ph) * pw;
+#pragma unroll
+        for (int dx = -2; dx <= 2; dx++) on = on && row[reflect101(2 * x + dx, pw)] != 0;
+    }
+    out[(size_t)y * w + x] = on ? 255 : 0;
+}
+
+__global__ __launch_bounds__(256) void window_weight_kernel(const WindowWeightParams p) {
+    helper_priority(p.hi_prio);
+    const int l = blockIdx.z;
+    const int w = p.w[l], h = p.h[l];
+    const int x0 = (blockIdx.x * 64 + (threadIdx.x & 63)) * 4, y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (x0 >= w || y >= h) return;
+    const uint8_t* __restrict__ m = l == 0 ? p.mask : p.m[l];
+    uint32_t col = 0;   // bit k: every pixel of column x0 - 1 + k in rows y - 1 .. y + 1 is on (outside the level: on)
+#pragma unroll
+    for (int k = 0; k < 6; k++) {
+        const int x = x0 - 1 + k;
+        bool on = true;
+        if (x >= 0 && x < w) {
+#pragma unroll
+            for (int dy = -1; dy <= 1; dy++) {
+                const int yy = y + dy;
+                if (yy >= 0 && yy < h) on = on && m[(size_t)yy * w + x] != 0;
+            }
+        }
+        col |= (uint32_t)on << k;
+    }
+    const uint32_t bits = col & (col >> 1) & (col >> 2) & 15u;
+    // bit k -> byte k = 255
+    const uint32_t word = ((bits & 1u) | ((bits & 2u) << 7) | ((bits & 4u) << 14) | ((bits & 8u) << 21)) * 255u;
+    uint8_t* const out = p.wt[l] + (size_t)y * p.pitch[l] + x0;   // interior rows start 4-byte aligned (kPadX, pitch)
+    if (x0 + 3 < w) {
+        *reinterpret_cast<uint32_t*>(out) = word;
+    } else {
+        for (int k = 0; k < 4 && x0 + k < w; k++) out[k] = (uint8_t)(word >> (8 * k));
+    }
+}
+
+void launch_window_weights(WindowWeightParams p, hipStream_t s) {
+    if (p.nlevels < 1) return;
+    p.hi_prio = helper_prio_arg();
+    for (int l = 1; l < p.nlevels; l++) {
+        const dim3 grid((p.w[l] + 63) / 64, (p.h[l] + 3) / 4);
+        hipLaunchKernelGGL(mask_down_kernel, grid, dim3(256), 0, s, l == 1 ? p.mask : p.m[l - 1], p.w[l - 1], p.h[l - 1], p.m[l], p.w[l], p.h[l],
+                           p.hi_prio);
+    }
+    const dim3 grid((p.w[0] + 255) / 256, (p.h[0] + 3) / 4, p.nlevels);
+    hipLaunchKernelGGL(window_weight_kernel, grid, dim3(256), 0, s, p);
 }
 
 }  // namespace pc

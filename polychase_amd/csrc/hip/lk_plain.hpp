@@ -2,7 +2,8 @@
 // calcOpticalFlowPyrLK(prev = the template image, next = the searched image, pts = {start}), bit for bit in either arithmetic
 // order.  Two kernels are built from it: the forward cross-check of the product kernels (kernels_lk.hip: lk_plain_kernel, template
 // = frame1, searched = a target, with the patch error) and the backward pass of the forward-backward check (kernels_lk_fb.hip:
-// lk_fb_kernel, template = a target, searched = frame1, no patch error).
+// lk_fb_kernel, template = a target, searched = frame1, no patch error).  The two kernels of the masked windows
+// (kernels_lk_wmask.hip; include/polychase_hip.h: pc_lk_track_window_masked has the rule) are the MASKED instances of the same body.
 //
 // The group evaluates its own win x win template (patch value + Scharr pair per pixel) per level and keeps it in its own slice of
 // LDS, 8 bytes per pixel; the searched image is gathered straight from the padded u8 plane: a window that passed OpenCV's bounds
@@ -25,6 +26,7 @@ struct PlainLKLevel {
     const uint8_t* I;
     const int32_t* dI;
     const uint8_t* J;
+    const uint8_t* Wt = nullptr;   // MASKED: the template image's weight plane (geometry of I), null: every sample on
 };
 struct PlainLKResult {
     float nx, ny;
@@ -52,6 +54,18 @@ __device__ __forceinline__ TemplatePixel template_pixel(const uint8_t* __restric
 }
 __device__ __forceinline__ uint2 pack_template(const TemplatePixel& t) {
     return make_uint2((uint32_t)t.ival, (uint32_t)(t.ix & 0xffff) | ((uint32_t)t.iy << 16));
+}
+// MASKED: a sample is on iff its four taps are on in the weight plane (255 / 0); the flag rides above ival (0 .. 8160) in the
+// entry's first word, and an off sample carries a zero Scharr pair
+constexpr uint32_t kTemplateOnBit = 1u << 16;
+__device__ __forceinline__ bool template_sample_on(const uint8_t* __restrict__ Wt, int pitch, ptrdiff_t o) {
+    const uint8_t* m = Wt + o;
+    return (m[0] & m[1] & m[pitch] & m[pitch + 1]) != 0;
+}
+template <bool MASKED>
+__device__ __forceinline__ uint32_t template_ival(uint32_t word) {
+    if constexpr (MASKED) return word & 0xffffu;
+    else return word;
 }
 __device__ __forceinline__ int interp_u8(int a, int b, int c, int d, const Weights& w) {
     return PC_DESCALE(a * w.w00 + b * w.w01 + c * w.w10 + d * w.w11, W_BITS - 5);
@@ -81,7 +95,9 @@ __device__ __forceinline__ float group8_exact_sum_i64(long long v) {
 // GUESS: the search of the top level starts at (guess_x, guess_y) * lscale instead of at the template's position -- OpenCV's
 // OPTFLOW_USE_INITIAL_FLOW, the guided pass of the search prepass (kernels_lk_search.hip); nothing else changes, and without it
 // the two arguments are not looked at.
-template <bool X86, bool ERR, bool GUESS = false, class LevelOf>
+// MASKED: the masked windows -- PlainLKLevel::Wt decides which template samples take part; the four places the rule changes are
+// marked below, and an instance without the switch is the code it was.
+template <bool X86, bool ERR, bool GUESS = false, bool MASKED = false, class LevelOf>
 __device__ __forceinline__ PlainLKResult plain_lk_pair(const LevelOf& level_of, float start_x, float start_y, int win, int lg, int max_level,
                                                        int max_iters, double eps_sq, float min_eig_thr, uint2* const tm,
                                                        float guess_x = 0.f, float guess_y = 0.f) {
@@ -124,14 +140,32 @@ __device__ __forceinline__ PlainLKResult plain_lk_pair(const LevelOf& level_of, 
         }
         const Weights wI = bilinear_weights(px - (float)ipx, py - (float)ipy);
         const ptrdiff_t oI = (ptrdiff_t)ipy * pitch + ipx;
+        [[maybe_unused]] const uint8_t* __restrict__ Wt = nullptr;
+        [[maybe_unused]] int n_on = win * win;
+        [[maybe_unused]] int lane_on = 0;
+        if constexpr (MASKED) Wt = L.Wt;
+        // MASKED (1): ix and iy of an off sample are 0, ival is kept
+        auto masked_template = [&](TemplatePixel& t, ptrdiff_t o) -> uint2 {
+            uint2 e;
+            if constexpr (MASKED) {
+                const bool on = !Wt || template_sample_on(Wt, pitch, o);
+                if (!on) t.ix = t.iy = 0;
+                lane_on += on ? 1 : 0;
+                e = pack_template(t);
+                e.x |= on ? kTemplateOnBit : 0u;
+            } else {
+                e = pack_template(t);
+            }
+            return e;
+        };
         float A11, A12, A22;
         if constexpr (X86) {
             float q11 = 0.f, q12 = 0.f, q22 = 0.f;
             const int xb = lg < 4 ? lg : simd_w, xe = lg < 4 ? simd_w : (lg == 4 ? win : 0), xs = lg < 4 ? 4 : 1;
             for (int y = 0; y < win; y++) {
                 for (int x = xb; x < xe; x += xs) {
-                    const TemplatePixel t = template_pixel(I, dI, pitch, oI + (ptrdiff_t)y * pitch + x, wI);
-                    tm[y * win + x] = pack_template(t);
+                    TemplatePixel t = template_pixel(I, dI, pitch, oI + (ptrdiff_t)y * pitch + x, wI);
+                    tm[y * win + x] = masked_template(t, oI + (ptrdiff_t)y * pitch + x);
                     if (lg < 4) {
                         const float fx = (float)t.ix, fy = (float)t.iy;
                         q22 = fy * fy + q22;
@@ -155,8 +189,8 @@ __device__ __forceinline__ PlainLKResult plain_lk_pair(const LevelOf& level_of, 
             long long s11 = 0, s12 = 0, s22 = 0;
             for (int x = lg; x < win; x += 8) {
                 for (int y = 0; y < win; y++) {
-                    const TemplatePixel t = template_pixel(I, dI, pitch, oI + (ptrdiff_t)y * pitch + x, wI);
-                    tm[y * win + x] = pack_template(t);
+                    TemplatePixel t = template_pixel(I, dI, pitch, oI + (ptrdiff_t)y * pitch + x, wI);
+                    tm[y * win + x] = masked_template(t, oI + (ptrdiff_t)y * pitch + x);
                     s11 += t.ix * t.ix;   // |ix|, |iy| <= 4080
                     s12 += t.ix * t.iy;
                     s22 += t.iy * t.iy;
@@ -166,9 +200,18 @@ __device__ __forceinline__ PlainLKResult plain_lk_pair(const LevelOf& level_of, 
             A12 = group8_exact_sum_i64(s12) * FLT_SCALE;
             A22 = group8_exact_sum_i64(s22) * FLT_SCALE;
         }
+        if constexpr (MASKED) {
+            // MASKED (2): a window with fewer than a quarter of its samples on fails like the min-eig test
+            n_on = group_allreduce_add<8>(lane_on);
+            if (4 * n_on < win * win) {
+                if (level == 0) status = false;
+                continue;
+            }
+        }
         float D = A11 * A22 - A12 * A12;
         const float tdiff = A11 - A22;
-        const float min_eig = (A22 + A11 - sqrtf(tdiff * tdiff + 4.f * A12 * A12)) / (float)(2 * win * win);
+        // MASKED (3): the divisor counts the on samples
+        const float min_eig = (A22 + A11 - sqrtf(tdiff * tdiff + 4.f * A12 * A12)) / (float)(2 * (MASKED ? n_on : win * win));
         if (min_eig < min_eig_thr || D < 1.1920928955078125e-07f /* FLT_EPSILON */) {
             if (level == 0) status = false;
             continue;
@@ -197,7 +240,8 @@ __device__ __forceinline__ PlainLKResult plain_lk_pair(const LevelOf& level_of, 
                         // the products of columns (c, c + 4) of a block of 8 are added as int32 before the conversion
                         for (int x0 = lg; x0 < simd_w; x0 += 8) {
                             const uint2 ta = tr[x0], tb = tr[x0 + 4];
-                            const int da = pixel_diff(jr + x0, pitch, wJ, ta.x), db = pixel_diff(jr + x0 + 4, pitch, wJ, tb.x);
+                            const int da = pixel_diff(jr + x0, pitch, wJ, template_ival<MASKED>(ta.x)),
+                                      db = pixel_diff(jr + x0 + 4, pitch, wJ, template_ival<MASKED>(tb.x));
                             const int p1 = da * (int)(int16_t)(ta.y & 0xffffu) + db * (int)(int16_t)(tb.y & 0xffffu);
                             const int p2 = da * ((int)ta.y >> 16) + db * ((int)tb.y >> 16);
                             q1 += (float)p1;
@@ -206,7 +250,7 @@ __device__ __forceinline__ PlainLKResult plain_lk_pair(const LevelOf& level_of, 
                     } else if (lg == 4) {
                         for (int x = simd_w; x < win; x++) {
                             const uint2 t = tr[x];
-                            const int d = pixel_diff(jr + x, pitch, wJ, t.x);
+                            const int d = pixel_diff(jr + x, pitch, wJ, template_ival<MASKED>(t.x));
                             q1 += (float)(d * (int)(int16_t)(t.y & 0xffffu));
                             q2 += (float)(d * ((int)t.y >> 16));
                         }
@@ -227,7 +271,7 @@ __device__ __forceinline__ PlainLKResult plain_lk_pair(const LevelOf& level_of, 
                         s += pitch;
                         const int u0 = s[0], u1 = s[1];
                         const uint2 t = tm[y * win + x];
-                        const int diff = interp_u8(t0, t1, u0, u1, wJ) - (int)t.x;   // |diff| <= 8160
+                        const int diff = interp_u8(t0, t1, u0, u1, wJ) - (int)template_ival<MASKED>(t.x);   // |diff| <= 8160
                         sb1 += diff * (int)(int16_t)(t.y & 0xffffu);
                         sb2 += diff * ((int)t.y >> 16);
                         t0 = u0;
@@ -268,12 +312,14 @@ __device__ __forceinline__ PlainLKResult plain_lk_pair(const LevelOf& level_of, 
                 int se = 0;
                 for (int y = 0; y < win; y++) {
                     for (int x = xb; x < xe; x += xs) {
-                        const int diff = pixel_diff(eb + (ptrdiff_t)y * pitch + x, pitch, wE, tm[y * win + x].x);
-                        se += diff < 0 ? -diff : diff;
+                        const uint32_t tw = tm[y * win + x].x;
+                        const int diff = pixel_diff(eb + (ptrdiff_t)y * pitch + x, pitch, wE, template_ival<MASKED>(tw));
+                        // MASKED (4): the error is that of the on samples
+                        if (!MASKED || (tw & kTemplateOnBit)) se += diff < 0 ? -diff : diff;
                     }
                 }
                 se = group_allreduce_add<8>(se);   // <= 31^2 * 8160 < 2^24: exact in fp32 too
-                err = ((float)se * 1.f) / (float)(32 * win * win);
+                err = ((float)se * 1.f) / (float)(32 * (MASKED ? n_on : win * win));
             }
         }
     }

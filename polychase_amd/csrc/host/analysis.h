@@ -62,6 +62,12 @@ struct OpticalFlowOptions {
     // with the smaller patch error stays -- flow rows that survive fast pans and the long skips (Blender's tracker calls the
     // search its prepass).  Not together with normalize.
     int search_radius = 0;
+    // not in the reference: masked windows (include/polychase_hip.h: pc_lk_track_window_masked).  true: the template pixels of an
+    // LK window that lie outside the detection mask of the window's frame carry no weight (Blender's use_mask), so keypoints near
+    // the outline of a matted object follow the object and not the layer behind it.  Like target_mask_margin it makes every frame
+    // take its mask, and it does nothing without a detection_mask.  Not together with normalize, affine_refinement, search_radius
+    // or min_correlation, which do not weight their windows.
+    bool mask_windows = false;
     // not in the reference: gray conversion (include/polychase_hip.h: pc_gray_conversion).  channel_weights: nothing = the
     // reference's RGB2GRAY; (r, g, b), finite, >= 0, not all zero = the weights of the three channels in the gray plane that is
     // detected and tracked (Blender's tracker has R / G / B switches), for u8 and float frames.  float_transfer: "none" = float
@@ -82,6 +88,8 @@ inline void CheckOpticalFlowOptions(const OpticalFlowOptions& o) {
         throw std::invalid_argument("search_radius must be 0 (off) or 1..256, got " + std::to_string(o.search_radius));
     if (o.search_radius > 0 && o.normalize)
         throw std::invalid_argument("search_radius assumes brightness constancy: it cannot be combined with normalize");
+    if (o.mask_windows && (o.normalize || o.affine_refinement || o.search_radius > 0 || o.min_correlation > 0.0))
+        throw std::invalid_argument("mask_windows cannot be combined with normalize, affine_refinement, search_radius or min_correlation: they do not weight their windows");
     if (o.affine_refinement && o.normalize)
         throw std::invalid_argument("affine_refinement assumes brightness constancy: it cannot be combined with normalize");
     if (o.channel_weights) {

@@ -458,6 +458,9 @@ static void RunAnalysis(const VideoInfo& video_info, FrameAccessorFunction frame
     // ... the target-side margin, off without a mask to choke ...
     const int target_margin = detection_mask.empty() ? -1 : flow_options.target_mask_margin;
     if (pc_analyzer_set_target_mask_margin(eng.an, target_margin) != PC_OK) ThrowHip("pc_analyzer_set_target_mask_margin");
+    // ... the masked windows, off without a mask to weight by (after the four options that exclude them) ...
+    const bool mask_windows = flow_options.mask_windows && !detection_mask.empty();
+    if (pc_analyzer_set_mask_windows(eng.an, mask_windows ? 1 : 0) != PC_OK) ThrowHip("pc_analyzer_set_mask_windows");
     // ... and so is the detection mask: the run's one mask, or none until the first frame's is asked for
     auto set_mask = [&](const std::optional<MaskView>& m) {
         if (m) check_mask(*m);
@@ -663,7 +666,7 @@ static void RunAnalysis(const VideoInfo& video_info, FrameAccessorFunction frame
             // the rows that end in it (asked for every frame: the halo of a shard and frames with stored keypoints too); a device
             // mask is read when the frame is put, so its owner waits with the frame's for pc_analyzer_frame_ingested
             std::shared_ptr<void> mask_owner;
-            const bool takes_mask = will_detect || target_margin >= 0;
+            const bool takes_mask = will_detect || target_margin >= 0 || mask_windows;
             if (takes_mask && detection_mask.per_frame) {
                 std::optional<MaskView> m = detection_mask.per_frame(fid);
                 set_mask(m);

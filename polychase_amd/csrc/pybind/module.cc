@@ -483,6 +483,7 @@ PYBIND11_MODULE(polychase_core, m) {
         .def_readwrite("normalize", &OpticalFlowOptions::normalize)   // not in the reference; brightness-normalised LK, off by default
         .def_readwrite("affine_refinement", &OpticalFlowOptions::affine_refinement)   // not in the reference; off by default, not with normalize
         .def_readwrite("search_radius", &OpticalFlowOptions::search_radius)   // not in the reference; 0 = off, 1..256, not with normalize
+        .def_readwrite("mask_windows", &OpticalFlowOptions::mask_windows)   // not in the reference; off by default, needs a detection_mask
         // not in the reference: the gray conversion (include/polychase_hip.h: pc_gray_conversion)
         .def_readwrite("channel_weights", &OpticalFlowOptions::channel_weights)           // None or three floats (r, g, b)
         .def_readwrite("float_transfer", &OpticalFlowOptions::float_transfer)             // "none", "srgb" or "gamma"

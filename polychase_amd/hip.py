@@ -39,6 +39,7 @@ SYMBOLS = [
     "pc_lk_track_normalized", "pc_analyzer_set_normalize",
     "pc_lk_track_affine", "pc_analyzer_set_affine_refinement",
     "pc_lk_track_search", "pc_analyzer_set_search_radius",
+    "pc_lk_track_window_masked", "pc_frame_download_window_weights", "pc_analyzer_set_mask_windows",
     "pc_lk_track", "pc_lk_track_filtered", "pc_lk_track_fb", "pc_lk_track_filtered_fb",
     "pc_analyzer_create", "pc_analyzer_destroy", "pc_analyzer_reset", "pc_analyzer_put_frame", "pc_analyzer_put_frame_f32",
     "pc_analyzer_has_frame", "pc_analyzer_frame_ingested",
@@ -237,6 +238,10 @@ def load():
     L.pc_analyzer_set_normalize.argtypes = [vp, C.c_int]
     L.pc_analyzer_set_affine_refinement.argtypes = [vp, C.c_int]
     L.pc_analyzer_set_search_radius.argtypes = [vp, C.c_int]
+    L.pc_lk_track_window_masked.argtypes = [vp, vp, C.POINTER(vp), C.c_int, C.POINTER(FlowOptions), C.c_int, C.c_double, C.c_int,
+                                            vp, vp, vp, vp, vp, vp]
+    L.pc_frame_download_window_weights.argtypes = [vp, vp, C.c_int, vp]
+    L.pc_analyzer_set_mask_windows.argtypes = [vp, C.c_int]
     L.pc_peer_buffer_alloc.argtypes = [C.c_int, C.c_size_t, C.POINTER(vp)]
     L.pc_peer_buffer_free.argtypes = [C.c_int, vp]
     L.pc_peer_buffer_export.argtypes = [C.c_int, vp, C.c_char_p]
@@ -578,6 +583,14 @@ class Frame:
         _check(load().pc_frame_download_choked_mask(self.ctx._h, self._h, int(margin), out.ctypes.data))
         return out
 
+    def window_weights(self, level: int) -> np.ndarray:
+        """The weight plane of pyramid level `level` under the mask in force, with its padding: uint8 (h_l + 2 win, w_l + 2 win),
+        255 / 0 (pc_frame_download_window_weights; include/polychase_hip.h: pc_lk_track_window_masked has the rule)."""
+        w, h = self.level_size(level)
+        out = np.empty((h + 2 * self.win, w + 2 * self.win), np.uint8)
+        _check(load().pc_frame_download_window_weights(self.ctx._h, self._h, int(level), out.ctypes.data))
+        return out
+
     def detect(self, opt: GfttOptions | None = None):
         opt = opt or gftt_options()
         _check(load().pc_frame_detect(self.ctx._h, self._h, C.byref(opt)))
@@ -711,6 +724,21 @@ def lk_track_search(ctx: Context, frame1: Frame, targets: list[Frame], search_ra
                     ("xy", "st", "err", "bxy", "bst", "am", "ast", "sd", "sst"))
 
 
+def lk_track_window_masked(ctx: Context, frame1: Frame, targets: list[Frame], mask_windows: int = 1, fb_threshold: float = 0.0,
+                           margin: int = -1, opt: FlowOptions | None = None):
+    """masked windows (include/polychase_hip.h: pc_lk_track_window_masked): with mask_windows 1 the template pixels outside the
+    mask of frame1 -- and, in the backward pass, of a masked target -- carry no weight; with 0 it is lk_track_masked plus the back
+    outputs of lk_track_fb.
+    -> next_xy [T,N,2], final status [T,N], err [T,N], back_xy [T,N,2], back_status [T,N], touched [N] (1: the keypoint's window
+    has an off sample at some level, and its rows were tracked under the rule)."""
+    opt = opt or flow_options()
+    n, t = frame1.num_keypoints, len(targets)
+    out = tuple(np.zeros((t, n) + _LK_OUT[k][0], _LK_OUT[k][1]) for k in ("xy", "st", "err", "bxy", "bst")) + (np.zeros(n, np.uint8),)
+    _check(load().pc_lk_track_window_masked(ctx._h, frame1._h, _target_handles(targets), t, C.byref(opt), int(mask_windows),
+                                            float(fb_threshold), int(margin), *[a.ctypes.data for a in out]))
+    return out
+
+
 def lk_track_filtered_fb(ctx: Context, frame1: Frame, targets: list[Frame], fb_threshold: float, opt: FlowOptions | None = None):
     """lk_track_filtered on the final status of the forward-backward check (pc_lk_track_filtered_fb)."""
     return _lk_call_filtered("pc_lk_track_filtered_fb", ctx, frame1, targets, opt, (float(fb_threshold),))
@@ -817,6 +845,12 @@ class Analyzer:
         """affine refinement for the jobs submitted from now on; 0 / False = off, 1 / True = on, refused while normalize is on
         (pc_analyzer_set_affine_refinement)"""
         _check(load().pc_analyzer_set_affine_refinement(self._h, int(affine)))
+
+    def set_mask_windows(self, on: bool):
+        """masked windows for the frames put and the jobs submitted from now on (pc_analyzer_set_mask_windows): every frame put
+        while a mask is in force gets its weight planes, and template pixels outside the mask carry no weight; refused beside
+        normalize, the affine refinement, a search radius or a minimum correlation"""
+        _check(load().pc_analyzer_set_mask_windows(self._h, int(on)))
 
     def set_search_radius(self, search_radius: int):
         """search prepass for the jobs submitted from now on; 0 = off, 1..256 = the radius in pixels, refused while normalize is on

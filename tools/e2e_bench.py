@@ -4,7 +4,7 @@ addon experiences), next to bench.py's HBM-resident number.  Not the headline me
 
   python tools/e2e_bench.py [--config c2|c3] [--frames 60] [--mask-fraction F [--mask-polygon] [--mask-outline N]
                              [--target-mask-margin R]] [--min-correlation V] [--normalize] [--affine]
-                             [--search-radius N] [--pan PX]
+                             [--search-radius N] [--mask-windows] [--pan PX]
 
 Modes: frames as torch CUDA tensors / host numpy arrays (PCIe upload included), with and without the
 SQLite insert.  --mask-fraction F: every run takes detection_mask = a centred rectangle of the frame's aspect covering F of
@@ -24,7 +24,9 @@ of the per-class pass (class "lk_corr") -- rows whose reference and matched wind
 off); the SQLite modes then report the mean number of flow rows per frame too.  --normalize: OpticalFlowOptions.normalize of every
 run, and of the per-class pass (the normalised launch is timed under class "lk").  --affine: OpticalFlowOptions.affine_refinement of
 every run, and of the per-class pass (the refinement launch is timed under class "lk" too: two launches per step).  --search-radius N: OpticalFlowOptions.search_radius of
-every run, and of the per-class pass (the search launch is timed under class "lk" as well).  --pan PX: instead of the benchmark clip,
+every run, and of the per-class pass (the search launch is timed under class "lk" as well).  --mask-windows (with --mask-fraction):
+OpticalFlowOptions.mask_windows of every run, and of the per-class pass (the masked launch is timed under class "lk" too, the weight
+planes of a frame under no class).  --pan PX: instead of the benchmark clip,
 frame t is frame 0 rolled by t * PX pixels in x -- a pan the plain search loses on the long skips."""
 import argparse
 import json
@@ -37,7 +39,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
-def per_class_ms(w, h, ml, frames, mask, steps=40, polygons=None, target_margin=-1, min_correlation=0.0, normalize=False, affine=False, search_radius=0):
+def per_class_ms(w, h, ml, frames, mask, steps=40, polygons=None, target_margin=-1, min_correlation=0.0, normalize=False, affine=False, search_radius=0,
+                 mask_windows=False):
     """one pipelined pass (polychase_amd.pipeline.ClipAnalyzer) with every kernel class timed: 20 untimed steps, then `steps`"""
     from polychase_amd import hip
     from polychase_amd.pipeline import ClipAnalyzer
@@ -53,6 +56,7 @@ def per_class_ms(w, h, ml, frames, mask, steps=40, polygons=None, target_margin=
     an.an.set_normalize(normalize)
     an.an.set_affine_refinement(affine)
     an.an.set_search_radius(search_radius)
+    an.an.set_mask_windows(mask_windows)
     steps = min(steps, len(frames) - 9 - 29)
     an.run(range(9, 29), None)
     ctx.synchronize()
@@ -80,6 +84,7 @@ def main():
     ap.add_argument("--normalize", action="store_true")
     ap.add_argument("--affine", action="store_true")
     ap.add_argument("--search-radius", type=int, default=0)
+    ap.add_argument("--mask-windows", action="store_true")
     ap.add_argument("--pan", type=int, default=0)
     a = ap.parse_args()
     import torch
@@ -101,6 +106,9 @@ def main():
     fo.normalize = a.normalize
     fo.affine_refinement = a.affine
     fo.search_radius = a.search_radius
+    fo.mask_windows = a.mask_windows
+    if a.mask_windows and a.mask_fraction is None:
+        ap.error("--mask-windows needs a mask (--mask-fraction, optionally --mask-polygon / --mask-outline)")
     vi = core.VideoInfo(w, h, 1, a.frames)
     out = {}
     mask = None
@@ -144,13 +152,15 @@ def main():
         out["affine_refinement"] = True
     if a.search_radius:
         out["search_radius"] = a.search_radius
+    if a.mask_windows:
+        out["mask_windows"] = True
     if a.pan:
         out["pan_px_per_frame"] = a.pan
     if a.frames >= 39:
         out["gpu_ms_per_step"] = per_class_ms(w, h, ml, dev, mask, polygons=polygons,
                                               target_margin=a.target_mask_margin if a.mask_fraction is not None else -1,
                                               min_correlation=a.min_correlation, normalize=a.normalize, affine=a.affine,
-                                              search_radius=a.search_radius)
+                                              search_radius=a.search_radius, mask_windows=a.mask_windows)
     else:
         out["gpu_ms_per_step"] = {"skipped": "the per-class pass needs --frames 39 or more (20 untimed steps, then at least one)"}
     with tempfile.TemporaryDirectory() as td:

@@ -8,6 +8,7 @@ the average launch time and a checksum of the raw outputs (equal checksums <=> b
 results, the way kernel variants are compared: POLYCHASE_HIP_LIB selects the library).
 
     python tools/lk_bench.py [--config c2|c3] [--reps 20] [--fb PX] [--min-correlation V] [--normalize] [--affine] [--search-radius N]
+                             [--mask-fraction F] [--mask-windows]
 
 --fb PX also times the forward-backward check (pc_lk_track_fb, threshold PX): the forward launch and the backward launch of
 the same call, and as the baseline the same backward work through the calls that existed before it -- per target,
@@ -20,6 +21,10 @@ launch measured above; with --fb PX the normalised backward launch beside it, ag
 the figure is the class total of the calls with the option minus that of the same number of calls without it.
 --search-radius N also times the search prepass (pc_lk_track_search, search_radius = N), the same way as --affine; --shift DX DY
 tracks into targets that are frame1 shifted by whole pixels (k * DX / 8, k * DY / 8 for the k-th skip), where the search has work.
+--mask-fraction F puts frame1 and the targets under a polygon mask (an ellipse-like 32-gon over the fraction F of the frame) before
+frame1 is detected, so the keypoints lie inside it; --mask-windows then also times the masked windows (pc_lk_track_window_masked):
+the masked launch is timed under the forward launch's class, so its figure is the class total of the calls with the option minus
+that of the calls without it, in alternating rounds; with --fb PX the weighted backward launch beside the plain one.
 
 (Parity against the CPU oracle is the test suite's business: tests/test_gpu_parity.py, tests/test_fullsize_gpu.py.)
 """
@@ -182,6 +187,49 @@ def search_timing(ctx, hip, f1, targets, fopt, reps, radius, xy, st, err):
             "forward_rows": int((st == 1).sum()), "rows_with_search": int((res[1] == 1).sum()), "sha256": hsh.hexdigest()[:16]}
 
 
+def mask_polygon(w, h, fraction):
+    """an ellipse-like 32-gon around the frame's centre that covers `fraction` of the frame (0 < fraction <= 0.75)"""
+    s = np.sqrt(fraction / np.pi)
+    a = 2.0 * np.pi * np.arange(32) / 32
+    return np.stack([w / 2 + w * s * np.cos(a), h / 2 + h * s * np.sin(a)], axis=1).astype(np.float32)
+
+
+def wmask_timing(ctx, hip, f1, targets, fopt, fb, reps, xy, st, err):
+    """forward + masked launch of pc_lk_track_window_masked against the forward launch alone (mask_windows = 0) in alternating
+    rounds; the backward launch of either variant has its own class"""
+    res = hip.lk_track_window_masked(ctx, f1, targets, 1, fb, -1, fopt)      # warm-up + the output that is compared
+    off = hip.lk_track_window_masked(ctx, f1, targets, 0, fb, -1, fopt)
+    assert np.array_equal(off[0], xy) and np.array_equal(off[2], err), "mask_windows = 0 changed a forward value"
+    touched = res[5] == 1
+    assert np.array_equal(res[0][:, ~touched], xy[:, ~touched]) and np.array_equal(res[2][:, ~touched], err[:, ~touched]), "an untouched record changed"
+    hsh = hashlib.sha256()
+    for a in res:
+        hsh.update(np.ascontiguousarray(a).tobytes())
+    ms = {0: {"lk": 0.0, "lk_fb": 0.0}, 1: {"lk": 0.0, "lk_fb": 0.0}}
+    launches = {0: 0, 1: 0}
+    ctx.enable_timing(["lk", "lk_fb"])
+    for _ in range(reps):
+        for flag in (0, 1):
+            ctx.reset_timing()
+            again = hip.lk_track_window_masked(ctx, f1, targets, flag, fb, -1, fopt)
+            t = ctx.timing()
+            launches[flag] += t["lk"][0]
+            for k in ms[flag]:
+                ms[flag][k] += t[k][1]
+    ctx.enable_timing(False)
+    assert all(np.array_equal(a, b) for a, b in zip(again, res)), "results vary between launches"
+    assert launches[0] == reps and launches[1] == 2 * reps, launches
+    fwd_ms, masked_ms = ms[0]["lk"] / reps, (ms[1]["lk"] - ms[0]["lk"]) / reps
+    out = {"forward_ms": fwd_ms, "masked_launch_ms": masked_ms, "forward_plus_masked_ms": fwd_ms + masked_ms,
+           "masked_over_forward": masked_ms / fwd_ms if fwd_ms else None, "keypoints": int(len(touched)), "touched": int(touched.sum()),
+           "touched_fraction": float(touched.mean()) if len(touched) else None, "forward_rows": int((st == 1).sum()),
+           "rows_with_mask_windows": int((res[1] == 1).sum()), "rows_option_off": int((off[1] == 1).sum()), "sha256": hsh.hexdigest()[:16]}
+    if fb > 0:
+        out.update(fb_threshold=fb, plain_backward_ms=ms[0]["lk_fb"] / reps, weighted_backward_ms=ms[1]["lk_fb"] / reps)
+        out["backward_over_plain"] = out["weighted_backward_ms"] / out["plain_backward_ms"] if out["plain_backward_ms"] else None
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", default="c2", choices=sorted(CONFIGS))
@@ -196,9 +244,16 @@ def main():
     ap.add_argument("--normalize", action="store_true", help="also time the brightness-normalised launch (with --fb: and its backward launch)")
     ap.add_argument("--affine", action="store_true", help="also time the affine refinement launch beside the forward launch")
     ap.add_argument("--search-radius", type=int, default=0, metavar="N", help="also time the search prepass launch at this radius beside the forward launch")
+    ap.add_argument("--mask-fraction", type=float, default=0.0, metavar="F",
+                    help="polygon mask over this fraction of the frame (0 < F <= 0.75) on frame1, before its detection, and on the targets")
+    ap.add_argument("--mask-windows", action="store_true", help="also time the masked windows beside the forward launch (needs --mask-fraction)")
     ap.add_argument("--shift", type=int, nargs=2, default=None, metavar=("DX", "DY"),
                     help="targets = frame1 rolled by whole pixels, (k DX / 8, k DY / 8) for skip k, instead of the clip's frames")
     args = ap.parse_args()
+    if args.mask_windows and not args.mask_fraction > 0:
+        ap.error("--mask-windows needs --mask-fraction")
+    if args.mask_fraction and not 0 < args.mask_fraction <= 0.75:
+        ap.error("--mask-fraction must be in (0, 0.75]")
 
     import torch
     from polychase_amd import hip, synth
@@ -217,6 +272,8 @@ def main():
         if args.shift and s:
             img = torch.roll(img, (s * args.shift[1] // 8, s * args.shift[0] // 8), (0, 1))
         f.set_rgb(img)
+        if args.mask_fraction > 0:
+            f.set_mask_polygons([mask_polygon(w, h, args.mask_fraction)])
         frames[s] = f
     f1 = frames[0]
     f1.detect()
@@ -259,6 +316,10 @@ def main():
         out["normalize"] = norm_timing(ctx, hip, f1, targets, fopt, args.fb, args.reps, ms / max(1, launches), st)
     if args.affine:
         out["affine"] = affine_timing(ctx, hip, f1, targets, fopt, args.reps, xy, st, err)
+    if args.mask_fraction > 0:
+        out["mask_fraction"] = args.mask_fraction
+    if args.mask_windows:
+        out["mask_windows"] = wmask_timing(ctx, hip, f1, targets, fopt, args.fb, args.reps, xy, st, err)
     if args.search_radius > 0:
         out["search"] = search_timing(ctx, hip, f1, targets, fopt, args.reps, args.search_radius, xy, st, err)
     if args.min_correlation > 0:      # (before --fb: that one leaves other keypoints on the target frames)
