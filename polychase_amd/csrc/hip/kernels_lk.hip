@@ -14,32 +14,30 @@ namespace pc {
 
 // The independent cross-check of the product kernels, every window 3 .. PC_MAX_WINDOW: one wavefront per keypoint (visiting order
 // p.perm), group g = lane / 8 tracks it into target g with plain_lk_pair (lk_plain.hpp) -- the template is evaluated per group,
-// nothing is shared across the wavefront, the target is gathered byte by byte.  A diagnostic, not a fast path.
+// nothing is shared across the wavefront, the target is gathered byte by byte.  A diagnostic, not a fast path.  The mapping and
+// the launch geometry are the ones of the kernels that follow the forward launch (lk_pair.hpp).
 template <bool X86>
 __global__ __launch_bounds__(256) void lk_plain_kernel(const LKParams p, const int win) {
     extern __shared__ __attribute__((aligned(16))) uint2 s_tmpl[];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int grp = lane >> 3, lg = lane & 7;
     lk_signal_dispatched(p);
-    const int slot = (int)blockIdx.x * (int)(blockDim.x >> 6) + wave;
-    if (slot >= p.n || grp >= p.n_targets) return;   // whole groups
-    const float2 pt = p.pts[p.perm ? (int)p.perm[slot] : slot];
+    LKPair q;
+    if (!lk_pair_prologue<false>(q, p)) return;   // whole wavefronts
+    if (!q.tgt_active) return;   // whole groups
+    const float2 pt = p.pts[q.feat];
     const auto level_of = [&](int level) {
         const Level L = p.src[level];
-        return PlainLKLevel{L.w, L.h, L.pitch, L.img, L.der, p.tgt[grp][level]};
+        return PlainLKLevel{L.w, L.h, L.pitch, L.img, L.der, p.tgt[q.grp][level]};
     };
-    const PlainLKResult r = plain_lk_pair<X86, true>(level_of, pt.x, pt.y, win, lg, p.max_level, p.max_iters, p.eps_sq, p.min_eig_thr,
-                                                     s_tmpl + (size_t)(wave * 8 + grp) * (win * win));
+    const PlainLKResult r = plain_lk_pair<X86, true>(level_of, pt.x, pt.y, win, q.lg, p.max_level, p.max_iters, p.eps_sq, p.min_eig_thr,
+                                                     s_tmpl + (size_t)(q.wave * 8 + q.grp) * (win * win));
     // one 16-byte record per (slot, target): the wavefront's results are contiguous
-    if (lg == 0) p.out_rec[(size_t)slot * kRecStride + grp] = make_float4(r.nx, r.ny, r.err, __uint_as_float(r.status ? 1u : 0u));
+    if (q.lg == 0) p.out_rec[(size_t)q.slot * kRecStride + q.grp] = make_float4(r.nx, r.ny, r.err, __uint_as_float(r.status ? 1u : 0u));
 }
 
 static bool launch_lk_plain(const LKParams& p, int win, hipStream_t s) {
-    if (win < 3 || win > PC_MAX_WINDOW) return false;
+    if (!lk_pair_args_ok(win, p.n_targets)) return false;
     if (p.n <= 0) return true;
-    const PlainLKLaunch g = plain_lk_launch(p.n, win);
-    if (p.x86_order) hipLaunchKernelGGL((lk_plain_kernel<true>), dim3(g.blocks), dim3(64 * g.waves), g.lds_bytes, s, p, win);
-    else hipLaunchKernelGGL((lk_plain_kernel<false>), dim3(g.blocks), dim3(64 * g.waves), g.lds_bytes, s, p, win);
+    launch_plain_geometry(p.x86_order ? lk_plain_kernel<true> : lk_plain_kernel<false>, p.n, win, s, p, win);
     return true;
 }
 

@@ -15,28 +15,13 @@
 // int64.  No pixel is read before its own floor passed the bounds test of the rule, which keeps all four taps inside the padding
 // (win rows, >= win columns), whatever the kernel is handed.  fp64 appears only in the factor, the two triangular solves and the
 // stop test.  Nothing crosses wavefronts: no barrier.  The window is a RUNTIME value (3 .. PC_MAX_WINDOW) and the arithmetic mode
-// plays no part: one instance.
+// plays no part: one instance.  Who a lane is, the walk of the window and the exact sums are lk_pair.hpp's.
 #include "lk_plain.hpp"
 
 namespace pc {
 
 constexpr int kAffWaves = 4;                                  // wavefronts (keypoints) per workgroup
 constexpr int kAffSlice = PC_MAX_WINDOW * PC_MAX_WINDOW;      // template entries per wavefront
-
-// sum over the group of per-lane signed 64-bit partials, exact (|total| < 2^47): three DPP sums of 16-bit-wide pieces
-__device__ __forceinline__ long long aff_group8_sum_s64(long long v) {
-    const int c0 = group_allreduce_add<8>((int)(v & 0xffff));
-    const int c1 = group_allreduce_add<8>((int)((v >> 16) & 0xffff));
-    const int c2 = group_allreduce_add<8>((int)(v >> 32));
-    return (long long)c2 * 4294967296ll + (long long)c1 * 65536ll + (long long)c0;
-}
-// sum over the wavefront of per-lane signed 64-bit partials, exact (|partial| < 2^47)
-__device__ __forceinline__ long long aff_wave_sum_s64(long long v) {
-    const int c0 = wave_sum_i32((int)(v & 0xffff));
-    const int c1 = wave_sum_i32((int)((v >> 16) & 0xffff));
-    const int c2 = wave_sum_i32((int)(v >> 32));
-    return (long long)c2 * 4294967296ll + (long long)c1 * 65536ll + (long long)c0;
-}
 
 // index of L[i][j], j <= i, in the packed lower triangle
 __device__ __forceinline__ constexpr int tri(int i, int j) { return i * (i + 1) / 2 + j; }
@@ -81,13 +66,13 @@ __device__ __forceinline__ bool affine_window(const uint8_t* __restrict__ J, int
         }
     }
     if (group_allreduce_add<8>(failed) != 0) return false;
-    b[0] = aff_group8_sum_s64(s0);
+    b[0] = group8_sum_s64(s0);   // |.| <= 961 * 2^26 * 30 < 2^47
     if constexpr (SOLVE) {
-        b[1] = aff_group8_sum_s64(s1);
-        b[2] = aff_group8_sum_s64(s2);
-        b[3] = aff_group8_sum_s64(s3);
-        b[4] = aff_group8_sum_s64(s4);
-        b[5] = aff_group8_sum_s64(s5);
+        b[1] = group8_sum_s64(s1);
+        b[2] = group8_sum_s64(s2);
+        b[3] = group8_sum_s64(s3);
+        b[4] = group8_sum_s64(s4);
+        b[5] = group8_sum_s64(s5);
     }
     return true;
 }
@@ -95,16 +80,12 @@ __device__ __forceinline__ bool affine_window(const uint8_t* __restrict__ J, int
 __global__ __launch_bounds__(64 * kAffWaves) void lk_affine_kernel(const AffineParams p) {
     __shared__ uint2 s_tm[kAffWaves][kAffSlice];
     __shared__ double s_L[kAffWaves][24];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int grp = lane >> 3, lg = lane & 7;
-    const int slot = (int)blockIdx.x * kAffWaves + wave;
-    if (slot >= p.n) return;   // whole wavefronts
-    const bool tgt_active = grp < p.n_targets;
-    float4 rec = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (tgt_active) rec = p.rec[(size_t)slot * kRecStride + grp];
-    const bool fwd_ok = tgt_active && __float_as_uint(rec.w) == 1u;   // uniform in the group
-    if (__ballot(fwd_ok) == 0ull) return;                             // uniform in the wavefront
-    const int feat = p.perm ? (int)p.perm[slot] : slot;
+    LKPair q;
+    if (!lk_pair_prologue<true, kAffWaves, false>(q, p)) return;   // whole wavefronts
+    if (__ballot(q.fwd_ok) == 0ull) return;                                  // uniform in the wavefront
+    lk_pair_keypoint(q, p.perm);
+    const int wave = q.wave, lane = q.lane, grp = q.grp, lg = q.lg;
+    const float4 rec = q.rec;
 
     const int win = p.win, n = win * win;
     const int w = p.f1.w, h = p.f1.h, pitch = p.f1.pitch;
@@ -112,20 +93,18 @@ __global__ __launch_bounds__(64 * kAffWaves) void lk_affine_kernel(const AffineP
     uint2* const tm = s_tm[wave];
     double* const Ls = s_L[wave];
 
-    // ---- template: all 64 lanes, pixel i = lane + 64 k at (r, c) = (i / win, i % win); H = sum g g^T, exact ----
-    const float2 pt = p.pts[feat];
+    // ---- template: all 64 lanes, pixel i at (r, c) = (i / win, i % win); H = sum g g^T, exact ----
+    const float2 pt = p.pts[q.feat];
     const float px = pt.x - half_win, py = pt.y - half_win;
     const int ipx = (int)floorf(px), ipy = (int)floorf(py);
-    bool can = !(ipx < -win || ipx >= w || ipy < -win || ipy >= h);   // uniform in the wavefront
+    bool can = !lk_window_outside(ipx, ipy, win, w, h);   // uniform in the wavefront
     if (can) {
         const Weights wI = bilinear_weights(px - (float)ipx, py - (float)ipy);
         const ptrdiff_t oI = (ptrdiff_t)ipy * pitch + ipx;
-        const int dy = 64 / win, dx = 64 - dy * win;   // what 64 pixels further means in rows and columns
         long long hs[21];
 #pragma unroll
         for (int k = 0; k < 21; k++) hs[k] = 0;
-        int r = lane / win, c = lane - r * win;
-        for (int i = lane; i < n; i += 64) {
+        for_each_window_pixel(lane, win, [&](int i, int r, int c) {
             const TemplatePixel t = template_pixel(p.f1.img, p.f1.der, pitch, oI + (ptrdiff_t)r * pitch + c, wI);
             tm[i] = pack_template(t);
             const int U = 2 * c - (win - 1), V = 2 * r - (win - 1);
@@ -135,17 +114,11 @@ __global__ __launch_bounds__(64 * kAffWaves) void lk_affine_kernel(const AffineP
             for (int a = 0; a < 6; a++)
 #pragma unroll
                 for (int bb = 0; bb <= a; bb++) hs[tri(a, bb)] += g[a] * g[bb];
-            c += dx;
-            r += dy;
-            if (c >= win) {
-                c -= win;
-                r++;
-            }
-        }
+        });
         // ---- factor: lower Cholesky of (double)H, column by column, the same in every lane ----
         double L[21];
 #pragma unroll
-        for (int k = 0; k < 21; k++) L[k] = (double)aff_wave_sum_s64(hs[k]);   // below 2^53: exact
+        for (int k = 0; k < 21; k++) L[k] = (double)wave_sum_s64(hs[k]);   // partials < 2^44; below 2^53: exact
 #pragma unroll
         for (int j = 0; j < 6; j++) {
             double s = L[tri(j, j)];
@@ -169,7 +142,7 @@ __global__ __launch_bounds__(64 * kAffWaves) void lk_affine_kernel(const AffineP
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");   // the groups read what the whole wavefront wrote
 
-    if (!fwd_ok) return;   // whole groups; nothing below crosses a group
+    if (!q.fwd_ok) return;   // whole groups; nothing below crosses a group
 
     // ---- the row: one group per target ----
     float cx = rec.x, cy = rec.y, m11 = 1.f, m12 = 0.f, m21 = 0.f, m22 = 1.f;
@@ -218,15 +191,14 @@ __global__ __launch_bounds__(64 * kAffWaves) void lk_affine_kernel(const AffineP
     }
 
     if (lg == 0) {
-        if (accepted) p.rec[(size_t)slot * kRecStride + grp] = make_float4(cx, cy, err_a, __uint_as_float(1u));
-        const size_t o = (size_t)grp * (size_t)p.n + (size_t)feat;
-        if (p.affine_m) p.affine_m[o] = make_float4(m11, m12, m21, m22);
-        if (p.affine_state) p.affine_state[o] = accepted ? (uint8_t)1 : (uint8_t)2;
+        if (accepted) p.rec[(size_t)q.slot * kRecStride + grp] = make_float4(cx, cy, err_a, __uint_as_float(1u));
+        if (p.affine_m) p.affine_m[q.side(p.n)] = make_float4(m11, m12, m21, m22);
+        if (p.affine_state) p.affine_state[q.side(p.n)] = accepted ? (uint8_t)1 : (uint8_t)2;
     }
 }
 
 bool launch_lk_affine(const AffineParams& p, hipStream_t s) {
-    if (p.win < 3 || p.win > PC_MAX_WINDOW || p.n_targets < 1 || p.n_targets > kRecStride) return false;
+    if (!lk_pair_args_ok(p.win, p.n_targets)) return false;
     if (p.n <= 0) return true;
     hipLaunchKernelGGL(lk_affine_kernel, dim3((unsigned)((p.n + kAffWaves - 1) / kAffWaves)), dim3(64 * kAffWaves), 0, s, p);
     return true;

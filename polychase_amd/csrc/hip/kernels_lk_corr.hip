@@ -14,20 +14,13 @@
 // walking whole window columns so that the bottom taps of a row are the top taps of the next.  No window is read before it passed
 // OpenCV's bounds test on the same floats, so every read lies inside the padding (win rows, >= win columns).  Nothing crosses
 // wavefronts: no barrier.  The window is a RUNTIME value (3 .. PC_MAX_WINDOW) and the arithmetic mode plays no part: one instance.
+// Who a lane is, the bounds test, the walk of the I window and the exact sums are lk_pair.hpp's.
 #include "lk_plain.hpp"
 
 namespace pc {
 
 constexpr int kCorrWaves = 4;                                              // wavefronts (keypoints) per workgroup
 constexpr int kCorrSlice = (PC_MAX_WINDOW * PC_MAX_WINDOW + 1) & ~1;       // int16 entries per wavefront, a whole number of dwords
-
-// sum over the group of non-negative per-lane 64-bit partials (< 2^47), exact: three DPP sums of 16-bit-wide pieces
-__device__ __forceinline__ long long group8_sum_i64(unsigned long long v) {
-    const int c0 = group_allreduce_add<8>((int)(v & 0xffffull));
-    const int c1 = group_allreduce_add<8>((int)((v >> 16) & 0xffffull));
-    const int c2 = group_allreduce_add<8>((int)(v >> 32));
-    return (long long)c2 * 4294967296ll + (long long)c1 * 65536ll + (long long)c0;
-}
 
 __global__ __launch_bounds__(64 * kCorrWaves) void lk_corr_kernel(const CorrParams p) {
     __shared__ int16_t s_win[kCorrWaves][kCorrSlice];
@@ -47,7 +40,7 @@ __global__ __launch_bounds__(64 * kCorrWaves) void lk_corr_kernel(const CorrPara
     const float half_win = (float)(win - 1) * 0.5f;
     int16_t* const iwin = s_win[wave];
 
-    // ---- I window: all 64 lanes, pixel i = lane + 64 k at (y, x) = (i / win, i % win) ----
+    // ---- I window: all 64 lanes, pixel i at (y, x) = (i / win, i % win) ----
     bool i_ok = false;
     int sI = 0;
     long long sII = 0;
@@ -55,28 +48,20 @@ __global__ __launch_bounds__(64 * kCorrWaves) void lk_corr_kernel(const CorrPara
         const float2 pt = p.pts[feat];
         const float px = pt.x - half_win, py = pt.y - half_win;
         const int ipx = (int)floorf(px), ipy = (int)floorf(py);
-        i_ok = !(ipx < -win || ipx >= w || ipy < -win || ipy >= h);
+        i_ok = !lk_window_outside(ipx, ipy, win, w, h);
         if (i_ok) {
             const Weights wI = bilinear_weights(px - (float)ipx, py - (float)ipy);
             const uint8_t* const ib = p.f1.img + (ptrdiff_t)ipy * pitch + ipx;
-            const int dy = 64 / win, dx = 64 - dy * win;   // what 64 pixels further means in rows and columns
-            int y = lane / win, x = lane - y * win;
             uint32_t s1 = 0u, s2 = 0u;                      // <= 16 pixels per lane: 16 * 8160^2 < 2^31
-            for (int i = lane; i < n; i += 64) {
+            for_each_window_pixel(lane, win, [&](int i, int y, int x) {
                 const uint8_t* const s = ib + (ptrdiff_t)y * pitch + x;
                 const int v = interp_u8(s[0], s[1], s[pitch], s[pitch + 1], wI);   // 0 .. 8160
                 iwin[i] = (int16_t)v;
                 s1 += (uint32_t)v;
                 s2 += (uint32_t)(v * v);
-                x += dx;
-                y += dy;
-                if (x >= win) {
-                    x -= win;
-                    y++;
-                }
-            }
+            });
             sI = wave_sum_i32((int)s1);                     // <= 961 * 8160 < 2^23
-            sII = (long long)wave_sum_i32((int)(s2 >> 16)) * 65536ll + (long long)wave_sum_i32((int)(s2 & 0xffffu));
+            sII = wave_sum_u32(s2);
         }
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");   // the groups read what the whole wavefront wrote
@@ -87,11 +72,11 @@ __global__ __launch_bounds__(64 * kCorrWaves) void lk_corr_kernel(const CorrPara
     if (fwd_ok && i_ok) {
         const float qx = rec.x - half_win, qy = rec.y - half_win;
         const int iqx = (int)floorf(qx), iqy = (int)floorf(qy);
-        if (!(iqx < -win || iqx >= w || iqy < -win || iqy >= h)) {
+        if (!lk_window_outside(iqx, iqy, win, w, h)) {
             const Weights wJ = bilinear_weights(qx - (float)iqx, qy - (float)iqy);
             const uint8_t* const jb = p.timg[grp] + (ptrdiff_t)iqy * pitch + iqx;
             int sJ = 0;
-            unsigned long long sJJ = 0ull, sIJ = 0ull;
+            long long sJJ = 0, sIJ = 0;   // non-negative
             for (int x = lg; x < win; x += 8) {
                 const uint8_t* s = jb + x;
                 int t0 = s[0], t1 = s[1];
@@ -111,7 +96,7 @@ __global__ __launch_bounds__(64 * kCorrWaves) void lk_corr_kernel(const CorrPara
                 sIJ += cIJ;
             }
             const long long SJ = (long long)group_allreduce_add<8>(sJ);   // <= 961 * 8160
-            const long long SJJ = group8_sum_i64(sJJ), SIJ = group8_sum_i64(sIJ);
+            const long long SJJ = group8_sum_s64(sJJ), SIJ = group8_sum_s64(sIJ);   // 961 * 8160^2 < 2^47
             const long long nn = (long long)n, SI = (long long)sI;
             const long long cov = nn * SIJ - SI * SJ;                     // |.| <= 961 * 961 * 8160^2 < 2^46
             const long long vI = nn * sII - SI * SI, vJ = nn * SJJ - SJ * SJ;
@@ -130,7 +115,7 @@ __global__ __launch_bounds__(64 * kCorrWaves) void lk_corr_kernel(const CorrPara
 }
 
 bool launch_lk_corr(const CorrParams& p, hipStream_t s) {
-    if (p.win < 3 || p.win > PC_MAX_WINDOW || p.n_targets < 1 || p.n_targets > kRecStride) return false;
+    if (!lk_pair_args_ok(p.win, p.n_targets)) return false;
     if (p.n <= 0) return true;
     hipLaunchKernelGGL(lk_corr_kernel, dim3((unsigned)((p.n + kCorrWaves - 1) / kCorrWaves)), dim3(64 * kCorrWaves), 0, s, p);
     return true;

@@ -6,14 +6,17 @@
 // backward pass fails or lands further than the threshold from the keypoint it started at.  Everything downstream of the
 // records (compaction, unpacking) is unchanged.
 //
-// Mapping: one wavefront per keypoint (visiting order of the forward launch), one group of 8 lanes per target.  The pass itself
-// is plain_lk_pair (lk_plain.hpp) with the roles of the images swapped: the template of every pair comes from the target's
-// planes at the forward end point, the searched image is frame1.  Pairs with status_f == 0 do no work; a wavefront without a
-// surviving pair only writes its zeros to the side arrays.
-#include "lk_plain.hpp"
+// Mapping: one wavefront per keypoint (visiting order of the forward launch), one group of 8 lanes per target.  The decision and
+// the side arrays are those of lk_fb_body (lk_fb.hpp), which the backward kernels of the options are built from; the pass itself is plain_lk_pair
+// (lk_plain.hpp) with the roles of the images swapped: the template of every pair comes from the target's planes at the forward
+// end point, the searched image is frame1.  Pairs with status_f == 0 do no work; a wavefront without a surviving pair only writes
+// its zeros to the side arrays.
+#include "lk_fb.hpp"
 
 namespace pc {
 
+// lk_fb_body<FBRows::NotReplaced> written out: built from the shared body the x86-order instance allocates 79 VGPRs instead of its
+// 78, whichever way the body is spelled, so this one kernel keeps its text.  What it decides and writes is what lk_fb_body does.
 template <bool X86>
 __global__ __launch_bounds__(256) void lk_fb_kernel(const LKFBParams p) {
     extern __shared__ __attribute__((aligned(16))) uint2 s_tmpl[];
@@ -32,10 +35,7 @@ __global__ __launch_bounds__(256) void lk_fb_kernel(const LKFBParams p) {
     float nx = 0.f, ny = 0.f;
     bool status = false;
     if (fwd_ok) {
-        const auto level_of = [&](int level) {
-            const Level L = p.f1[level];
-            return PlainLKLevel{L.w, L.h, L.pitch, p.timg[grp][level], p.tder[grp][level], L.img};
-        };
+        const auto level_of = [&](int level) { return lk_fb_level(p, grp, level); };
         const PlainLKResult r = plain_lk_pair<X86, false>(level_of, rec.x, rec.y, p.win, lg, p.max_level, p.max_iters, p.eps_sq, p.min_eig_thr,
                                                           s_tmpl + (size_t)(wave * 8 + grp) * (p.win * p.win));
         nx = r.nx;
@@ -58,11 +58,9 @@ __global__ __launch_bounds__(256) void lk_fb_kernel(const LKFBParams p) {
 }
 
 bool launch_lk_fb(const LKFBParams& p, hipStream_t s) {
-    if (p.win < 3 || p.win > PC_MAX_WINDOW || p.n_targets < 1 || p.n_targets > kRecStride) return false;
+    if (!lk_pair_args_ok(p.win, p.n_targets)) return false;
     if (p.n <= 0) return true;
-    const PlainLKLaunch g = plain_lk_launch(p.n, p.win);
-    if (p.x86_order) hipLaunchKernelGGL((lk_fb_kernel<true>), dim3(g.blocks), dim3(64 * g.waves), g.lds_bytes, s, p);
-    else hipLaunchKernelGGL((lk_fb_kernel<false>), dim3(g.blocks), dim3(64 * g.waves), g.lds_bytes, s, p);
+    launch_plain_geometry(p.x86_order ? lk_fb_kernel<true> : lk_fb_kernel<false>, p.n, p.win, s, p);
     return true;
 }
 

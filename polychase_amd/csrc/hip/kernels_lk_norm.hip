@@ -2,7 +2,8 @@
 // DESIGN.md section 4 "Brightness normalisation"): the forward launch and the backward launch of the forward-backward check when
 // the option is on.  Both leave exactly what the kernels they stand in for leave -- the raw records
 // out_rec[slot * 8 + target] = (q, err, status_f), the back arrays --, so everything downstream is unchanged.  The body is
-// norm_lk_pair (lk_norm.hpp).
+// norm_lk_pair (lk_norm.hpp); the backward launch's decision is lk_fb_body (lk_fb.hpp).
+#include "lk_fb.hpp"
 #include "lk_norm.hpp"
 
 namespace pc {
@@ -17,67 +18,34 @@ constexpr int kNormWaves = 4;   // wavefronts (keypoints) per workgroup of the f
 // the padding (win rows, >= win columns).
 __global__ __launch_bounds__(64 * kNormWaves) void lk_norm_kernel(const LKParams p, const int win) {
     extern __shared__ __attribute__((aligned(16))) uint2 s_tmpl[];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int grp = lane >> 3;
     lk_signal_dispatched(p);
-    const int slot = (int)blockIdx.x * kNormWaves + wave;
-    if (slot >= p.n) return;   // whole wavefronts
-    const bool active = grp < p.n_targets;
-    const float2 pt = p.pts[p.perm ? (int)p.perm[slot] : slot];
+    LKPair q;
+    if (!lk_pair_prologue<false, kNormWaves>(q, p)) return;   // whole wavefronts
+    const float2 pt = p.pts[q.feat];
     const auto level_of = [&](int level) {
         const Level L = p.src[level];
-        return PlainLKLevel{L.w, L.h, L.pitch, L.img, L.der, p.tgt[grp][level]};
+        return PlainLKLevel{L.w, L.h, L.pitch, L.img, L.der, p.tgt[q.grp][level]};
     };
-    const PlainLKResult r = norm_lk_pair<true, true>(level_of, pt.x, pt.y, win, lane, active, p.max_level, p.max_iters, p.eps_sq,
-                                                     p.min_eig_thr, s_tmpl + (size_t)wave * (win * win));
+    const PlainLKResult r = norm_lk_pair<true, true>(level_of, pt.x, pt.y, win, q.lane, q.tgt_active, p.max_level, p.max_iters, p.eps_sq,
+                                                     p.min_eig_thr, s_tmpl + (size_t)q.wave * (win * win));
     // one 16-byte record per (slot, target): the wavefront's results are contiguous
-    if ((lane & 7) == 0 && active) p.out_rec[(size_t)slot * kRecStride + grp] = make_float4(r.nx, r.ny, r.err, __uint_as_float(r.status ? 1u : 0u));
+    if (q.lg == 0 && q.tgt_active)
+        p.out_rec[(size_t)q.slot * kRecStride + q.grp] = make_float4(r.nx, r.ny, r.err, __uint_as_float(r.status ? 1u : 0u));
 }
 
-// Backward: lk_fb_kernel's mapping and parameters with the normalised body; the template of every pair comes from the target's
-// planes at the forward end point (per group), the searched image is frame1.
+// Backward: lk_fb_kernel's mapping, parameters, decision and side arrays (lk_fb.hpp) with the normalised body; it owns every
+// row.  The template of every pair comes from the target's planes at the forward end point (per group), the searched image is
+// frame1.
 __global__ __launch_bounds__(256) void lk_norm_fb_kernel(const LKFBParams p) {
     extern __shared__ __attribute__((aligned(16))) uint2 s_tmpl[];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int grp = lane >> 3, lg = lane & 7;
-    const int slot = (int)blockIdx.x * (int)(blockDim.x >> 6) + wave;
-    if (slot >= p.n) return;   // whole wavefronts
-    const bool tgt_active = grp < p.n_targets;
-    float4 rec = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (tgt_active) rec = p.rec[(size_t)slot * kRecStride + grp];
-    const bool fwd_ok = tgt_active && __float_as_uint(rec.w) == 1u;   // uniform in the group
-    const int feat = p.perm ? (int)p.perm[slot] : slot;
-
-    float nx = 0.f, ny = 0.f;
-    bool status = false;
-    if (fwd_ok) {
-        const auto level_of = [&](int level) {
-            const Level L = p.f1[level];
-            return PlainLKLevel{L.w, L.h, L.pitch, p.timg[grp][level], p.tder[grp][level], L.img};
-        };
-        const PlainLKResult r = norm_lk_pair<false, false>(level_of, rec.x, rec.y, p.win, lane, true, p.max_level, p.max_iters, p.eps_sq,
-                                                           p.min_eig_thr, s_tmpl + (size_t)(wave * 8 + grp) * (p.win * p.win));
-        nx = r.nx;
-        ny = r.ny;
-        status = r.status;
-    }
-
-    if (lg == 0 && tgt_active) {
-        if (fwd_ok) {
-            const float2 pt = p.pts[feat];
-            const float dx = nx - pt.x, dy = ny - pt.y;
-            const float d2 = dx * dx + dy * dy;
-            const bool keep = status && (d2 <= p.thr2);   // a NaN fails
-            if (!keep) p.rec[(size_t)slot * kRecStride + grp].w = __uint_as_float(0u);
-        }
-        const size_t o = (size_t)grp * (size_t)p.n + (size_t)feat;
-        if (p.back_xy) p.back_xy[o] = fwd_ok ? make_float2(nx, ny) : make_float2(0.f, 0.f);
-        if (p.back_status) p.back_status[o] = (fwd_ok && status) ? (uint8_t)1 : (uint8_t)0;
-    }
+    lk_fb_body<FBRows::All>(p, s_tmpl, [&](const LKPair& q, uint2* tm) {
+        const auto level_of = [&](int level) { return lk_fb_level(p, q.grp, level); };
+        return norm_lk_pair<false, false>(level_of, q.rec.x, q.rec.y, p.win, q.lane, true, p.max_level, p.max_iters, p.eps_sq, p.min_eig_thr, tm);
+    });
 }
 
 bool launch_lk_norm(const LKParams& p, int win, hipStream_t s) {
-    if (win < 3 || win > PC_MAX_WINDOW || p.n_targets < 1 || p.n_targets > kRecStride) return false;
+    if (!lk_pair_args_ok(win, p.n_targets)) return false;
     if (p.n <= 0) return true;
     const size_t lds_bytes = (size_t)kNormWaves * win * win * sizeof(uint2);   // <= 30752
     hipLaunchKernelGGL(lk_norm_kernel, dim3((unsigned)((p.n + kNormWaves - 1) / kNormWaves)), dim3(64 * kNormWaves), lds_bytes, s, p, win);
@@ -85,10 +53,9 @@ bool launch_lk_norm(const LKParams& p, int win, hipStream_t s) {
 }
 
 bool launch_lk_norm_fb(const LKFBParams& p, hipStream_t s) {
-    if (p.win < 3 || p.win > PC_MAX_WINDOW || p.n_targets < 1 || p.n_targets > kRecStride) return false;
+    if (!lk_pair_args_ok(p.win, p.n_targets)) return false;
     if (p.n <= 0) return true;
-    const PlainLKLaunch g = plain_lk_launch(p.n, p.win);
-    hipLaunchKernelGGL(lk_norm_fb_kernel, dim3(g.blocks), dim3(64 * g.waves), g.lds_bytes, s, p);
+    launch_plain_geometry(lk_norm_fb_kernel, p.n, p.win, s, p);
     return true;
 }
 

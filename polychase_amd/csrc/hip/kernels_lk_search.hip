@@ -23,8 +23,8 @@
 //
 // lk_search_fb_kernel: the backward pass of the forward-backward check for the rows the search replaced (state 1), the same
 // canonical body with the roles of the images swapped and the top level started at q - d; lk_fb_kernel (kernels_lk_fb.hip) leaves
-// those rows to it.
-#include "lk_plain.hpp"
+// those rows to it, and the decision and the side arrays are the ones both share (lk_fb.hpp: lk_fb_body).
+#include "lk_fb.hpp"
 
 namespace pc {
 
@@ -84,13 +84,11 @@ __device__ __forceinline__ unsigned long long group8_min_u64(unsigned long long 
 
 __global__ __launch_bounds__(256) void lk_search_kernel(const SearchParams p) {
     extern __shared__ __attribute__((aligned(16))) uint8_t s_search[];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int grp = lane >> 3, lg = lane & 7;
-    const int slot = (int)blockIdx.x * (int)(blockDim.x >> 6) + wave;
-    if (slot >= p.n) return;   // whole wavefronts
-    const bool tgt_active = grp < p.n_targets;
-    const int feat = p.perm ? (int)p.perm[slot] : slot;
-    const size_t o = (size_t)grp * (size_t)p.n + (size_t)feat;
+    LKPair q;   // the record is read last, by one lane
+    if (!lk_pair_prologue<false>(q, p)) return;   // whole wavefronts
+    const int wave = q.wave, lane = q.lane, grp = q.grp, lg = q.lg, slot = q.slot, feat = q.feat;
+    const bool tgt_active = q.tgt_active;
+    const size_t o = q.side(p.n);
     const int r = p.r, s = p.s;
     uint8_t* const wmem = s_search + (size_t)wave * search_wave_bytes(r, p.win);
     uint8_t* const slice = wmem + 64 + grp * search_slice_bytes(r, p.win);
@@ -173,43 +171,12 @@ __global__ __launch_bounds__(256) void lk_search_kernel(const SearchParams p) {
 
 __global__ __launch_bounds__(256) void lk_search_fb_kernel(const LKFBParams p) {
     extern __shared__ __attribute__((aligned(16))) uint2 s_tmpl[];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int grp = lane >> 3, lg = lane & 7;
-    const int slot = (int)blockIdx.x * (int)(blockDim.x >> 6) + wave;
-    if (slot >= p.n) return;   // whole wavefronts
-    if (grp >= p.n_targets) return;   // whole groups; nothing below crosses a group
-    const int feat = p.perm ? (int)p.perm[slot] : slot;
-    const size_t o = (size_t)grp * (size_t)p.n + (size_t)feat;
-    if (p.search_state[o] != 1) return;   // lk_fb_kernel's row
-    const float4 rec = p.rec[(size_t)slot * kRecStride + grp];
-    const bool fwd_ok = __float_as_uint(rec.w) == 1u;   // a check in between may have dropped the row
-
-    float nx = 0.f, ny = 0.f;
-    bool status = false;
-    if (fwd_ok) {
-        const short2 d = p.search_d[o];
-        const auto level_of = [&](int level) {
-            const Level L = p.f1[level];
-            return PlainLKLevel{L.w, L.h, L.pitch, p.timg[grp][level], p.tder[grp][level], L.img};
-        };
-        const PlainLKResult r = plain_lk_pair<false, false, true>(level_of, rec.x, rec.y, p.win, lg, p.max_level, p.max_iters, p.eps_sq,
-                                                                  p.min_eig_thr, s_tmpl + (size_t)(wave * 8 + grp) * (p.win * p.win),
-                                                                  rec.x - (float)d.x, rec.y - (float)d.y);
-        nx = r.nx;
-        ny = r.ny;
-        status = r.status;
-    }
-    if (lg == 0) {
-        if (fwd_ok) {
-            const float2 pt = p.pts[feat];
-            const float dx = nx - pt.x, dy = ny - pt.y;
-            const float d2 = dx * dx + dy * dy;
-            const bool keep = status && (d2 <= p.thr2);   // a NaN fails
-            if (!keep) p.rec[(size_t)slot * kRecStride + grp].w = __uint_as_float(0u);
-        }
-        if (p.back_xy) p.back_xy[o] = fwd_ok ? make_float2(nx, ny) : make_float2(0.f, 0.f);
-        if (p.back_status) p.back_status[o] = (fwd_ok && status) ? (uint8_t)1 : (uint8_t)0;
-    }
+    lk_fb_body<FBRows::Replaced>(p, s_tmpl, [&](const LKPair& q, uint2* tm) {
+        const short2 d = p.search_d[q.side(p.n)];
+        const auto level_of = [&](int level) { return lk_fb_level(p, q.grp, level); };
+        return plain_lk_pair<false, false, true>(level_of, q.rec.x, q.rec.y, p.win, q.lg, p.max_level, p.max_iters, p.eps_sq, p.min_eig_thr, tm,
+                                                 q.rec.x - (float)d.x, q.rec.y - (float)d.y);
+    });
 }
 
 void search_level_radius(int search_radius, int top_level, int* s, int* r) {
@@ -220,7 +187,7 @@ void search_level_radius(int search_radius, int top_level, int* s, int* r) {
 }
 
 bool launch_lk_search(const SearchParams& p, hipStream_t s) {
-    if (p.win < 3 || p.win > PC_MAX_WINDOW || p.n_targets < 1 || p.n_targets > kRecStride) return false;
+    if (!lk_pair_args_ok(p.win, p.n_targets)) return false;
     if (p.r < 1 || p.r > kSearchMaxR || p.s < 0 || p.s > p.max_level) return false;
     // the region is staged in aligned dwords
     if (p.src[p.s].pitch & 3) return false;
@@ -235,11 +202,10 @@ bool launch_lk_search(const SearchParams& p, hipStream_t s) {
 }
 
 bool launch_lk_search_fb(const LKFBParams& p, hipStream_t s) {
-    if (p.win < 3 || p.win > PC_MAX_WINDOW || p.n_targets < 1 || p.n_targets > kRecStride) return false;
+    if (!lk_pair_args_ok(p.win, p.n_targets)) return false;
     if (!p.search_d || !p.search_state) return false;
     if (p.n <= 0) return true;
-    const PlainLKLaunch g = plain_lk_launch(p.n, p.win);
-    hipLaunchKernelGGL(lk_search_fb_kernel, dim3(g.blocks), dim3(64 * g.waves), g.lds_bytes, s, p);
+    launch_plain_geometry(lk_search_fb_kernel, p.n, p.win, s, p);
     return true;
 }
 

@@ -1,7 +1,7 @@
 // lk_norm.hpp -- brightness-normalised pyramidal Lucas-Kanade of ONE point (include/polychase_hip.h: pc_lk_track_normalized has
 // the rule; tests/lk_normalized_ref.py restates it in numpy).  It is plain_lk_pair (lk_plain.hpp) level by level -- bounds tests,
 // bilinear weights, template_pixel, interp_u8, the 2x2 solve, the epsilon test, the oscillation exit and the level-0 L1 patch
-// error are the same fp32 / integer expressions -- with two replacements: the structure tensor is the CENTRED Gram matrix of the
+// error are the same fp32 / integer expressions, the shared ones the same functions (lk_pair.hpp) -- with two replacements: the structure tensor is the CENTRED Gram matrix of the
 // template's gradients, and the mismatch vector is that of g (J - mean J) - (I - mean I), g the ratio of the two windows'
 // standard deviations.  All window sums are exact integers; fp64 appears only in the handful of scalars per level / iteration,
 // every operation rounded on its own.  The arithmetic mode plays no part: one instance.
@@ -15,22 +15,6 @@
 #include "lk_plain.hpp"
 
 namespace pc {
-
-// sum over the group of per-lane 64-bit partials, exact (|total| < 2^47): v = (v >> 32) 2^32 + ((v >> 16) & 0xffff) 2^16 +
-// (v & 0xffff) in two's complement, three DPP sums
-__device__ __forceinline__ long long group8_sum_s64(long long v) {
-    const int c0 = group_allreduce_add<8>((int)(v & 0xffff));
-    const int c1 = group_allreduce_add<8>((int)((v >> 16) & 0xffff));
-    const int c2 = group_allreduce_add<8>((int)(v >> 32));
-    return (long long)c2 * 4294967296ll + (long long)c1 * 65536ll + (long long)c0;
-}
-// sum over the wavefront of per-lane 32-bit partials, exact in 64 bits
-__device__ __forceinline__ long long wave_sum_s32(int v) {
-    return (long long)wave_sum_i32(v >> 16) * 65536ll + (long long)wave_sum_i32(v & 0xffff);
-}
-__device__ __forceinline__ long long wave_sum_u32(uint32_t v) {
-    return (long long)wave_sum_i32((int)(v >> 16)) * 65536ll + (long long)wave_sum_i32((int)(v & 0xffffu));
-}
 
 // what a level's template leaves for its iterations
 struct NormTemplate {
@@ -93,7 +77,7 @@ __device__ __forceinline__ PlainLKResult norm_lk_pair(const LevelOf& level_of, f
         px -= half_win;
         py -= half_win;
         const int ipx = (int)floorf(px), ipy = (int)floorf(py);
-        if (ipx < -win || ipx >= L.w || ipy < -win || ipy >= L.h) {
+        if (lk_window_outside(ipx, ipy, win, L.w, L.h)) {
             if (level == 0) status = false;
             continue;
         }
@@ -101,12 +85,10 @@ __device__ __forceinline__ PlainLKResult norm_lk_pair(const LevelOf& level_of, f
         const ptrdiff_t oI = (ptrdiff_t)ipy * pitch + ipx;
         NormTemplate T;
         if constexpr (WAVE) {
-            // pixel i = lane + 64 k at (y, x) = (i / win, i % win); <= 16 pixels per lane: 16 * 8160^2 < 2^31
-            const int dy = 64 / win, dx = 64 - dy * win;   // what 64 pixels further means in rows and columns
-            int y = lane / win, x = lane - y * win;
+            // <= 16 pixels per lane: 16 * 8160^2 < 2^31
             int sI = 0, sx = 0, sy = 0, sxy = 0, sIx = 0, sIy = 0;
             uint32_t sII = 0u, sxx = 0u, syy = 0u;
-            for (int i = lane; i < n; i += 64) {
+            for_each_window_pixel(lane, win, [&](int i, int y, int x) {
                 const TemplatePixel t = template_pixel(I, dI, pitch, oI + (ptrdiff_t)y * pitch + x, wI);
                 tm[i] = pack_template(t);
                 sI += t.ival;
@@ -118,13 +100,7 @@ __device__ __forceinline__ PlainLKResult norm_lk_pair(const LevelOf& level_of, f
                 syy += (uint32_t)(t.iy * t.iy);
                 sIx += t.ival * t.ix;
                 sIy += t.ival * t.iy;
-                x += dx;
-                y += dy;
-                if (x >= win) {
-                    x -= win;
-                    y++;
-                }
-            }
+            });
             T = norm_template(n, (long long)wave_sum_i32(sI), wave_sum_u32(sII), (long long)wave_sum_i32(sx), (long long)wave_sum_i32(sy),
                               wave_sum_u32(sxx), wave_sum_s32(sxy), wave_sum_u32(syy), wave_sum_s32(sIx), wave_sum_s32(sIy));
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");   // the groups read what the whole wavefront wrote
@@ -169,7 +145,7 @@ __device__ __forceinline__ PlainLKResult norm_lk_pair(const LevelOf& level_of, f
             float pdx = 0.f, pdy = 0.f;
             for (int j = 0; j < max_iters; j++) {
                 const int iqx = (int)floorf(qx), iqy = (int)floorf(qy);
-                if (iqx < -win || iqx >= L.w || iqy < -win || iqy >= L.h) {
+                if (lk_window_outside(iqx, iqy, win, L.w, L.h)) {
                     if (level == 0) status = false;
                     break;
                 }
@@ -206,27 +182,14 @@ __device__ __forceinline__ PlainLKResult norm_lk_pair(const LevelOf& level_of, f
                 if (T.vI > 0 && vJ > 0) g = fminf(fmaxf((float)sqrt((double)T.vI / (double)vJ), 0.25f), 4.f);
                 const float b1 = (float)(((double)g * (double)CJx - (double)T.CIx) / dn) * FLT_SCALE;
                 const float b2 = (float)(((double)g * (double)CJy - (double)T.CIy) / dn) * FLT_SCALE;
-                const float dx = (A12 * b2 - A22 * b1) * D;
-                const float dy = (A12 * b1 - A11 * b2) * D;
-                qx += dx;
-                qy += dy;
-                nx = qx + half_win;
-                ny = qy + half_win;
-                if ((double)dx * (double)dx + (double)dy * (double)dy <= eps_sq) break;
-                if (j > 0 && fabs((double)(dx + pdx)) < 0.01 && fabs((double)(dy + pdy)) < 0.01) {
-                    nx -= dx * 0.5f;
-                    ny -= dy * 0.5f;
-                    break;
-                }
-                pdx = dx;
-                pdy = dy;
+                if (lk_newton_step(A11, A12, A22, D, b1, b2, half_win, j, eps_sq, qx, qy, nx, ny, pdx, pdy)) break;
             }
 
             // ---- L1 patch error at level 0: OpenCV's, un-normalised ----
             if (status && level == 0) {
                 const float ex = nx - half_win, ey = ny - half_win;
                 const int iex = (int)floorf(ex), iey = (int)floorf(ey);
-                if (iex < -win || iex >= L.w || iey < -win || iey >= L.h) {
+                if (lk_window_outside(iex, iey, win, L.w, L.h)) {
                     status = false;
                 } else if constexpr (ERR) {
                     const Weights wE = bilinear_weights(ex - (float)iex, ey - (float)iey);

@@ -1,9 +1,16 @@
 // lk_plain.hpp -- pyramidal Lucas-Kanade of ONE point by ONE group of 8 lanes, written the way oracle/pc_oracle.c's pco_lk reads:
 // calcOpticalFlowPyrLK(prev = the template image, next = the searched image, pts = {start}), bit for bit in either arithmetic
-// order.  Two kernels are built from it: the forward cross-check of the product kernels (kernels_lk.hip: lk_plain_kernel, template
-// = frame1, searched = a target, with the patch error) and the backward pass of the forward-backward check (kernels_lk_fb.hip:
-// lk_fb_kernel, template = a target, searched = frame1, no patch error).  The two kernels of the masked windows
-// (kernels_lk_wmask.hip; include/polychase_hip.h: pc_lk_track_window_masked has the rule) are the MASKED instances of the same body.
+// order.  Ten kernel instances are built from it:
+//   lk_plain_kernel<X86>      kernels_lk.hip        the forward cross-check of the product kernels: template = frame1, searched = a
+//                                                   target, with the patch error
+//   lk_fb_kernel<X86>         kernels_lk_fb.hip     the backward pass of the forward-backward check (lk_fb.hpp): template = a target,
+//                                                   searched = frame1, no patch error
+//   lk_search_kernel          kernels_lk_search.hip the guided pass of the search prepass (GUESS), and
+//   lk_search_fb_kernel                             the backward pass of the rows it replaced
+//   lk_wmask_kernel<X86>      kernels_lk_wmask.hip  the MASKED instances (include/polychase_hip.h: pc_lk_track_window_masked has the
+//   lk_wmask_fb_kernel<X86>                         rule), forward and backward
+// and lk_norm.hpp restates it level by level for the brightness-normalised pair.  Who a lane is, the bounds test, the exact sums,
+// the Newton step and the launch geometry are lk_pair.hpp's, shared with the kernels that only read the records.
 //
 // The group evaluates its own win x win template (patch value + Scharr pair per pixel) per level and keeps it in its own slice of
 // LDS, 8 bytes per pixel; the searched image is gathered straight from the padded u8 plane: a window that passed OpenCV's bounds
@@ -12,10 +19,7 @@
 // COLUMNS in every phase).  The window is a RUNTIME value (3 .. PC_MAX_WINDOW): one instance per arithmetic order.
 #pragma once
 
-#include <algorithm>
-
-#include "../../../include/polychase_hip.h"
-#include "lk_common.hpp"
+#include "lk_pair.hpp"
 
 namespace pc {
 
@@ -75,16 +79,6 @@ __device__ __forceinline__ int pixel_diff(const uint8_t* __restrict__ s, int pit
     return interp_u8(s[0], s[1], s[pitch], s[pitch + 1], w) - (int)ival;
 }
 
-// Sum over the group of per-lane 64-bit partials (|total| < 2^40) as ONE rounding of the exact integer: three 16-bit-wide
-// DPP sums, the total rebuilt in 64 bits, then hi * 2^16 + lo with both terms exact in fp32.
-__device__ __forceinline__ float group8_exact_sum_i64(long long v) {
-    const int c0 = group_allreduce_add<8>((int)(v & 0xffff));
-    const int c1 = group_allreduce_add<8>((int)((v >> 16) & 0xffff));
-    const int c2 = group_allreduce_add<8>((int)(v >> 32));
-    const long long t = (long long)c2 * 4294967296ll + (long long)c1 * 65536ll + (long long)c0;
-    return exact_sum_to_float((int)(t >> 16), (int)(t & 0xffff));
-}
-
 // level_of(level) -> PlainLKLevel; lg: the lane's index in its group; tm: the group's LDS slice, win * win entries.
 // Every lane of the group returns the same result.
 //
@@ -134,7 +128,7 @@ __device__ __forceinline__ PlainLKResult plain_lk_pair(const LevelOf& level_of, 
         px -= half_win;
         py -= half_win;
         const int ipx = (int)floorf(px), ipy = (int)floorf(py);
-        if (ipx < -win || ipx >= L.w || ipy < -win || ipy >= L.h) {
+        if (lk_window_outside(ipx, ipy, win, L.w, L.h)) {
             if (level == 0) status = false;
             continue;
         }
@@ -224,7 +218,7 @@ __device__ __forceinline__ PlainLKResult plain_lk_pair(const LevelOf& level_of, 
         float pdx = 0.f, pdy = 0.f;
         for (int j = 0; j < max_iters; j++) {
             const int iqx = (int)floorf(qx), iqy = (int)floorf(qy);
-            if (iqx < -win || iqx >= L.w || iqy < -win || iqy >= L.h) {
+            if (lk_window_outside(iqx, iqy, win, L.w, L.h)) {
                 if (level == 0) status = false;
                 break;
             }
@@ -281,27 +275,14 @@ __device__ __forceinline__ PlainLKResult plain_lk_pair(const LevelOf& level_of, 
                 b1 = group8_exact_sum_i64(sb1) * FLT_SCALE;
                 b2 = group8_exact_sum_i64(sb2) * FLT_SCALE;
             }
-            const float dx = (A12 * b2 - A22 * b1) * D;
-            const float dy = (A12 * b1 - A11 * b2) * D;
-            qx += dx;
-            qy += dy;
-            nx = qx + half_win;
-            ny = qy + half_win;
-            if ((double)dx * (double)dx + (double)dy * (double)dy <= eps_sq) break;
-            if (j > 0 && fabs((double)(dx + pdx)) < 0.01 && fabs((double)(dy + pdy)) < 0.01) {
-                nx -= dx * 0.5f;
-                ny -= dy * 0.5f;
-                break;
-            }
-            pdx = dx;
-            pdy = dy;
+            if (lk_newton_step(A11, A12, A22, D, b1, b2, half_win, j, eps_sq, qx, qy, nx, ny, pdx, pdy)) break;
         }
 
         // ---- L1 patch error at level 0 ----
         if (status && level == 0) {
             const float ex = nx - half_win, ey = ny - half_win;
             const int iex = (int)floorf(ex), iey = (int)floorf(ey);
-            if (iex < -win || iex >= L.w || iey < -win || iey >= L.h) {
+            if (lk_window_outside(iex, iey, win, L.w, L.h)) {
                 status = false;
             } else if constexpr (ERR) {
                 const Weights wE = bilinear_weights(ex - (float)iex, ey - (float)iey);
@@ -329,20 +310,6 @@ __device__ __forceinline__ PlainLKResult plain_lk_pair(const LevelOf& level_of, 
     r.status = status;
     r.err = status ? err : 0.f;
     return r;
-}
-
-// Launch geometry of both kernels: dynamic LDS of 8 groups x win^2 x 8 bytes per wavefront, 1..4 wavefronts per workgroup, as
-// many as fit below 64 KiB (window 16: 3 wavefronts, 49152 bytes, not 4, exactly 64 KiB; window 31: 1).
-struct PlainLKLaunch {
-    int waves;
-    unsigned blocks;
-    size_t lds_bytes;
-};
-inline PlainLKLaunch plain_lk_launch(int n, int win) {
-    static_assert((size_t)kRecStride * PC_MAX_WINDOW * PC_MAX_WINDOW * sizeof(uint2) < 65536, "one wavefront's templates must fit below 64 KiB");
-    const size_t wave_bytes = (size_t)kRecStride * win * win * sizeof(uint2);   // <= 61504
-    const int waves = (int)std::min<size_t>(4, 65535 / wave_bytes);
-    return {waves, (unsigned)((n + waves - 1) / waves), waves * wave_bytes};
 }
 
 }  // namespace pc

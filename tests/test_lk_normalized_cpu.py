@@ -128,3 +128,27 @@ def test_the_normalised_kernels_are_in_the_library_and_use_no_scratch():
         assert len(found) == 1, (name, [n for n in kernels if name in n])
         assert found[0][".private_segment_fixed_size"] == 0, (name, found[0][".private_segment_fixed_size"])
         assert found[0].get(".agpr_count", 0) == 0, name
+
+
+# ---- 5. the kernels built from the shared pair helpers (csrc/hip/lk_pair.hpp, lk_fb.hpp) keep their registers ----
+# (mangled-name fragment, VGPRs of the build before the helpers were shared: profiles/lk_pair_helpers.json)
+PAIR_HELPER_INSTANCES = [
+    ("12lk_fb_kernelILb0E", 56), ("12lk_fb_kernelILb1E", 78),
+    ("18lk_wmask_fb_kernelILb0E", 62), ("18lk_wmask_fb_kernelILb1E", 78),
+    ("15lk_wmask_kernelILb0E", 123), ("15lk_wmask_kernelILb1E", 129),
+    ("15lk_plain_kernelILb0E", 125), ("15lk_plain_kernelILb1E", 156),
+    ("17lk_norm_fb_kernelE", 71), ("19lk_search_fb_kernelE", 61), ("16lk_search_kernelE", 136),
+]
+
+
+@pytest.mark.parametrize("fragment,parent_vgprs", PAIR_HELPER_INSTANCES)
+def test_a_kernel_of_the_pair_family_exists_once_and_keeps_its_registers(fragment, parent_vgprs):
+    path = build.hip_library_path()
+    kernels = {k[".name"]: k for elf in _code_objects(path) for k in _kernel_metadata(elf)}
+    found = [k for n, k in kernels.items() if fragment in n]
+    assert len(found) == 1, (fragment, [n for n in kernels if fragment in n])
+    k = found[0]
+    print("%s: %d VGPRs (before: %d)" % (k[".name"], k[".vgpr_count"], parent_vgprs))
+    assert k.get(".private_segment_fixed_size", 0) == 0, (fragment, k.get(".private_segment_fixed_size"))
+    assert k.get(".agpr_count", 0) == 0, (fragment, k.get(".agpr_count"))
+    assert k[".vgpr_count"] <= parent_vgprs, (fragment, k[".vgpr_count"], parent_vgprs)
