@@ -843,6 +843,9 @@ typedef struct pc_lm_debug_state {
 int pc_debug_lm_decide(pc_context* ctx, int mode, int n_scripts, int n_rounds, int max_rounds,
                        const pc_pnp_solve_options* options /* [n_scripts] */, const pc_pnp_camera* initial /* [n_scripts] */,
                        const float* sums /* [n_scripts][n_rounds][56] */, pc_lm_debug_state* states /* [n_scripts][n_rounds] */);
+/* tests, debugging: device allocations, pinned allocations, streams and events currently owned by objects of this library
+ * in this process (what pc_peer_buffer_alloc / pc_host_buffer_alloc handed out is the caller's and is not counted). */
+int pc_debug_live_resources(int out[4]);
 /* ---- SolveFrame in one call (cpp/tracker.cc:36-131): the correspondences of EVERY source frame + SolvePnPIterative ----
  * Two launches and one wait per frame: one ray-cast launch over the matches of all sources (each under its own
  * camera; world points stay on the GPU, no compaction), then the whole Levenberg-Marquardt loop and the inlier pass as

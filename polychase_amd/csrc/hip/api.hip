@@ -37,8 +37,8 @@ int collect_timing(pc_context* c) {
             c->total_ms[r.cls] += ms;
             if (hipEventElapsedTime(&t0, origin, r.a) == hipSuccess) spans[r.cls].emplace_back(t0, t0 + ms);
         }
-        c->event_pool.push_back(r.a);
-        c->event_pool.push_back(r.b);
+        c->event_pool.push_back(std::move(r.a));
+        c->event_pool.push_back(std::move(r.b));
     }
     c->ranges.clear();
     for (int k = 0; k < PC_K_COUNT; k++) {
@@ -79,11 +79,9 @@ std::vector<int2> suppression_offsets(double min_distance) {
 
 int ensure_kp_capacity(pc_frame* f, int n) {
     if (n <= f->kp_cap) return PC_OK;
-    if (f->d_kps) (void)hipFree(f->d_kps);
-    f->d_kps = nullptr;
     f->kp_cap = 0;
     const int want = n + n / 2 + 1024;
-    PC_HIP(hipMalloc(reinterpret_cast<void**>(&f->d_kps), (size_t)want * sizeof(float2)));
+    PC_HIP(f->d_kps.ensure((size_t)want, /*exact=*/true));
     f->kp_cap = want;
     return PC_OK;
 }
@@ -166,7 +164,7 @@ static bool fused_detection(const pc_gftt_options& opt) {
 }
 
 // the frame's detection mask plane, or null: the unmasked kernels
-static const uint8_t* frame_mask(const pc_frame* f) { return f->mask_on ? f->d_mask : nullptr; }
+static const uint8_t* frame_mask(const pc_frame* f) { return f->mask_on ? f->d_mask.p : nullptr; }
 
 // cornerMinEigenVal / cornerHarris of the frame (gftt.cc:31-36) + per-cell maxima: the fused register kernel for the detector's
 // default, the general pair of kernels otherwise (their covariance scratch is allocated on first use: not the addon's path)
@@ -209,7 +207,7 @@ int detect_reserve(pc_context* ctx, int w, int h, DetectScratch& d, const pc_gft
     PC_HIP(d.bucket_offsets.ensure(pc::kSortBuckets + 1));
     PC_HIP(d.per_block.ensure((size_t)pc::suppress_num_blocks(d.cand_cap) + 1));
     PC_HIP(d.h_counters.ensure(kHostCells));
-    if (!d.ev_b) PC_HIP(hipEventCreateWithFlags(&d.ev_b, hipEventDisableTiming));
+    if (!d.ev_b) PC_HIP(d.ev_b.create(hipEventDisableTiming));
     (void)ctx;
     return PC_OK;
 }
@@ -240,11 +238,9 @@ static int upload_suppression_offsets(pc_context* ctx, const pc_gftt_options& op
 
 static int ensure_perm_capacity(pc_frame* f, int n) {
     if (f->perm_cap >= n) return PC_OK;
-    if (f->d_perm) PC_HIP(hipFree(f->d_perm));
-    f->d_perm = nullptr;
     f->perm_cap = 0;
     const int want = std::max(n + n / 2, 1024);
-    PC_HIP(hipMalloc(&f->d_perm, (size_t)want * 2 * sizeof(uint32_t)));   // order + inverse
+    PC_HIP(f->d_perm.ensure((size_t)want * 2, /*exact=*/true));   // order + inverse
     f->perm_cap = want;
     return PC_OK;
 }
@@ -296,19 +292,19 @@ int detect_enqueue(pc_context* ctx, pc_frame* f, const pc::GfttGrid& grid, const
     if (fused) {
         ScopedTimer t(ctx, PC_K_SUPPRESS);
         pc::launch_suppress_compact(d.keys_sorted.p, n_launch, cnt + kCntCand, w, h, d.eig.p, d.cstate.p, ctx->sup_offsets.p,
-                                    ctx->n_sup_offsets, ctx->sup_rows.p, ctx->sup_R, d.per_block.p, cnt + kCntStuck, limit, f->d_kps,
+                                    ctx->n_sup_offsets, ctx->sup_rows.p, ctx->sup_R, d.per_block.p, cnt + kCntStuck, limit, f->d_kps.p,
                                     cnt + kCntKps, hist.p, cnt + kCntOverflow, tickets + d.ticket_stride, ctx->work);
     } else {
         ScopedTimer t(ctx, PC_K_SUPPRESS);
         pc::launch_suppress_and_compact(d.keys_sorted.p, n_launch, cnt + kCntCand, w, h, d.eig.p, d.cstate.p, ctx->sup_offsets.p,
                                         ctx->n_sup_offsets, ctx->sup_rows.p, ctx->sup_R, opt.min_distance >= 1, d.per_block.p,
-                                        cnt + kCntStuck, limit, f->d_kps,
+                                        cnt + kCntStuck, limit, f->d_kps.p,
                                         cnt + kCntKps, hist.p, cnt + kCntOverflow, tickets + d.ticket_stride, d.ticket_stride,
                                         opt.min_distance, large_radius ? d.sup_grid.p : nullptr, ctx->work);
     }
     // the visiting order; the same launch stores the counters in pinned host memory (no copy command behind it)
-    pc::launch_spatial_bins_counted(f->d_kps, (int)std::min<uint32_t>(limit, n_launch), cnt + kCntKps, w, h, hist.p, f->d_perm,
-                                    f->d_perm + f->perm_cap, cnt, d.h_counters.p, kHostCells, ctx->work);
+    pc::launch_spatial_bins_counted(f->d_kps.p, (int)std::min<uint32_t>(limit, n_launch), cnt + kCntKps, w, h, hist.p, f->d_perm.p,
+                                    f->d_perm.p + f->perm_cap, cnt, d.h_counters.p, kHostCells, ctx->work);
     PC_HIP(hipEventRecord(d.ev_b, ctx->work));
     f->n_kps = -1;
     f->n_cands = -1;
@@ -352,10 +348,10 @@ static int detect_slow_path(pc_context* ctx, pc_frame* f, const pc::GfttGrid& gr
     const bool large_radius = opt.min_distance > pc::kSuppressMaxTableRadius;
     if (large_radius) PC_HIP(d.sup_grid.ensure((size_t)pc::suppress_large_grid_words(w, h, opt.min_distance)));
     pc::launch_suppress_and_compact(d.keys_sorted.p, n_cand, nullptr, w, h, d.eig.p, d.cstate.p, ctx->sup_offsets.p, ctx->n_sup_offsets,
-                                    ctx->sup_rows.p, ctx->sup_R, opt.min_distance >= 1, d.per_block.p, cnt + kCntStuck, (uint32_t)std::max(opt.max_corners, 0), f->d_kps,
+                                    ctx->sup_rows.p, ctx->sup_R, opt.min_distance >= 1, d.per_block.p, cnt + kCntStuck, (uint32_t)std::max(opt.max_corners, 0), f->d_kps.p,
                                     cnt + kCntKps, hist.p, nullptr, tickets + d.ticket_stride, d.ticket_stride, opt.min_distance,
                                     large_radius ? d.sup_grid.p : nullptr, ctx->work);
-    pc::launch_spatial_bins_counted(f->d_kps, cap, cnt + kCntKps, w, h, hist.p, f->d_perm, f->d_perm + f->perm_cap, nullptr, nullptr, 0,
+    pc::launch_spatial_bins_counted(f->d_kps.p, cap, cnt + kCntKps, w, h, hist.p, f->d_perm.p, f->d_perm.p + f->perm_cap, nullptr, nullptr, 0,
                                     ctx->work);
     PC_HIP(hipMemcpyAsync(d.h_counters.p, cnt, kHostCells * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->work));
     PC_HIP(hipStreamSynchronize(ctx->work));
@@ -390,7 +386,7 @@ int detect_finish(pc_context* ctx, pc_frame* f, const pc::GfttGrid& grid, const 
 // order `stream` after it.
 int join_prep(pc_context* ctx) {
     if (!ctx->prep_dirty) return PC_OK;
-    for (hipStream_t s : {ctx->prep_stream, ctx->stream_b}) {
+    for (hipStream_t s : {ctx->prep_stream.s, ctx->stream_b.s}) {
         if (!s) continue;
         PC_HIP(hipEventRecord(ctx->prep_fence, s));
         PC_HIP(hipStreamWaitEvent(ctx->stream, ctx->prep_fence, 0));
@@ -407,7 +403,7 @@ int order_keypoints_spatially(pc_context* ctx, pc_frame* f, DevBuf<uint32_t>& hi
     if (n <= 0) return PC_OK;
     if (int rc = ensure_perm_capacity(f, n)) return rc;
     PC_HIP(hist.ensure((size_t)pc::bin_num_tiles(f->w, f->h) + 1));
-    pc::launch_spatial_bins(f->d_kps, n, nullptr, f->w, f->h, hist.p, f->d_perm, f->d_perm + f->perm_cap, ctx->work);
+    pc::launch_spatial_bins(f->d_kps.p, n, nullptr, f->w, f->h, hist.p, f->d_perm.p, f->d_perm.p + f->perm_cap, ctx->work);
     f->perm_valid = true;
     return PC_OK;
 }
@@ -496,10 +492,11 @@ int pc_context_create(int device_index, pc_context** out) {
         return fail(PC_E_NO_DEVICE, "no HIP device available (this library has no CPU fallback)");
     if (device_index < 0 || device_index >= count) return fail(PC_E_INVALID, "device index %d out of range [0,%d)", device_index, count);
     PC_HIP(hipSetDevice(device_index));
-    pc_context* c = new (std::nothrow) pc_context();
+    // an early return destroys what exists so far (pc_context_destroy)
+    std::unique_ptr<pc_context, void (*)(pc_context*)> c(new (std::nothrow) pc_context(), pc_context_destroy);
     if (!c) return fail(PC_E_INVALID, "out of host memory");
     c->device = device_index;
-    hipError_t e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
+    PC_HIP(c->stream.create(hipStreamNonBlocking));
     {
         const char* g = getenv("POLYCHASE_LK_GATE");
         c->lk_gate_on = !(g && atoi(g) == 0);
@@ -515,13 +512,13 @@ int pc_context_create(int device_index, pc_context** out) {
                 }
         }
     }
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&c->stream_b, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&c->prep_stream, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&c->prep_fence, hipEventDisableTiming);
+    PC_HIP(c->stream_b.create(hipStreamNonBlocking));
+    PC_HIP(c->prep_stream.create(hipStreamNonBlocking));
+    PC_HIP(c->prep_fence.create(hipEventDisableTiming));
     c->work = c->stream;
     {
         const char* v = getenv("POLYCHASE_COPY_STREAM");
-        if (e == hipSuccess && !(v && atoi(v) == 0)) e = hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking);
+        if (!(v && atoi(v) == 0)) PC_HIP(c->copy_stream.create(hipStreamNonBlocking));
     }
     if (const char* m = getenv("POLYCHASE_ARITH")) {
         const std::string mode(m);
@@ -531,16 +528,10 @@ int pc_context_create(int device_index, pc_context** out) {
         else if (mode == "canonical") c->arith = PC_ARITH_CANONICAL;
         else if (mode == "sobel_fma_rows") c->arith = PC_ARITH_SOBEL_FMA | PC_ARITH_SOBEL_ROW_FMA;
         else if (mode == "opencv_x86_rows") c->arith = PC_ARITH_OPENCV_X86 | PC_ARITH_SOBEL_ROW_FMA;
-        else if (!mode.empty()) {
-            delete c;
+        else if (!mode.empty())
             return fail(PC_E_INVALID, "POLYCHASE_ARITH=%s: expected canonical, opencv_x86, lk_x86, sobel_fma, sobel_fma_rows or opencv_x86_rows", m);
-        }
     }
-    if (e != hipSuccess) {
-        delete c;
-        return fail(PC_E_HIP, "hipStreamCreate failed: %s", hipGetErrorString(e));
-    }
-    *out = c;
+    *out = c.release();
     return PC_OK;
 }
 
@@ -556,7 +547,7 @@ int pc_peer_buffer_alloc(int device_index, size_t bytes, void** device_ptr) {
     if (!device_ptr || bytes == 0) return fail(PC_E_INVALID, "bad argument");
     *device_ptr = nullptr;
     PC_HIP(hipSetDevice(device_index));
-    PC_HIP(hipMalloc(device_ptr, bytes));
+    PC_HIP(hipMalloc(device_ptr, bytes));   // not owned here: the caller's, until pc_peer_buffer_free
     return PC_OK;
 }
 int pc_peer_buffer_free(int device_index, void* device_ptr) {
@@ -717,61 +708,8 @@ void pc_context_destroy(pc_context* c) {
     (void)hipSetDevice(c->device);
     if (c->prep_stream) (void)c->sync_side_streams();
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    for (auto& r : c->ranges) {
-        (void)hipEventDestroy(r.a);
-        (void)hipEventDestroy(r.b);
-    }
-    for (auto e : c->event_pool) (void)hipEventDestroy(e);
-    c->staging.release();
-    for (auto& b : c->staging2) b.release();
-    for (auto& pair : c->staging_ev)
-        for (hipEvent_t ev : pair)
-            if (ev) (void)hipEventDestroy(ev);
-    if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
-    c->sup_offsets.release();
-    c->sup_rows.release();
-    if (c->detect) {
-        c->detect->release();
-        delete c->detect;
-        c->detect = nullptr;
-    }
-    c->sort_temp.release();
-    for (auto& b : c->gray_table_buf) b.release();
-    c->poly_host.release();
-    c->poly_dev.release();
-    c->lk_rec[0].release();
-    c->lk_rec[1].release();
-    c->lk_cxy.release();
-    c->lk_ustatus.release();
-    c->lk_cerr.release();
-    c->lk_back_xy.release();
-    c->lk_back_status.release();
-    c->lk_choked.release();
-    c->lk_touched.release();
-    c->lk_corr.release();
-    c->lk_affine_m.release();
-    c->lk_affine_state.release();
-    for (auto& b : c->lk_search_d) b.release();
-    for (auto& b : c->lk_search_state) b.release();
-    c->lk_cidx.release();
-    for (auto& b : c->lk_block_counts) b.release();
-    c->lk_perm.release();
-    c->lk_prof.release();
-    c->lk_x86_stats.release();
-    c->lk_gate.release();
-    c->lk_gate_timed_out.release();
-    c->lk_hist.release();
-    c->lk_row_offset.release();
-    c->h_row_offset.release();
-    for (auto& b : c->lk_pack) b.release();
-    if (c->stream_b) {
-        (void)hipStreamSynchronize(c->stream_b);
-        (void)hipStreamDestroy(c->stream_b);
-    }
-    if (c->prep_stream) (void)hipStreamDestroy(c->prep_stream);
-    if (c->prep_fence) (void)hipEventDestroy(c->prep_fence);
-    if (c->stream) (void)hipStreamDestroy(c->stream);
-    delete c;
+    if (c->stream_b) (void)hipStreamSynchronize(c->stream_b);
+    delete c;   // the members let go of what they hold: buffers first, streams last (internal.hpp)
 }
 
 int pc_context_synchronize(pc_context* c) {
@@ -782,7 +720,7 @@ int pc_context_synchronize(pc_context* c) {
     return PC_OK;
 }
 
-void* pc_context_stream(pc_context* c) { return c ? (void*)c->stream : nullptr; }
+void* pc_context_stream(pc_context* c) { return c ? (void*)c->stream.s : nullptr; }
 
 int pc_context_enable_timing(pc_context* c, int enable) {
     if (!c) return fail(PC_E_INVALID, "null context");
@@ -837,6 +775,12 @@ int pc_debug_lk_x86_stats(pc_context* c, int enable, unsigned long long* out) {
     return PC_OK;
 }
 
+int pc_debug_live_resources(int out[4]) {
+    if (!out) return fail(PC_E_INVALID, "null argument");
+    for (int k = 0; k < 4; k++) out[k] = pc::g_live[k].load(std::memory_order_relaxed);
+    return PC_OK;
+}
+
 int pc_context_pci_bus_id(pc_context* c, char* buf, int len) {
     if (!c || !buf || len < 16) return fail(PC_E_INVALID, "bad argument");
     PC_HIP(hipDeviceGetPCIBusId(buf, len, c->device));
@@ -867,7 +811,7 @@ int pc_frame_create(pc_context* ctx, int width, int height, int window_size, int
     max_level = std::min(max_level, PC_MAX_LEVELS - 1);
     if ((long long)width * height > (1ll << 30)) return fail(PC_E_INVALID, "frame too large");
     PC_HIP(hipSetDevice(ctx->device));
-    pc_frame* f = new (std::nothrow) pc_frame();
+    std::unique_ptr<pc_frame, void (*)(pc_frame*)> f(new (std::nothrow) pc_frame(), pc_frame_destroy);
     if (!f) return fail(PC_E_INVALID, "out of host memory");
     f->ctx = ctx;
     f->w = width;
@@ -897,33 +841,19 @@ int pc_frame_create(pc_context* ctx, int width, int height, int window_size, int
     }
     // tail slack: the LK staging reads 16 uint16 columns per region row, a few past the last row of the last plane
     total += 256;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&f->slab), total);
-    if (e != hipSuccess) {
-        delete f;
-        return fail(PC_E_HIP, "hipMalloc(%zu) failed: %s", total, hipGetErrorString(e));
-    }
+    PC_HIP(f->slab.ensure(total, /*exact=*/true));
     f->slab_bytes = total;
     // zero once: derivative padding must stay zero (derivBorder = BORDER_CONSTANT)
-    e = hipMemsetAsync(f->slab, 0, total, ctx->stream);
-    if (e != hipSuccess) {
-        (void)hipFree(f->slab);
-        delete f;
-        return fail(PC_E_HIP, "hipMemsetAsync failed: %s", hipGetErrorString(e));
-    }
+    PC_HIP(hipMemsetAsync(f->slab.p, 0, total, ctx->stream));
     for (int l = 0; l < f->nlevels; l++) {
         pc::Level& L = f->levels[l];
         const size_t interior = (size_t)window_size * L.pitch + pc::kPadX;
-        L.img = f->slab + img_off[l] + interior;
-        L.der = reinterpret_cast<int32_t*>(f->slab + der_off[l]) + interior;
-        L.img16 = reinterpret_cast<uint16_t*>(f->slab + i16_off[l]) + interior + (size_t)pc::kImg16SlackRows * L.pitch;
+        L.img = f->slab.p + img_off[l] + interior;
+        L.der = reinterpret_cast<int32_t*>(f->slab.p + der_off[l]) + interior;
+        L.img16 = reinterpret_cast<uint16_t*>(f->slab.p + i16_off[l]) + interior + (size_t)pc::kImg16SlackRows * L.pitch;
     }
-    int rc = ensure_kp_capacity(f, std::max(4096, (int)((long long)width * height / 16)));
-    if (rc != PC_OK) {
-        (void)hipFree(f->slab);
-        delete f;
-        return rc;
-    }
-    *out = f;
+    if (int rc = ensure_kp_capacity(f.get(), std::max(4096, (int)((long long)width * height / 16)))) return rc;
+    *out = f.release();
     return PC_OK;
 }
 
@@ -935,34 +865,26 @@ void pc_frame_destroy(pc_frame* f) {
         (void)hipStreamSynchronize(f->ctx->stream);
         if (f->ctx->eig_owner == f) f->ctx->eig_owner = nullptr;
     }
-    if (f->slab) (void)hipFree(f->slab);
-    if (f->d_kps) (void)hipFree(f->d_kps);
-    if (f->d_perm) (void)hipFree(f->d_perm);
-    if (f->d_mask) (void)hipFree(f->d_mask);
-    if (f->d_choked) (void)hipFree(f->d_choked);
-    if (f->d_weights) (void)hipFree(f->d_weights);
     delete f;
 }
 
 }  // extern "C"
 
 int pc_api::ensure_mask_plane(pc_frame* f) {
-    if (f->d_mask) return PC_OK;
     // + 16: the kernels read a quad's bytes as one aligned dword, never past the plane, but a little room costs nothing
-    PC_HIP(hipMalloc(reinterpret_cast<void**>(&f->d_mask), (size_t)f->w * f->h + 16));
+    PC_HIP(f->d_mask.ensure((size_t)f->w * f->h + 16, /*exact=*/true));
     return PC_OK;
 }
 
 int pc_api::ensure_choked_plane(pc_frame* f) {
-    if (f->d_choked) return PC_OK;
-    PC_HIP(hipMalloc(reinterpret_cast<void**>(&f->d_choked), (size_t)f->w * f->h + 16));
+    PC_HIP(f->d_choked.ensure((size_t)f->w * f->h + 16, /*exact=*/true));
     return PC_OK;
 }
 
 int pc_api::upload_mask(pc_frame* f, const uint8_t* mask, size_t row_pitch, int on_device, hipStream_t s) {
     int rc = ensure_mask_plane(f);
     if (rc != PC_OK) return rc;
-    PC_HIP(hipMemcpy2DAsync(f->d_mask, (size_t)f->w, mask, row_pitch, (size_t)f->w, (size_t)f->h,
+    PC_HIP(hipMemcpy2DAsync(f->d_mask.p, (size_t)f->w, mask, row_pitch, (size_t)f->w, (size_t)f->h,
                             on_device == 1 ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
     f->mask_on = true;
     f->weights_valid = false;
@@ -970,7 +892,7 @@ int pc_api::upload_mask(pc_frame* f, const uint8_t* mask, size_t row_pitch, int 
 }
 
 int pc_api::alloc_window_weights(pc_frame* f, hipStream_t s) {
-    if (f->d_weights) return PC_OK;
+    if (f->d_weights.p) return PC_OK;
     size_t total = 0, wt_off[PC_MAX_LEVELS], wm_off[PC_MAX_LEVELS];
     for (int l = 0; l < f->nlevels; l++) {
         const pc::Level& L = f->levels[l];
@@ -981,12 +903,12 @@ int pc_api::alloc_window_weights(pc_frame* f, hipStream_t s) {
         wm_off[l] = total;
         total += align_up((size_t)f->levels[l].w * f->levels[l].h, 256);
     }
-    PC_HIP(hipMalloc(reinterpret_cast<void**>(&f->d_weights), total));
+    PC_HIP(f->d_weights.ensure(total, /*exact=*/true));
     // once: the padding is on, and the launches write the interiors only
-    PC_HIP(hipMemsetAsync(f->d_weights, 255, total, s));
+    PC_HIP(hipMemsetAsync(f->d_weights.p, 255, total, s));
     for (int l = 0; l < f->nlevels; l++) {
-        f->wt[l] = f->d_weights + wt_off[l] + (size_t)f->win * f->levels[l].pitch + pc::kPadX;
-        f->wm[l] = l ? f->d_weights + wm_off[l] : nullptr;
+        f->wt[l] = f->d_weights.p + wt_off[l] + (size_t)f->win * f->levels[l].pitch + pc::kPadX;
+        f->wm[l] = l ? f->d_weights.p + wm_off[l] : nullptr;
     }
     f->weights_valid = false;
     return PC_OK;
@@ -1002,7 +924,7 @@ int pc_api::make_window_weights(pc_frame* f, hipStream_t s) {
     if (f->weights_valid) return PC_OK;
     pc::WindowWeightParams p;
     std::memset(&p, 0, sizeof(p));
-    p.mask = f->d_mask;
+    p.mask = f->d_mask.p;
     p.nlevels = f->nlevels;
     for (int l = 0; l < f->nlevels; l++) {
         p.m[l] = f->wm[l];
@@ -1050,7 +972,7 @@ size_t pc_api::snap_polygons(const float* xy, const int32_t* counts, int n_polyg
 int pc_api::fill_mask_polygons(pc_frame* f, const int32_t* d_poly, int n_vertices, int n_polygons, int invert, hipStream_t s) {
     int rc = ensure_mask_plane(f);
     if (rc != PC_OK) return rc;
-    pc::launch_polygon_mask(d_poly, n_vertices, n_polygons, invert ? 1 : 0, f->d_mask, f->w, f->h, s);
+    pc::launch_polygon_mask(d_poly, n_vertices, n_polygons, invert ? 1 : 0, f->d_mask.p, f->w, f->h, s);
     PC_HIP(hipGetLastError());
     f->mask_on = true;
     f->weights_valid = false;
@@ -1092,8 +1014,8 @@ int pc_api::set_image(pc_context* ctx, pc_frame* f, const uint8_t* src, size_t r
             staged = b;
             PC_HIP(ctx->staging2[b].ensure(row_pitch * (size_t)f->h));
             if (!ctx->staging_ev[b][0]) {
-                PC_HIP(hipEventCreateWithFlags(&ctx->staging_ev[b][0], hipEventDisableTiming));
-                PC_HIP(hipEventCreateWithFlags(&ctx->staging_ev[b][1], hipEventDisableTiming));
+                PC_HIP(ctx->staging_ev[b][0].create(hipEventDisableTiming));
+                PC_HIP(ctx->staging_ev[b][1].create(hipEventDisableTiming));
             } else {
                 PC_HIP(hipStreamWaitEvent(ctx->copy_stream, ctx->staging_ev[b][1], 0));   // the kernels that read this buffer two frames ago
             }
@@ -1165,7 +1087,7 @@ extern "C" {
 int pc_host_buffer_alloc(size_t bytes, void** out) {
     if (!out) return fail(PC_E_INVALID, "null out");
     *out = nullptr;
-    PC_HIP(hipHostMalloc(out, bytes ? bytes : 1, hipHostMallocDefault));
+    PC_HIP(hipHostMalloc(out, bytes ? bytes : 1, hipHostMallocDefault));   // not owned here: the caller's, until pc_host_buffer_free
     return PC_OK;
 }
 void pc_host_buffer_free(void* buffer) {
@@ -1219,7 +1141,7 @@ int pc_frame_download_mask(pc_context* ctx, const pc_frame* f, uint8_t* out) {
     if (!ctx || !f || !out) return fail(PC_E_INVALID, "null argument");
     if (!f->mask_on) return fail(PC_E_STATE, "the frame has no mask on");
     if (int jrc = join_prep(ctx)) return jrc;
-    PC_HIP(hipMemcpyAsync(out, f->d_mask, (size_t)f->w * f->h, hipMemcpyDeviceToHost, ctx->stream));
+    PC_HIP(hipMemcpyAsync(out, f->d_mask.p, (size_t)f->w * f->h, hipMemcpyDeviceToHost, ctx->stream));
     PC_HIP(hipStreamSynchronize(ctx->stream));
     return PC_OK;
 }
@@ -1232,7 +1154,7 @@ int pc_frame_download_choked_mask(pc_context* ctx, const pc_frame* f, int margin
     if (int jrc = join_prep(ctx)) return jrc;
     const size_t bytes = (size_t)f->w * f->h;
     PC_HIP(ctx->lk_choked.ensure(bytes + 16));
-    pc::launch_mask_choke(f->d_mask, ctx->lk_choked.p, f->w, f->h, margin, ctx->stream);
+    pc::launch_mask_choke(f->d_mask.p, ctx->lk_choked.p, f->w, f->h, margin, ctx->stream);
     PC_HIP(hipGetLastError());
     PC_HIP(hipMemcpyAsync(out, ctx->lk_choked.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
     PC_HIP(hipStreamSynchronize(ctx->stream));
@@ -1317,7 +1239,7 @@ int pc_frame_detect(pc_context* ctx, pc_frame* f, const pc_gftt_options* opt) {
     if (rc != PC_OK) return rc;
     PC_HIP(hipSetDevice(ctx->device));
     if (int jrc = join_prep(ctx)) return jrc;
-    if (!ctx->detect) ctx->detect = new DetectScratch();
+    if (!ctx->detect) ctx->detect = std::make_unique<DetectScratch>();
     if ((rc = detect_enqueue(ctx, f, g, *opt, *ctx->detect, ctx->lk_hist, /*full_launch=*/true)) != PC_OK) return rc;
     ctx->eig_owner = f;
     if ((rc = detect_finish(ctx, f, g, *opt, *ctx->detect, ctx->lk_hist)) != PC_OK) return rc;
@@ -1354,7 +1276,7 @@ int pc_frame_download_keypoints(pc_context* ctx, const pc_frame* f, float* out_x
     if (f->n_kps < 0) return fail(PC_E_STATE, "frame has no keypoints");
     if (capacity < f->n_kps) return fail(PC_E_CAPACITY, "capacity %d < %d keypoints", capacity, f->n_kps);
     if (f->n_kps == 0) return PC_OK;
-    PC_HIP(hipMemcpyAsync(out_xy, f->d_kps, (size_t)f->n_kps * sizeof(float2), hipMemcpyDeviceToHost, ctx->stream));
+    PC_HIP(hipMemcpyAsync(out_xy, f->d_kps.p, (size_t)f->n_kps * sizeof(float2), hipMemcpyDeviceToHost, ctx->stream));
     PC_HIP(hipStreamSynchronize(ctx->stream));
     return PC_OK;
 }
@@ -1365,7 +1287,7 @@ int pc_frame_set_keypoints(pc_context* ctx, pc_frame* f, const float* xy, int n)
     int rc = ensure_kp_capacity(f, n);
     if (rc != PC_OK) return rc;
     if (n > 0) {
-        PC_HIP(hipMemcpyAsync(f->d_kps, xy, (size_t)n * sizeof(float2), hipMemcpyHostToDevice, ctx->stream));
+        PC_HIP(hipMemcpyAsync(f->d_kps.p, xy, (size_t)n * sizeof(float2), hipMemcpyHostToDevice, ctx->stream));
         PC_HIP(hipStreamSynchronize(ctx->stream));
     }
     f->n_kps = n;

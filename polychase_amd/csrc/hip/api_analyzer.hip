@@ -21,10 +21,11 @@ struct Slot {
     bool valid = false;
     DetState det = DET_NONE;
     bool supplied = false;  // keypoints came from the caller (database), not from detection
+    // not owned (pc_analyzer::lk_done), per job lane: `lk_done` of the latest job whose LK reads this slot
+    hipEvent_t last_read[2] = {nullptr, nullptr};
+    Event img_ready;   // gray + pyramid of the resident frame are complete (prep stream)
+    Event kps_ready;   // keypoints + visiting order are complete (prep stream)
     DetectScratch scratch;
-    hipEvent_t last_read[2] = {nullptr, nullptr};  // per job lane: `lk_done` of the latest job whose LK reads this slot
-    hipEvent_t img_ready = nullptr;  // gray + pyramid of the resident frame are complete (prep stream)
-    hipEvent_t kps_ready = nullptr;  // keypoints + visiting order are complete (prep stream)
 };
 
 struct Job {
@@ -33,10 +34,10 @@ struct Job {
     bool detected = false;
     int n_targets = 0;
     int32_t targets[PC_MAX_TARGETS];
+    Event done;               // records of this job are in pinned memory (the job's lane)
     PinBuf<uint8_t> h_pack;   // the job's records, same layout as pc_context::lk_pack
     size_t o_kps = 0, o_idx = 0, o_xy = 0, o_err = 0, pack_bytes = 0;
     bool host_records = true;       // the whole pack was downloaded (else its 128-byte header only)
-    hipEvent_t done = nullptr;      // records of this job are in pinned memory (the job's lane)
 };
 
 // Issue priority of the helper kernels this analyzer enqueues (common.hpp: helper_priority), from what it observes.
@@ -97,7 +98,7 @@ struct pc_analyzer {
     // that read them; an event that has been re-recorded since marks a LATER launch of the same lane, which the
     // lane's stream order puts behind the remembered one -- waiting for it is still correct.
     static constexpr int kLaneEvents = 16;
-    hipEvent_t lk_done[2][kLaneEvents] = {};
+    Event lk_done[2][kLaneEvents];
     bool gate_armed = false;             // a gated launch is ahead: the next one waits for its "all dispatched" signal
     HelperPriorityControl prio;
     int32_t put_newest = 0, put_previous = 0;   // frame ids of the two most recent put_frame calls
@@ -122,19 +123,19 @@ struct pc_analyzer {
     static constexpr int kMaskGens = 4;
     int mask_kind = 0;                   // 0 none, 1 host (mask_host[mask_gen]), 2 device (mask_dev, mask_dev_pitch), 3 polygons (poly_dev[poly_gen])
     int mask_gen = 0;
+    Event mask_copied[kMaskGens];
     PinBuf<uint8_t> mask_host[kMaskGens];
-    hipEvent_t mask_copied[kMaskGens] = {};
-    const uint8_t* mask_dev = nullptr;
+    const uint8_t* mask_dev = nullptr;   // not owned: the caller's memory
     size_t mask_dev_pitch = 0;
     // Polygon masks (pc_analyzer_set_mask_polygons): the snapped vertices are written into one of kMaskGens pinned buffers, used
     // in turn, and copied on the preparation stream into that buffer's device twin, which the frames' rasteriser launches read
     // on the same stream.  poly_read[g]: the latest copy out of poly_host[g] and the latest launch that read poly_dev[g] are
     // complete -- the host waits for it before it writes poly_host[g] again, kMaskGens masks later.
     int poly_gen = 0, poly_vertices = 0, poly_polygons = 0, poly_invert = 0;
+    Event poly_read[kMaskGens];
     PinBuf<int32_t> poly_host[kMaskGens];
     DevBuf<int32_t> poly_dev[kMaskGens];
-    hipEvent_t poly_read[kMaskGens] = {};
-    uint8_t* d_log = nullptr;            // optional device-resident record log
+    uint8_t* d_log = nullptr;            // not owned (the caller's memory): optional device-resident record log
     size_t log_cap = 0, log_used = 0;
     std::vector<PinBuf<long long>> log_hdr;  // one pinned header per job slot
 };
@@ -192,7 +193,8 @@ int pc_analyzer_create(pc_context* ctx, int width, int height, const pc_gftt_opt
         if (vrc != PC_OK) return vrc;
     }
     PC_HIP(hipSetDevice(ctx->device));
-    pc_analyzer* a = new (std::nothrow) pc_analyzer();
+    // an early return destroys what exists so far (pc_analyzer_destroy)
+    std::unique_ptr<pc_analyzer, void (*)(pc_analyzer*)> a(new (std::nothrow) pc_analyzer(), pc_analyzer_destroy);
     if (!a) return fail(PC_E_INVALID, "out of host memory");
     a->ctx = ctx;
     // POLYCHASE_LK_LANES=1 (read per analyzer): every job on lane 0, i.e. no two LK launches in flight -- a launch's
@@ -211,66 +213,42 @@ int pc_analyzer_create(pc_context* ctx, int width, int height, const pc_gftt_opt
     // the critical path of that launch
     a->slots.resize((size_t)ring_frames + kSpareSlots);
     a->jobs.resize((size_t)max_jobs);
-    int rc = PC_OK;
     for (auto& s : a->slots) {
-        rc = pc_frame_create(ctx, width, height, flow->window_size, flow->max_level, &s.frame);
-        if (rc != PC_OK) break;
+        if (int rc = pc_frame_create(ctx, width, height, flow->window_size, flow->max_level, &s.frame)) return rc;
         // room for a typical frame's keypoints up front: growing later frees device memory, which synchronises
         const int kp0 = std::max(16384, (width * height) / 16);   // candidates of a textured frame: ~1 per 23 px
-        if ((rc = ensure_kp_capacity(s.frame, kp0)) != PC_OK) break;
-        if (hipMalloc(reinterpret_cast<void**>(&s.frame->d_perm), (size_t)kp0 * 2 * sizeof(uint32_t)) != hipSuccess) {
-            rc = fail(PC_E_HIP, "hipMalloc failed");
-            break;
-        }
+        if (int rc = ensure_kp_capacity(s.frame, kp0)) return rc;
+        PC_HIP(s.frame->d_perm.ensure((size_t)kp0 * 2, /*exact=*/true));
         s.frame->perm_cap = kp0;
-        if ((rc = detect_reserve(ctx, width, height, s.scratch, &a->gopt)) != PC_OK) break;
-        if (s.scratch.bin_hist.ensure((size_t)pc::bin_num_tiles(width, height) + 1) != hipSuccess) {
-            rc = fail(PC_E_HIP, "allocation failed");
-            break;
-        }
-        if (hipEventCreateWithFlags(&s.img_ready, hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&s.kps_ready, hipEventDisableTiming) != hipSuccess) {
-            rc = fail(PC_E_HIP, "hipEventCreate failed");
-            break;
-        }
+        if (int rc = detect_reserve(ctx, width, height, s.scratch, &a->gopt)) return rc;
+        PC_HIP(s.scratch.bin_hist.ensure((size_t)pc::bin_num_tiles(width, height) + 1));
+        PC_HIP(s.img_ready.create(hipEventDisableTiming));
+        PC_HIP(s.kps_ready.create(hipEventDisableTiming));
     }
-    if (rc == PC_OK)
-        for (auto& j : a->jobs)
-            if (hipEventCreateWithFlags(&j.done, hipEventDisableTiming) != hipSuccess) {
-                rc = fail(PC_E_HIP, "hipEventCreate failed");
-                break;
-            }
-    if (rc == PC_OK)
-        for (auto& lane : a->lk_done)
-            for (hipEvent_t& e : lane)
-                if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) rc = fail(PC_E_HIP, "hipEventCreate failed");
-    if (rc == PC_OK) {
+    for (auto& j : a->jobs) PC_HIP(j.done.create(hipEventDisableTiming));
+    for (auto& lane : a->lk_done)
+        for (Event& e : lane) PC_HIP(e.create(hipEventDisableTiming));
+    {
         // Warm the runtime's copy engines: it picks a free SDMA engine per copy and creates an engine's queue the first
         // time it is used (5-8 ms inside some hipMemcpyAsync, observed twice or three times in the first few dozen
         // frames).  A burst of overlapping downloads makes it create them now.
         const size_t chunk = (size_t)4 << 20, burst = 12;
         Job& j0 = a->jobs[0];
-        if (ctx->lk_pack[0].ensure(chunk) != hipSuccess || ctx->lk_pack[1].ensure(chunk) != hipSuccess ||
-            j0.h_pack.ensure(chunk * burst) != hipSuccess) {
-            rc = fail(PC_E_HIP, "allocation failed");
-        } else {
-            hipStream_t streams[3] = {ctx->stream_b, ctx->prep_stream, ctx->stream};
-            for (int round = 0; round < 3 && rc == PC_OK; round++) {
-                for (size_t k = 0; k < burst; k++)
-                    if (hipMemcpyAsync(j0.h_pack.p + k * chunk, ctx->lk_pack[k & 1].p, chunk, hipMemcpyDeviceToHost, streams[k % 3]) !=
-                        hipSuccess)
-                        rc = fail(PC_E_HIP, "copy engine warm-up failed");
-                for (hipStream_t st : streams) (void)hipStreamSynchronize(st);
+        PC_HIP(ctx->lk_pack[0].ensure(chunk));
+        PC_HIP(ctx->lk_pack[1].ensure(chunk));
+        PC_HIP(j0.h_pack.ensure(chunk * burst));
+        hipStream_t streams[3] = {ctx->stream_b, ctx->prep_stream, ctx->stream};
+        for (int round = 0; round < 3; round++) {
+            hipError_t e = hipSuccess;
+            for (size_t k = 0; k < burst; k++) {
+                const hipError_t ek = hipMemcpyAsync(j0.h_pack.p + k * chunk, ctx->lk_pack[k & 1].p, chunk, hipMemcpyDeviceToHost, streams[k % 3]);
+                if (e == hipSuccess) e = ek;
             }
+            for (hipStream_t st : streams) (void)hipStreamSynchronize(st);
+            if (e != hipSuccess) return fail(PC_E_HIP, "copy engine warm-up failed");
         }
     }
-    if (rc != PC_OK) {
-        std::string keep = pc::last_error();
-        pc_analyzer_destroy(a);
-        pc::last_error() = keep;
-        return rc;
-    }
-    *out = a;
+    *out = a.release();
     return PC_OK;
 }
 
@@ -279,27 +257,8 @@ void pc_analyzer_destroy(pc_analyzer* a) {
     (void)hipSetDevice(a->ctx->device);
     (void)a->ctx->sync_side_streams();
     (void)hipStreamSynchronize(a->ctx->stream);
-    for (auto& s : a->slots) {
+    for (auto& s : a->slots)
         if (s.frame) pc_frame_destroy(s.frame);
-        if (s.img_ready) (void)hipEventDestroy(s.img_ready);
-        if (s.kps_ready) (void)hipEventDestroy(s.kps_ready);
-        s.scratch.release();
-    }
-    for (auto& hdr : a->log_hdr) hdr.release();
-    for (auto& m : a->mask_host) m.release();
-    for (hipEvent_t e : a->mask_copied)
-        if (e) (void)hipEventDestroy(e);
-    for (auto& m : a->poly_host) m.release();
-    for (auto& m : a->poly_dev) m.release();
-    for (hipEvent_t e : a->poly_read)
-        if (e) (void)hipEventDestroy(e);
-    for (auto& j : a->jobs) {
-        j.h_pack.release();
-        if (j.done) (void)hipEventDestroy(j.done);
-    }
-    for (auto& lane : a->lk_done)
-        for (hipEvent_t e : lane)
-            if (e) (void)hipEventDestroy(e);
     delete a;
 }
 
@@ -387,7 +346,7 @@ static int analyzer_put(pc_analyzer* a, int32_t frame_id, const uint8_t* rgb, si
     if (as_target) {
         s.frame->mask_on = will_detect != 0;
         if (a->target_margin > 0) {   // (the slot's choked plane exists: ensure_target_planes ran when margin and mask met)
-            pc::launch_mask_choke(s.frame->d_mask, s.frame->d_choked, a->w, a->h, a->target_margin, a->ctx->prep_stream);
+            pc::launch_mask_choke(s.frame->d_mask.p, s.frame->d_choked.p, a->w, a->h, a->target_margin, a->ctx->prep_stream);
             PC_HIP(hipGetLastError());
         }
         s.frame->target_margin = a->target_margin;
@@ -439,7 +398,7 @@ int pc_analyzer_set_keypoints(pc_analyzer* a, int32_t frame_id, const float* xy,
         // resume path (keypoints from the database): pageable source, so the copy is synchronous
         hipStream_t const ds = a->ctx->prep_stream;
         PC_HIP(hipStreamSynchronize(ds));   // a detection of this frame in flight would write the same buffer
-        PC_HIP(hipMemcpyAsync(s->frame->d_kps, xy, (size_t)n * sizeof(float2), hipMemcpyHostToDevice, ds));
+        PC_HIP(hipMemcpyAsync(s->frame->d_kps.p, xy, (size_t)n * sizeof(float2), hipMemcpyHostToDevice, ds));
         PC_HIP(hipStreamSynchronize(ds));
     }
     s->frame->n_kps = n;
@@ -552,7 +511,7 @@ int pc_analyzer_submit(pc_analyzer* a, int32_t frame1, const int32_t* targets, i
         LkPasses passes{.search_radius = a->search_radius, .affine = a->affine, .normalize = a->normalize,
                         .min_correlation = a->min_correlation, .fb_threshold = a->fb_threshold, .mask_windows = a->mask_windows};
         for (int t = 0; t < n_targets; t++)
-            if (tg[t]->target_margin >= 0) passes.plane[t] = tg[t]->target_margin > 0 ? tg[t]->d_choked : tg[t]->d_mask;
+            if (tg[t]->target_margin >= 0) passes.plane[t] = tg[t]->target_margin > 0 ? tg[t]->d_choked.p : tg[t]->d_mask.p;
         if (a->mask_windows) {
             passes.weights_f1 = s1->frame->window_weights;
             for (int t = 0; t < n_targets; t++) passes.weights_tgt[t] = tg[t]->window_weights;
@@ -571,7 +530,7 @@ int pc_analyzer_submit(pc_analyzer* a, int32_t frame1, const int32_t* targets, i
                            ctx->lk_block_counts[lane].cap != scratch_cap_before, p_ro, reinterpret_cast<uint32_t*>(pack + j.o_idx),
                            reinterpret_cast<float2*>(pack + j.o_xy), reinterpret_cast<float*>(pack + j.o_err), ls);
     }
-    pc::launch_copy_keypoints(s1->frame->d_kps, reinterpret_cast<float2*>(pack + j.o_kps), n, ls);
+    pc::launch_copy_keypoints(s1->frame->d_kps.p, reinterpret_cast<float2*>(pack + j.o_kps), n, ls);
     // Everything that reads the resident frames is enqueued: the pyramids (LK), frame1's keypoints (LK, the copy
     // above) and its inverse visiting order (compaction).  A slot may be overwritten once this event has fired.
     hipEvent_t const lk_done = a->lk_done[lane][(a->one_lane ? a->submitted : (a->submitted >> 1)) % pc_analyzer::kLaneEvents];
@@ -725,7 +684,7 @@ int pc_analyzer_set_mask(pc_analyzer* a, const uint8_t* mask, size_t row_pitch, 
         return ensure_target_planes(a);
     }
     const int g = (a->mask_gen + 1) % pc_analyzer::kMaskGens;
-    if (!a->mask_copied[g]) PC_HIP(hipEventCreateWithFlags(&a->mask_copied[g], hipEventDisableTiming));
+    if (!a->mask_copied[g]) PC_HIP(a->mask_copied[g].create(hipEventDisableTiming));
     else PC_HIP(hipEventSynchronize(a->mask_copied[g]));   // copies out of this buffer, kMaskGens masks ago
     PC_HIP(a->mask_host[g].ensure((size_t)a->w * a->h));
     for (int y = 0; y < a->h; y++) std::memcpy(a->mask_host[g].p + (size_t)y * a->w, mask + (size_t)y * row_pitch, (size_t)a->w);
@@ -746,7 +705,7 @@ int pc_analyzer_set_mask_polygons(pc_analyzer* a, const float* xy, const int32_t
     for (int k = 0; k < pc_analyzer::kMaskGens; k++) {
         PC_HIP(a->poly_host[k].ensure((size_t)pc::kPolyWords));
         PC_HIP(a->poly_dev[k].ensure((size_t)pc::kPolyWords, true));
-        if (!a->poly_read[k]) PC_HIP(hipEventCreateWithFlags(&a->poly_read[k], hipEventDisableTiming));
+        if (!a->poly_read[k]) PC_HIP(a->poly_read[k].create(hipEventDisableTiming));
     }
     const int g = (a->poly_gen + 1) % pc_analyzer::kMaskGens;
     PC_HIP(hipEventSynchronize(a->poly_read[g]));   // what read this buffer, kMaskGens masks ago (a fresh event is complete)

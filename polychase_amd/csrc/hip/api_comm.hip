@@ -64,7 +64,7 @@ Rccl& rccl() {
 struct pc_comm {
     int device = 0, world = 1, rank = 0;
     ncclComm_t comm = nullptr;
-    hipStream_t stream = nullptr;            // the collectives' own stream: never behind the analysis
+    pc::Stream stream;                       // the collectives' own stream: never behind the analysis
     pc::DevBuf<unsigned long long> sizes;    // [world + 1]: this rank's size, then everybody's
     pc::DevBuf<uint8_t> staging;             // the padded copy of a piece (an all-gather wants equal counts)
 };
@@ -95,7 +95,7 @@ int pc_comm_create(pc_context* ctx, const void* id, int world_size, int rank, pc
     Rccl& r = rccl();
     if (!r.error.empty()) return fail(PC_E_NO_DEVICE, "%s", r.error.c_str());
     PC_HIP(hipSetDevice(ctx->device));
-    pc_comm* c = new (std::nothrow) pc_comm();
+    std::unique_ptr<pc_comm, void (*)(pc_comm*)> c(new (std::nothrow) pc_comm(), pc_comm_destroy);
     if (!c) return fail(PC_E_INVALID, "out of host memory");
     c->device = ctx->device;
     c->world = world_size;
@@ -103,18 +103,10 @@ int pc_comm_create(pc_context* ctx, const void* id, int world_size, int rank, pc
     ncclUniqueId u;
     std::memcpy(&u, id, sizeof(u));
     ncclResult_t nr = r.CommInitRank(&c->comm, world_size, u, rank);
-    if (nr != ncclSuccess) {
-        delete c;
-        return fail(PC_E_HIP, "ncclCommInitRank(rank %d of %d) failed: %s", rank, world_size, r.GetErrorString(nr));
-    }
-    hipError_t e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
-    if (e == hipSuccess) e = c->sizes.ensure((size_t)world_size + 1);
-    if (e != hipSuccess) {
-        r.CommDestroy(c->comm);
-        delete c;
-        return fail(PC_E_HIP, "pc_comm_create: %s", hipGetErrorString(e));
-    }
-    *out = c;
+    if (nr != ncclSuccess) return fail(PC_E_HIP, "ncclCommInitRank(rank %d of %d) failed: %s", rank, world_size, r.GetErrorString(nr));
+    PC_HIP(c->stream.create(hipStreamNonBlocking));
+    PC_HIP(c->sizes.ensure((size_t)world_size + 1));
+    *out = c.release();
     return PC_OK;
 }
 
@@ -123,9 +115,6 @@ void pc_comm_destroy(pc_comm* c) {
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     if (c->comm) rccl().CommDestroy(c->comm);
-    if (c->stream) (void)hipStreamDestroy(c->stream);
-    c->sizes.release();
-    c->staging.release();
     delete c;
 }
 

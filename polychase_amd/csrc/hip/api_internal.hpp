@@ -12,17 +12,17 @@ namespace pc_api {
 struct ScopedTimer {
     pc_context* c;
     int cls;
-    hipEvent_t a = nullptr, b = nullptr;
+    Event a, b;
     hipStream_t s = nullptr;
     ScopedTimer(pc_context* ctx, int k, hipStream_t on = nullptr) : c(ctx), cls(k), s(on ? on : ctx->work) {
         if (!(c->timing_mask & (1u << k))) return;
         auto get = [&]() {
-            hipEvent_t e = nullptr;
+            Event e;
             if (!c->event_pool.empty()) {
-                e = c->event_pool.back();
+                e = std::move(c->event_pool.back());
                 c->event_pool.pop_back();
             } else {
-                (void)hipEventCreate(&e);
+                (void)e.create();
             }
             return e;
         };
@@ -33,7 +33,7 @@ struct ScopedTimer {
     ~ScopedTimer() {
         if (!a) return;
         (void)hipEventRecord(b, s);
-        c->ranges.push_back({cls, a, b});
+        c->ranges.push_back({cls, std::move(a), std::move(b)});
     }
 };
 

@@ -110,9 +110,9 @@ int lk_job_begin(pc_context* ctx, const pc_frame* frame1, const pc_frame* const*
         cap = (size_t)j->n;
         PC_HIP(ctx->lk_perm.ensure((size_t)j->n * 2));
         PC_HIP(ctx->lk_hist.ensure((size_t)pc::bin_num_tiles(frame1->w, frame1->h) + 1));
-        pc::launch_spatial_bins(frame1->d_kps, j->n, nullptr, frame1->w, frame1->h, ctx->lk_hist.p, ctx->lk_perm.p, ctx->lk_perm.p + j->n, j->stream);
+        pc::launch_spatial_bins(frame1->d_kps.p, j->n, nullptr, frame1->w, frame1->h, ctx->lk_hist.p, ctx->lk_perm.p, ctx->lk_perm.p + j->n, j->stream);
     }
-    j->perm = frame1->perm_valid ? frame1->d_perm : ctx->lk_perm.p;
+    j->perm = frame1->perm_valid ? frame1->d_perm.p : ctx->lk_perm.p;
     ctx->lk_slot_of[set] = j->slot_of = j->perm + cap;
     return PC_OK;
 }
@@ -133,7 +133,7 @@ int lk_forward(pc_context* ctx, const LkJob& j, int normalize) {
     p.n_targets = j.n_targets;
     p.max_level = j.max_level;
     p.n = j.n;
-    p.pts = j.frame1->d_kps;
+    p.pts = j.frame1->d_kps.p;
     p.perm = j.perm;
     p.max_iters = j.max_iters;
     p.eps_sq = j.eps_sq;
@@ -173,7 +173,7 @@ int lk_search(pc_context* ctx, const LkJob& j, int search_radius, short2* search
     p.max_iters = j.max_iters;
     p.eps_sq = j.eps_sq;
     p.min_eig_thr = j.min_eig_thr;
-    p.pts = j.frame1->d_kps;
+    p.pts = j.frame1->d_kps.p;
     p.perm = j.perm;
     p.rec = j.rec;
     p.search_d = search_d;
@@ -194,7 +194,7 @@ int lk_affine(pc_context* ctx, const LkJob& j, float4* affine_m, uint8_t* affine
     p.win = j.win;
     p.max_iters = j.max_iters;
     p.eps_sq = j.eps_sq;
-    p.pts = j.frame1->d_kps;
+    p.pts = j.frame1->d_kps.p;
     p.perm = j.perm;
     p.rec = j.rec;
     p.affine_m = affine_m;
@@ -218,7 +218,7 @@ int lk_window_mask(pc_context* ctx, const LkJob& j, uint8_t* touched) {
     p.max_level = j.max_level;
     p.n = j.n;
     p.win = j.win;
-    p.pts = j.frame1->d_kps;
+    p.pts = j.frame1->d_kps.p;
     p.perm = j.perm;
     p.max_iters = j.max_iters;
     p.eps_sq = j.eps_sq;
@@ -263,7 +263,7 @@ int lk_correlation(pc_context* ctx, const LkJob& j, double min_correlation, floa
     p.n = j.n;
     p.win = j.win;
     p.drop = min_correlation > 0.0 ? 1 : 0;
-    p.pts = j.frame1->d_kps;
+    p.pts = j.frame1->d_kps.p;
     p.perm = j.perm;
     p.t2 = min_correlation * min_correlation;
     p.rec = j.rec;
@@ -289,7 +289,7 @@ int lk_backward(pc_context* ctx, const LkJob& j, const LkPasses& passes, const s
     p.max_level = j.max_level;
     p.n = j.n;
     p.win = j.win;
-    p.pts = j.frame1->d_kps;
+    p.pts = j.frame1->d_kps.p;
     p.perm = j.perm;
     p.max_iters = j.max_iters;
     p.eps_sq = j.eps_sq;
@@ -459,10 +459,10 @@ int lk_track_impl(pc_context* ctx, const pc_frame* frame1, const pc_frame* const
         if (margin > 0 && masked > 0) PC_HIP(ctx->lk_choked.ensure((size_t)masked * plane_bytes + 16));
         for (int t = 0, k = 0; t < n_targets; t++) {
             if (!targets[t]->mask_on) continue;
-            passes.plane[t] = targets[t]->d_mask;
+            passes.plane[t] = targets[t]->d_mask.p;
             if (margin > 0) {
                 uint8_t* const choked = ctx->lk_choked.p + (size_t)(k++) * plane_bytes;
-                pc::launch_mask_choke(targets[t]->d_mask, choked, frame1->w, frame1->h, margin, ctx->stream);
+                pc::launch_mask_choke(targets[t]->d_mask.p, choked, frame1->w, frame1->h, margin, ctx->stream);
                 passes.plane[t] = choked;
             }
         }

@@ -42,7 +42,7 @@ struct pc_pnp_problem {
     pc_context* ctx = nullptr;
     int n = 0;
     bool has_weights = false;
-    // what the sweeps read and write: the problem's own buffers, or those of the pc_corr_set it was made from
+    // what the sweeps read and write: the problem's own buffers, or those of the pc_corr_set it was made from (not owned then)
     const float *X = nullptr, *x = nullptr, *w = nullptr;
     float *partials = nullptr, *out = nullptr, *h_out = nullptr;
     DevBuf<float> own_X, own_x, own_w, own_partials, own_out;
@@ -58,6 +58,9 @@ struct pc_pnp_problem {
 // 3D-2D correspondences of the frame being solved (include/polychase_hip.h)
 struct pc_corr_set {
     pc_context* ctx = nullptr;
+    // pc_track_frame_upload: the matches travel on a stream of the set's own (made the first time a frame is uploaded)
+    Stream copy_stream;
+    Event upload_done;
     DevBuf<float> X;             // world points, capacity x 3
     DevBuf<float2> x;            // image points
     size_t capacity = 0;
@@ -89,8 +92,6 @@ struct pc_corr_set {
     DevBuf<uint8_t> t_block[3];   // the matches of the (up to two) frames in flight and of the one uploaded behind them
     int t_cur = 0;                // the block of the last pc_track_frame_upload
     size_t t_block_bytes = 0;
-    hipStream_t copy_stream = nullptr;
-    hipEvent_t upload_done = nullptr;
     // Up to TWO frames in flight, finished in launch order: the second one's launches sit behind the first one's on the stream and
     // may take the first one's camera from the device (pc_track_frame_launch_chained), so the GPU goes from one frame to the next
     // without waiting for the host to see a pose.
@@ -122,21 +123,21 @@ int pc_mesh_create(pc_context* ctx, const float* vertices, int n_vertices, const
     for (int i = 0; i < 3 * n_triangles; i++)
         if (triangles[i] >= (uint32_t)n_vertices) return fail(PC_E_INVALID, "triangle index %u out of range", triangles[i]);
     PC_HIP(hipSetDevice(ctx->device));
-    pc_mesh* m = new (std::nothrow) pc_mesh();
+    std::unique_ptr<pc_mesh, void (*)(pc_mesh*)> m(new (std::nothrow) pc_mesh(), pc_mesh_destroy);
     if (!m) return fail(PC_E_INVALID, "out of host memory");
     m->ctx = ctx;
     m->n_vertices = n_vertices;
     m->n_triangles = n_triangles;
     m->mask_sent.assign((size_t)((n_triangles + 31) / 32), 0u);
     const int words = (n_triangles + 31) / 32 + 4;
-    hipError_t e = m->verts.ensure((size_t)std::max(1, n_vertices) * 3);
-    if (e == hipSuccess) e = m->tris.ensure((size_t)std::max(1, n_triangles) * 3);
-    if (e == hipSuccess) e = m->mask.ensure((size_t)words);
-    if (e == hipSuccess && n_vertices) e = hipMemcpyAsync(m->verts.p, vertices, (size_t)n_vertices * 3 * sizeof(float), hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess && n_triangles) e = hipMemcpyAsync(m->tris.p, triangles, (size_t)n_triangles * 3 * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(m->mask.p, 0, (size_t)words * sizeof(uint32_t), ctx->stream);
+    PC_HIP(m->verts.ensure((size_t)std::max(1, n_vertices) * 3));
+    PC_HIP(m->tris.ensure((size_t)std::max(1, n_triangles) * 3));
+    PC_HIP(m->mask.ensure((size_t)words));
+    if (n_vertices) PC_HIP(hipMemcpyAsync(m->verts.p, vertices, (size_t)n_vertices * 3 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    if (n_triangles) PC_HIP(hipMemcpyAsync(m->tris.p, triangles, (size_t)n_triangles * 3 * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+    PC_HIP(hipMemsetAsync(m->mask.p, 0, (size_t)words * sizeof(uint32_t), ctx->stream));
     // acceleration structure (rtcCommitScene in the reference, ray_casting.cc:23-63): LBVH built on the GPU
-    if (e == hipSuccess && n_triangles > 0) {
+    if (n_triangles > 0) {
         const size_t n = (size_t)n_triangles;
         float lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
         for (int v = 0; v < n_vertices; v++)
@@ -147,50 +148,38 @@ int pc_mesh_create(pc_context* ctx, const float* vertices, int n_vertices, const
             }
         const float extent = std::max(std::max(hi[0] - lo[0], hi[1] - lo[1]), hi[2] - lo[2]);
         const float pad = 1e-5f * extent + 1e-30f;
+        // the build's scratch, freed where this block ends
         DevBuf<unsigned long long> keys_in, keys_out;
         DevBuf<float> box_lo, box_hi;
         DevBuf<int> links;      // parent (2n-1) | visits (n) | left (n) | right (n)
         DevBuf<uint32_t> bounds;
         DevBuf<uint8_t> sort_temp;
         const size_t temp_bytes = pc::bvh_sort_temp_bytes(n_triangles);
-        e = m->bvh_nodes.ensure(n);
-        if (e == hipSuccess) e = m->bvh_leaf_tri.ensure(n);
-        if (e == hipSuccess) e = keys_in.ensure(n);
-        if (e == hipSuccess) e = keys_out.ensure(n);
-        if (e == hipSuccess) e = box_lo.ensure(3 * (2 * n));
-        if (e == hipSuccess) e = box_hi.ensure(3 * (2 * n));
-        if (e == hipSuccess) e = links.ensure(5 * n + 8);
-        if (e == hipSuccess) e = bounds.ensure(8);
-        if (e == hipSuccess) e = sort_temp.ensure(temp_bytes + 16);
-        if (e == hipSuccess) {
-            pc::BvhBuildScratch sc;
-            sc.keys_in = keys_in.p;
-            sc.keys_out = keys_out.p;
-            sc.box_lo = box_lo.p;
-            sc.box_hi = box_hi.p;
-            sc.parent = links.p;
-            sc.visits = links.p + 2 * n;
-            sc.left = links.p + 3 * n;
-            sc.right = links.p + 4 * n;
-            sc.bounds = bounds.p;
-            e = pc::bvh_build(m->verts.p, m->tris.p, n_triangles, pad, sc, sort_temp.p, temp_bytes, m->bvh_nodes.p,
-                              m->bvh_leaf_tri.p, ctx->stream);
-        }
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        keys_in.release();
-        keys_out.release();
-        box_lo.release();
-        box_hi.release();
-        links.release();
-        bounds.release();
-        sort_temp.release();
+        PC_HIP(m->bvh_nodes.ensure(n));
+        PC_HIP(m->bvh_leaf_tri.ensure(n));
+        PC_HIP(keys_in.ensure(n));
+        PC_HIP(keys_out.ensure(n));
+        PC_HIP(box_lo.ensure(3 * (2 * n)));
+        PC_HIP(box_hi.ensure(3 * (2 * n)));
+        PC_HIP(links.ensure(5 * n + 8));
+        PC_HIP(bounds.ensure(8));
+        PC_HIP(sort_temp.ensure(temp_bytes + 16));
+        pc::BvhBuildScratch sc;
+        sc.keys_in = keys_in.p;
+        sc.keys_out = keys_out.p;
+        sc.box_lo = box_lo.p;
+        sc.box_hi = box_hi.p;
+        sc.parent = links.p;
+        sc.visits = links.p + 2 * n;
+        sc.left = links.p + 3 * n;
+        sc.right = links.p + 4 * n;
+        sc.bounds = bounds.p;
+        PC_HIP(pc::bvh_build(m->verts.p, m->tris.p, n_triangles, pad, sc, sort_temp.p, temp_bytes, m->bvh_nodes.p, m->bvh_leaf_tri.p,
+                             ctx->stream));
+        PC_HIP(hipStreamSynchronize(ctx->stream));
     }
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) {
-        pc_mesh_destroy(m);
-        return fail(PC_E_HIP, "mesh upload failed: %s", hipGetErrorString(e));
-    }
-    *out = m;
+    PC_HIP(hipStreamSynchronize(ctx->stream));
+    *out = m.release();
     return PC_OK;
 }
 
@@ -217,16 +206,6 @@ void pc_mesh_destroy(pc_mesh* m) {
         (void)hipSetDevice(m->ctx->device);
         (void)hipStreamSynchronize(m->ctx->stream);
     }
-    m->verts.release();
-    m->tris.release();
-    m->mask.release();
-    m->bvh_nodes.release();
-    m->bvh_leaf_tri.release();
-    m->d_xy.release();
-    m->d_hit.release();
-    m->d_pos.release();
-    m->d_uvt.release();
-    m->d_prim.release();
     delete m;
 }
 
@@ -280,21 +259,17 @@ int pc_corr_set_create(pc_context* ctx, pc_corr_set** out) {
     if (!ctx || !out) return fail(PC_E_INVALID, "null argument");
     *out = nullptr;
     PC_HIP(hipSetDevice(ctx->device));
-    pc_corr_set* s = new (std::nothrow) pc_corr_set();
+    std::unique_ptr<pc_corr_set, void (*)(pc_corr_set*)> s(new (std::nothrow) pc_corr_set(), pc_corr_set_destroy);
     if (!s) return fail(PC_E_INVALID, "out of host memory");
     s->ctx = ctx;
-    hipError_t e = s->counter.ensure(2);
-    if (e == hipSuccess) e = s->h_counter.ensure(2);
-    if (e == hipSuccess) e = s->out.ensure(64);
-    if (e == hipSuccess) e = s->h_out.ensure(64);
-    if (e == hipSuccess) e = s->lm_state.ensure(1);
-    if (e == hipSuccess) e = s->lm_host.ensure(1);
-    if (e == hipSuccess) e = hipMemsetAsync(s->counter.p, 0, 2 * sizeof(int), ctx->stream);
-    if (e != hipSuccess) {
-        pc_corr_set_destroy(s);
-        return fail(PC_E_HIP, "correspondence set: %s", hipGetErrorString(e));
-    }
-    *out = s;
+    PC_HIP(s->counter.ensure(2));
+    PC_HIP(s->h_counter.ensure(2));
+    PC_HIP(s->out.ensure(64));
+    PC_HIP(s->h_out.ensure(64));
+    PC_HIP(s->lm_state.ensure(1));
+    PC_HIP(s->lm_host.ensure(1));
+    PC_HIP(hipMemsetAsync(s->counter.p, 0, 2 * sizeof(int), ctx->stream));
+    *out = s.release();
     return PC_OK;
 }
 
@@ -305,33 +280,6 @@ void pc_corr_set_destroy(pc_corr_set* s) {
         (void)hipStreamSynchronize(s->ctx->stream);
         if (s->copy_stream) (void)hipStreamSynchronize(s->copy_stream);
     }
-    s->X.release();
-    s->x.release();
-    s->counter.release();
-    s->h_counter.release();
-    s->flag.release();
-    s->world.release();
-    s->block_counts.release();
-    s->block_offsets.release();
-    s->d_idx.release();
-    s->d_tgt.release();
-    for (auto& c : s->cache) c.xy.release();
-    for (auto& b : s->uncached_kps) b.release();
-    s->partials.release();
-    s->out.release();
-    s->h_out.release();
-    s->lm_partials4.release();
-    s->lm_state.release();
-    s->lm_host.release();
-    for (auto& b : s->t_block) b.release();
-    if (s->copy_stream) (void)hipStreamDestroy(s->copy_stream);
-    if (s->upload_done) (void)hipEventDestroy(s->upload_done);
-    s->t_sync.release();
-    s->t_obs.release();
-    s->t_pts.release();
-    s->t_partials.release();
-    s->t_out.release();
-    s->t_chain.release();
     delete s;
 }
 
@@ -367,20 +315,14 @@ static int corr_reserve(pc_context* ctx, pc_corr_set* s, size_t need) {
     DevBuf<float> nX;
     DevBuf<float2> nx;
     PC_HIP(nX.ensure(want * 3));
-    hipError_t e = nx.ensure(want);
-    if (e != hipSuccess) {
-        nX.release();
-        return fail(PC_E_HIP, "correspondence set: %s", hipGetErrorString(e));
-    }
+    PC_HIP(nx.ensure(want));
     if (s->capacity) {   // at most `capacity` entries are live; stream order puts the copies behind the appends
         (void)hipMemcpyAsync(nX.p, s->X.p, s->capacity * 3 * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream);
         (void)hipMemcpyAsync(nx.p, s->x.p, s->capacity * sizeof(float2), hipMemcpyDeviceToDevice, ctx->stream);
         PC_HIP(hipStreamSynchronize(ctx->stream));
     }
-    s->X.release();
-    s->x.release();
-    s->X = nX;
-    s->x = nx;
+    s->X = std::move(nX);
+    s->x = std::move(nx);
     s->capacity = want;
     return PC_OK;
 }
@@ -504,34 +446,29 @@ int pc_pnp_problem_create(pc_context* ctx, const float* X, const float* x, const
     if (!ctx || !out || n < 1 || !X || !x) return fail(PC_E_INVALID, "bad argument");
     *out = nullptr;
     PC_HIP(hipSetDevice(ctx->device));
-    pc_pnp_problem* p = new (std::nothrow) pc_pnp_problem();
+    std::unique_ptr<pc_pnp_problem, void (*)(pc_pnp_problem*)> p(new (std::nothrow) pc_pnp_problem(), pc_pnp_problem_destroy);
     if (!p) return fail(PC_E_INVALID, "out of host memory");
     p->ctx = ctx;
     p->n = n;
     p->has_weights = weights != nullptr;
     const int nb = pc::pnp_num_blocks(n);
-    hipError_t e = p->own_X.ensure((size_t)n * 3);
-    if (e == hipSuccess) e = p->own_x.ensure((size_t)n * 2);
-    if (e == hipSuccess && weights) e = p->own_w.ensure((size_t)n);
-    if (e == hipSuccess) e = p->own_partials.ensure((size_t)nb * 56);
-    if (e == hipSuccess) e = p->own_out.ensure(64);
-    if (e == hipSuccess) e = p->own_h_out.ensure(64);
-    if (e == hipSuccess) e = hipMemcpyAsync(p->own_X.p, X, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(p->own_x.p, x, (size_t)n * 2 * sizeof(float), hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess && weights)
-        e = hipMemcpyAsync(p->own_w.p, weights, (size_t)n * sizeof(float), hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    PC_HIP(p->own_X.ensure((size_t)n * 3));
+    PC_HIP(p->own_x.ensure((size_t)n * 2));
+    if (weights) PC_HIP(p->own_w.ensure((size_t)n));
+    PC_HIP(p->own_partials.ensure((size_t)nb * 56));
+    PC_HIP(p->own_out.ensure(64));
+    PC_HIP(p->own_h_out.ensure(64));
+    PC_HIP(hipMemcpyAsync(p->own_X.p, X, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    PC_HIP(hipMemcpyAsync(p->own_x.p, x, (size_t)n * 2 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    if (weights) PC_HIP(hipMemcpyAsync(p->own_w.p, weights, (size_t)n * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    PC_HIP(hipStreamSynchronize(ctx->stream));
     p->X = p->own_X.p;
     p->x = p->own_x.p;
     p->w = p->own_w.p;
     p->partials = p->own_partials.p;
     p->out = p->own_out.p;
     p->h_out = p->own_h_out.p;
-    if (e != hipSuccess) {
-        pc_pnp_problem_destroy(p);
-        return fail(PC_E_HIP, "PnP upload failed: %s", hipGetErrorString(e));
-    }
-    *out = p;
+    *out = p.release();
     return PC_OK;
 }
 
@@ -541,15 +478,6 @@ void pc_pnp_problem_destroy(pc_pnp_problem* p) {
         (void)hipSetDevice(p->ctx->device);
         (void)hipStreamSynchronize(p->ctx->stream);
     }
-    p->own_X.release();
-    p->own_x.release();
-    p->own_w.release();
-    p->own_partials.release();
-    p->own_out.release();
-    p->own_h_out.release();
-    p->own_lm_state.release();
-    p->own_lm_host.release();
-    p->own_lm_partials4.release();
     delete p;
 }
 
@@ -717,14 +645,18 @@ static int check_track_sources(const pc_track_source* sources, int n_sources, si
     return PC_OK;
 }
 
+// the set's upload stream and its event, made the first time either call below needs them
+static int ensure_copy_stream(pc_corr_set* s) {
+    if (!s->copy_stream) PC_HIP(s->copy_stream.create(hipStreamNonBlocking));
+    if (!s->upload_done) PC_HIP(s->upload_done.create(hipEventDisableTiming));
+    return PC_OK;
+}
+
 int pc_corr_set_reserve(pc_context* ctx, pc_corr_set* s, int n_matches, int n_keypoints, int n_cached) {
     if (!ctx || !s || n_matches < 0 || n_keypoints < 0 || n_cached < 0) return fail(PC_E_INVALID, "bad argument");
     if (s->t_inflight > 0) return fail(PC_E_STATE, "a frame is in flight: pc_track_frame_finish first");
     PC_HIP(hipSetDevice(ctx->device));
-    if (!s->copy_stream) {
-        PC_HIP(hipStreamCreateWithFlags(&s->copy_stream, hipStreamNonBlocking));
-        PC_HIP(hipEventCreateWithFlags(&s->upload_done, hipEventDisableTiming));
-    }
+    if (int src = ensure_copy_stream(s)) return src;
     const size_t total = (size_t)n_matches;
     for (auto& b : s->t_block) PC_HIP(b.ensure(total * 12 + 16 * 2 * pc::kTrackMaxSources + 16));   // per source: uint32 indices + float2 targets, 16-byte aligned
     PC_HIP(s->t_obs.ensure(total));
@@ -751,10 +683,7 @@ int pc_track_frame_upload(pc_context* ctx, pc_corr_set* s, const void* matches, 
     int rc = check_track_sources(sources, n_sources, matches_bytes, &total);
     if (rc != PC_OK) return rc;
     PC_HIP(hipSetDevice(ctx->device));
-    if (!s->copy_stream) {
-        PC_HIP(hipStreamCreateWithFlags(&s->copy_stream, hipStreamNonBlocking));
-        PC_HIP(hipEventCreateWithFlags(&s->upload_done, hipEventDisableTiming));
-    }
+    if (int src = ensure_copy_stream(s)) return src;
     // the other block: the launch that reads the current one may still be running
     s->t_cur = (s->t_cur + 1) % 3;
     s->t_block_bytes = matches_bytes;
@@ -983,19 +912,16 @@ int pc_pnp_total_cost(pc_context* ctx, const pc_pnp_problem* prob, const pc_pnp_
 int pc_debug_llt9(pc_context* ctx, const float* a81, const float* b9, float* l81, float* x9, int* positive_definite) {
     if (!ctx || !a81 || !b9 || !l81 || !x9 || !positive_definite) return fail(PC_E_INVALID, "null argument");
     PC_HIP(hipSetDevice(ctx->device));
-    float* d = nullptr;
-    PC_HIP(hipMalloc(reinterpret_cast<void**>(&d), (81 + 9 + 81 + 9 + 1) * sizeof(float)));
-    hipError_t e = hipMemcpyAsync(d, a81, 81 * sizeof(float), hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d + 81, b9, 9 * sizeof(float), hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) {
-        pc::launch_llt9_debug(d, d + 81, d + 90, d + 171, reinterpret_cast<int*>(d + 180), ctx->stream);
-        e = hipMemcpyAsync(l81, d + 90, 81 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream);
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(x9, d + 171, 9 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(positive_definite, d + 180, sizeof(int), hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    (void)hipFree(d);
-    if (e != hipSuccess) return fail(PC_E_HIP, "pc_debug_llt9: %s", hipGetErrorString(e));
+    DevBuf<float> buf;
+    PC_HIP(buf.ensure(81 + 9 + 81 + 9 + 1, /*exact=*/true));
+    float* const d = buf.p;
+    PC_HIP(hipMemcpyAsync(d, a81, 81 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    PC_HIP(hipMemcpyAsync(d + 81, b9, 9 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    pc::launch_llt9_debug(d, d + 81, d + 90, d + 171, reinterpret_cast<int*>(d + 180), ctx->stream);
+    PC_HIP(hipMemcpyAsync(l81, d + 90, 81 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    PC_HIP(hipMemcpyAsync(x9, d + 171, 9 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    PC_HIP(hipMemcpyAsync(positive_definite, d + 180, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    PC_HIP(hipStreamSynchronize(ctx->stream));
     return PC_OK;
 }
 
@@ -1022,26 +948,20 @@ int pc_debug_lm_decide(pc_context* ctx, int mode, int n_scripts, int n_rounds, i
     }
     const size_t b_cfg = ns * sizeof(pc::LmConfig), b_cam = ns * sizeof(pc::LmCamera), b_lim = ns * sizeof(int),
                  b_sums = n_sums * sizeof(float), b_states = n_states * sizeof(pc::LmDebugState);   // (every size a multiple of 4)
-    char* d = nullptr;
-    PC_HIP(hipMalloc(reinterpret_cast<void**>(&d), b_cfg + b_cam + b_lim + b_sums + b_states));
-    char *d_cfg = d, *d_cam = d_cfg + b_cfg, *d_lim = d_cam + b_cam, *d_sums = d_lim + b_lim, *d_states = d_sums + b_sums;
-    hipError_t e = hipMemcpyAsync(d_cfg, cfgs.data(), b_cfg, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_cam, cams.data(), b_cam, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_lim, limits.data(), b_lim, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_sums, sums, b_sums, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) {
-        pc::launch_lm_decide_debug(mode, n_scripts, n_rounds, reinterpret_cast<const pc::LmConfig*>(d_cfg),
-                                   reinterpret_cast<const pc::LmCamera*>(d_cam), reinterpret_cast<const int*>(d_lim),
-                                   reinterpret_cast<const float*>(d_sums), reinterpret_cast<pc::LmDebugState*>(d_states), ctx->stream);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(states, d_states, b_states, hipMemcpyDeviceToHost, ctx->stream);
-    // (the host vectors above are pageable: the copies from them have been staged by the time hipMemcpyAsync returns; waiting
-    // here before they go out of scope all the same)
-    const hipError_t e_sync = hipStreamSynchronize(ctx->stream);
-    if (e == hipSuccess) e = e_sync;
-    (void)hipFree(d);
-    if (e != hipSuccess) return fail(PC_E_HIP, "pc_debug_lm_decide: %s", hipGetErrorString(e));
+    DevBuf<char> buf;   // declared behind the host vectors: an early return frees it, which waits for the device, before they go
+    PC_HIP(buf.ensure(b_cfg + b_cam + b_lim + b_sums + b_states, /*exact=*/true));
+    char *d_cfg = buf.p, *d_cam = d_cfg + b_cfg, *d_lim = d_cam + b_cam, *d_sums = d_lim + b_lim, *d_states = d_sums + b_sums;
+    // (the host vectors above are pageable: the copies from them have been staged by the time hipMemcpyAsync returns)
+    PC_HIP(hipMemcpyAsync(d_cfg, cfgs.data(), b_cfg, hipMemcpyHostToDevice, ctx->stream));
+    PC_HIP(hipMemcpyAsync(d_cam, cams.data(), b_cam, hipMemcpyHostToDevice, ctx->stream));
+    PC_HIP(hipMemcpyAsync(d_lim, limits.data(), b_lim, hipMemcpyHostToDevice, ctx->stream));
+    PC_HIP(hipMemcpyAsync(d_sums, sums, b_sums, hipMemcpyHostToDevice, ctx->stream));
+    pc::launch_lm_decide_debug(mode, n_scripts, n_rounds, reinterpret_cast<const pc::LmConfig*>(d_cfg),
+                               reinterpret_cast<const pc::LmCamera*>(d_cam), reinterpret_cast<const int*>(d_lim),
+                               reinterpret_cast<const float*>(d_sums), reinterpret_cast<pc::LmDebugState*>(d_states), ctx->stream);
+    PC_HIP(hipGetLastError());
+    PC_HIP(hipMemcpyAsync(states, d_states, b_states, hipMemcpyDeviceToHost, ctx->stream));
+    PC_HIP(hipStreamSynchronize(ctx->stream));
     return PC_OK;
 }
 
@@ -1055,12 +975,12 @@ struct pc_refine_problem {
     const pc_mesh* mesh = nullptr;
     int n_frames = 0, n_edges = 0, block_len = 6, opt_f = 0, opt_pp = 0;
     size_t n_kp = 0, n_res = 0;
+    Event sweep_begin, sweep_end;   // around the kernel of every sweep
     DevBuf<int> kp_offset, edge_src, edge_tgt, edge_offset, edge_valid;
     DevBuf<float2> kp_xy, res_tgt_xy;
     DevBuf<double2> edge_cost;
     DevBuf<uint32_t> res_src_kp, prim_cache;
     DevBuf<float4> tri_plane, tri_verts;
-    hipEvent_t sweep_begin = nullptr, sweep_end = nullptr;   // around the kernel of every sweep
     int cost_launches = 0, neq_launches = 0;
     double cost_ms = 0.0, neq_ms = 0.0;
     DevBuf<float> edge_weight;
@@ -1162,7 +1082,7 @@ int pc_refine_problem_create_parts(pc_context* ctx, const pc_mesh* mesh, const p
             return fail(PC_E_INVALID, "the parts hold %zu keypoints and %zu residuals, the offsets say %zu and %zu", kp_sum, res_sum, n_kp, n_res);
     }
     PC_HIP(hipSetDevice(ctx->device));
-    pc_refine_problem* p = new (std::nothrow) pc_refine_problem();
+    std::unique_ptr<pc_refine_problem, void (*)(pc_refine_problem*)> p(new (std::nothrow) pc_refine_problem(), pc_refine_problem_destroy);
     if (!p) return fail(PC_E_INVALID, "out of host memory");
     p->ctx = ctx;
     p->mesh = mesh;
@@ -1179,70 +1099,61 @@ int pc_refine_problem_create_parts(pc_context* ctx, const pc_mesh* mesh, const p
     fixed.front() = fixed.back() = 1;  // IsGroundTruth (refiner.cc:268-271)
     const int B2 = 2 * d->block_len, nacc = B2 * (B2 + 1) / 2 + B2;
     hipStream_t s = ctx->stream;
-    hipError_t e = upload(p->kp_offset, d->kp_offset, (size_t)d->n_frames + 1, s);
-    if (e == hipSuccess) e = upload(p->edge_src, d->edge_src, (size_t)d->n_edges, s);
-    if (e == hipSuccess) e = upload(p->edge_tgt, d->edge_tgt, (size_t)d->n_edges, s);
-    if (e == hipSuccess) e = upload(p->edge_offset, d->edge_offset, (size_t)d->n_edges + 1, s);
-    if (e == hipSuccess) e = upload(p->edge_weight, d->edge_weight, (size_t)d->n_edges, s);
-    if (e == hipSuccess) e = upload(p->frame_fixed, fixed.data(), fixed.size(), s);
-    if (e == hipSuccess) e = p->kp_xy.ensure(n_kp ? n_kp : 1);
-    if (e == hipSuccess) e = p->res_src_kp.ensure(n_res ? n_res : 1);
-    if (e == hipSuccess) e = p->res_tgt_xy.ensure(n_res ? n_res : 1);
+    PC_HIP(upload(p->kp_offset, d->kp_offset, (size_t)d->n_frames + 1, s));
+    PC_HIP(upload(p->edge_src, d->edge_src, (size_t)d->n_edges, s));
+    PC_HIP(upload(p->edge_tgt, d->edge_tgt, (size_t)d->n_edges, s));
+    PC_HIP(upload(p->edge_offset, d->edge_offset, (size_t)d->n_edges + 1, s));
+    PC_HIP(upload(p->edge_weight, d->edge_weight, (size_t)d->n_edges, s));
+    PC_HIP(upload(p->frame_fixed, fixed.data(), fixed.size(), s));
+    PC_HIP(p->kp_xy.ensure(n_kp ? n_kp : 1));
+    PC_HIP(p->res_src_kp.ensure(n_res ? n_res : 1));
+    PC_HIP(p->res_tgt_xy.ensure(n_res ? n_res : 1));
     {   // Every part to its place.  The pieces are pageable host memory: the runtime page-locks the source of a large copy on
         // the fly, which is what bounds this (17 GB/s from 4-KiB pages, 38-44 GB/s from 2-MiB pages: the host side allocates
         // its parts with MADV_HUGEPAGE).  Measured and not better: hipHostRegister around the copies, several threads with a
         // stream each, a hand-made staging pipeline through page-locked blocks (tools/probes/pageable_upload_probe.hip).
         size_t kp_at = 0, res_at = 0;
-        for (int t = 0; t < n_parts && e == hipSuccess; t++) {
+        for (int t = 0; t < n_parts; t++) {
             const pc_refine_part& part = parts[t];
             const size_t nk = (size_t)part.n_keypoints, nr = (size_t)part.n_residuals;
-            if (nk) e = hipMemcpyAsync(p->kp_xy.p + kp_at, part.kp_xy, nk * sizeof(float2), hipMemcpyHostToDevice, s);
-            if (e == hipSuccess && nr) e = hipMemcpyAsync(p->res_src_kp.p + res_at, part.res_src_kp, nr * sizeof(uint32_t), hipMemcpyHostToDevice, s);
-            if (e == hipSuccess && nr) e = hipMemcpyAsync(p->res_tgt_xy.p + res_at, part.res_tgt_xy, nr * sizeof(float2), hipMemcpyHostToDevice, s);
+            if (nk) PC_HIP(hipMemcpyAsync(p->kp_xy.p + kp_at, part.kp_xy, nk * sizeof(float2), hipMemcpyHostToDevice, s));
+            if (nr) PC_HIP(hipMemcpyAsync(p->res_src_kp.p + res_at, part.res_src_kp, nr * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+            if (nr) PC_HIP(hipMemcpyAsync(p->res_tgt_xy.p + res_at, part.res_tgt_xy, nr * sizeof(float2), hipMemcpyHostToDevice, s));
             kp_at += nk;
             res_at += nr;
         }
     }
-    if (e == hipSuccess) e = p->prim_cache.ensure(n_kp ? n_kp : 1);
-    if (e == hipSuccess) e = hipMemsetAsync(p->prim_cache.p, 0xff, (n_kp ? n_kp : 1) * sizeof(uint32_t), s);
-    if (e == hipSuccess) e = p->edge_cost.ensure((size_t)std::max(1, d->n_edges));
-    if (e == hipSuccess) e = p->h_edge_cost.ensure((size_t)std::max(1, d->n_edges));
-    if (e == hipSuccess) e = p->edge_valid.ensure((size_t)std::max(1, d->n_edges));
-    if (e == hipSuccess) e = p->edge_blocks.ensure((size_t)std::max(1, d->n_edges) * nacc);
-    if (e == hipSuccess) e = p->cams.ensure((size_t)d->n_frames);
-    if (e == hipSuccess) e = hipEventCreate(&p->sweep_begin);
-    if (e == hipSuccess) e = hipEventCreate(&p->sweep_end);
-    if (e == hipSuccess) e = p->tri_plane.ensure(2 * (size_t)std::max(1, mesh->n_triangles));
-    if (e == hipSuccess) e = p->tri_verts.ensure(3 * (size_t)std::max(1, mesh->n_triangles));
-    if (e == hipSuccess) {
-        pc::launch_refine_tri_planes(refine_view(p), p->tri_plane.p, s);
-        pc::launch_refine_tri_verts(refine_view(p), p->tri_verts.p, s);
-        e = hipGetLastError();
-    }
+    PC_HIP(p->prim_cache.ensure(n_kp ? n_kp : 1));
+    PC_HIP(hipMemsetAsync(p->prim_cache.p, 0xff, (n_kp ? n_kp : 1) * sizeof(uint32_t), s));
+    PC_HIP(p->edge_cost.ensure((size_t)std::max(1, d->n_edges)));
+    PC_HIP(p->h_edge_cost.ensure((size_t)std::max(1, d->n_edges)));
+    PC_HIP(p->edge_valid.ensure((size_t)std::max(1, d->n_edges)));
+    PC_HIP(p->edge_blocks.ensure((size_t)std::max(1, d->n_edges) * nacc));
+    PC_HIP(p->cams.ensure((size_t)d->n_frames));
+    PC_HIP(p->sweep_begin.create());
+    PC_HIP(p->sweep_end.create());
+    PC_HIP(p->tri_plane.ensure(2 * (size_t)std::max(1, mesh->n_triangles)));
+    PC_HIP(p->tri_verts.ensure(3 * (size_t)std::max(1, mesh->n_triangles)));
+    pc::launch_refine_tri_planes(refine_view(p.get()), p->tri_plane.p, s);
+    pc::launch_refine_tri_verts(refine_view(p.get()), p->tri_verts.p, s);
+    PC_HIP(hipGetLastError());
     // the residuals' keypoint indices are checked where they now are (edge_valid is free until the first sweep)
     int bad[2] = {std::numeric_limits<int>::max(), 0};
-    if (e == hipSuccess && d->n_edges > 0) {
-        e = p->edge_valid.ensure((size_t)std::max(2, d->n_edges));
-        if (e == hipSuccess) e = hipMemcpyAsync(p->edge_valid.p, bad, sizeof(bad), hipMemcpyHostToDevice, s);
-        if (e == hipSuccess) {
-            pc::launch_refine_validate(refine_view(p), p->edge_valid.p, s);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) e = hipMemcpyAsync(bad, p->edge_valid.p, sizeof(bad), hipMemcpyDeviceToHost, s);
+    if (d->n_edges > 0) {
+        PC_HIP(p->edge_valid.ensure((size_t)std::max(2, d->n_edges)));
+        PC_HIP(hipMemcpyAsync(p->edge_valid.p, bad, sizeof(bad), hipMemcpyHostToDevice, s));
+        pc::launch_refine_validate(refine_view(p.get()), p->edge_valid.p, s);
+        PC_HIP(hipGetLastError());
+        PC_HIP(hipMemcpyAsync(bad, p->edge_valid.p, sizeof(bad), hipMemcpyDeviceToHost, s));
     }
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) {
-        pc_refine_problem_destroy(p);
-        return fail(PC_E_HIP, "refine problem upload failed: %s", hipGetErrorString(e));
-    }
+    PC_HIP(hipStreamSynchronize(s));
     if (bad[0] != std::numeric_limits<int>::max()) {
         const int edge = bad[0];
         const int src_kps = d->kp_offset[d->edge_src[edge] + 1] - d->kp_offset[d->edge_src[edge]];
-        pc_refine_problem_destroy(p);
         return fail(PC_E_INVALID, "edge %d references a keypoint (up to %d) its source frame does not have (%d keypoints)", edge, bad[1], src_kps);
     }
     p->h_edge_weight.assign(d->edge_weight, d->edge_weight + d->n_edges);
-    *out = p;
+    *out = p.release();
     return PC_OK;
 }
 
@@ -1270,25 +1181,6 @@ void pc_refine_problem_destroy(pc_refine_problem* p) {
         (void)hipSetDevice(p->ctx->device);
         (void)hipStreamSynchronize(p->ctx->stream);
     }
-    p->kp_offset.release();
-    p->edge_src.release();
-    p->edge_tgt.release();
-    p->edge_offset.release();
-    p->edge_valid.release();
-    p->kp_xy.release();
-    p->res_tgt_xy.release();
-    p->edge_cost.release();
-    p->res_src_kp.release();
-    p->prim_cache.release();
-    p->tri_plane.release();
-    if (p->sweep_begin) (void)hipEventDestroy(p->sweep_begin);
-    if (p->sweep_end) (void)hipEventDestroy(p->sweep_end);
-    p->tri_verts.release();
-    p->edge_weight.release();
-    p->edge_blocks.release();
-    p->frame_fixed.release();
-    p->cams.release();
-    p->h_edge_cost.release();
     delete p;
 }
 

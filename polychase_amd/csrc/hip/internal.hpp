@@ -1,4 +1,4 @@
-// internal.hpp -- host-side structures shared by api.hip and analyzer.hip (not part of the C ABI).
+// internal.hpp -- host-side structures shared by the api*.hip units (not part of the C ABI).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -7,12 +7,16 @@
 #include <cstdlib>
 
 #include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <memory>
 #include <new>
 #include <string>
+#include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "../../../include/polychase_hip.h"
@@ -47,23 +51,49 @@ inline bool trace_allocations() {
     return on;
 }
 
+// pc_debug_live_resources: what the four owners below hold in this process, counted where a handle is acquired and let go
+enum { kLiveDevice = 0, kLivePinned, kLiveStreams, kLiveEvents };
+inline std::atomic<int> g_live[4];
+inline void live_add(int kind, int d) { g_live[kind].fetch_add(d, std::memory_order_relaxed); }
+
+// The owners of everything behind the C ABI: a device buffer, a pinned host buffer, a stream, an event.  Each lets go of what
+// it holds in its destructor, cannot be copied, and is empty after a move.  None may be a global or a function-local static
+// (its destructor would run after the HIP runtime has shut down).  A struct declares its streams and events before the buffers
+// that work on them: members are destroyed in reverse order, so the buffers are freed first and the streams destroyed last.
 template <typename T>
 struct DevBuf {
     T* p = nullptr;
     size_t cap = 0;  // elements
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    DevBuf(DevBuf&& o) noexcept : p(std::exchange(o.p, nullptr)), cap(std::exchange(o.cap, 0)) {}
+    DevBuf& operator=(DevBuf&& o) noexcept {
+        if (this != &o) {
+            release();
+            p = std::exchange(o.p, nullptr);
+            cap = std::exchange(o.cap, 0);
+        }
+        return *this;
+    }
+    ~DevBuf() { release(); }
     hipError_t ensure(size_t n, bool exact = false) {   // exact: a buffer of fixed size, no room to grow
         if (n <= cap) return hipSuccess;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
+        const size_t old = cap;
+        release();
         size_t want = exact ? n : n + n / 2 + 64;   // generous: a reallocation synchronises the device
-        if (trace_allocations()) fprintf(stderr, "[polychase_hip] device buffer %zu -> %zu bytes\n", cap * sizeof(T), want * sizeof(T));
+        if (trace_allocations()) fprintf(stderr, "[polychase_hip] device buffer %zu -> %zu bytes\n", old * sizeof(T), want * sizeof(T));
         hipError_t e = hipMalloc(reinterpret_cast<void**>(&p), want * sizeof(T));
-        if (e == hipSuccess) cap = want;
+        if (e != hipSuccess) return e;
+        cap = want;
+        live_add(kLiveDevice, 1);
         return e;
     }
     void release() {
-        if (p) (void)hipFree(p);
+        if (p) {
+            (void)hipFree(p);
+            live_add(kLiveDevice, -1);
+        }
         p = nullptr;
         cap = 0;
     }
@@ -73,33 +103,118 @@ template <typename T>
 struct PinBuf {
     T* p = nullptr;
     size_t cap = 0;
+    PinBuf() = default;
+    PinBuf(const PinBuf&) = delete;
+    PinBuf& operator=(const PinBuf&) = delete;
+    PinBuf(PinBuf&& o) noexcept : p(std::exchange(o.p, nullptr)), cap(std::exchange(o.cap, 0)) {}
+    PinBuf& operator=(PinBuf&& o) noexcept {
+        if (this != &o) {
+            release();
+            p = std::exchange(o.p, nullptr);
+            cap = std::exchange(o.cap, 0);
+        }
+        return *this;
+    }
+    ~PinBuf() { release(); }
     hipError_t ensure(size_t n) {
         if (n <= cap) return hipSuccess;
-        if (p) (void)hipHostFree(p);
-        p = nullptr;
-        cap = 0;
+        const size_t old = cap;
+        release();
         size_t want = n + n / 2 + 64;   // pinned allocations take tens of milliseconds
-        if (trace_allocations()) fprintf(stderr, "[polychase_hip] pinned buffer %zu -> %zu bytes\n", cap * sizeof(T), want * sizeof(T));
+        if (trace_allocations()) fprintf(stderr, "[polychase_hip] pinned buffer %zu -> %zu bytes\n", old * sizeof(T), want * sizeof(T));
         hipError_t e = hipHostMalloc(reinterpret_cast<void**>(&p), want * sizeof(T), hipHostMallocDefault);
-        if (e == hipSuccess) cap = want;
+        if (e != hipSuccess) return e;
+        cap = want;
+        live_add(kLivePinned, 1);
         return e;
     }
     void release() {
-        if (p) (void)hipHostFree(p);
+        if (p) {
+            (void)hipHostFree(p);
+            live_add(kLivePinned, -1);
+        }
         p = nullptr;
         cap = 0;
     }
 };
 
+struct Stream {
+    hipStream_t s = nullptr;
+    Stream() = default;
+    Stream(const Stream&) = delete;
+    Stream& operator=(const Stream&) = delete;
+    Stream(Stream&& o) noexcept : s(std::exchange(o.s, nullptr)) {}
+    Stream& operator=(Stream&& o) noexcept {
+        if (this != &o) {
+            release();
+            s = std::exchange(o.s, nullptr);
+        }
+        return *this;
+    }
+    ~Stream() { release(); }
+    hipError_t create(unsigned flags) {   // an empty owner only
+        hipError_t e = hipStreamCreateWithFlags(&s, flags);
+        if (e == hipSuccess) live_add(kLiveStreams, 1);
+        else s = nullptr;
+        return e;
+    }
+    void release() {
+        if (s) {
+            (void)hipStreamDestroy(s);
+            live_add(kLiveStreams, -1);
+        }
+        s = nullptr;
+    }
+    operator hipStream_t() const { return s; }
+};
+
+struct Event {
+    hipEvent_t e = nullptr;
+    Event() = default;
+    Event(const Event&) = delete;
+    Event& operator=(const Event&) = delete;
+    Event(Event&& o) noexcept : e(std::exchange(o.e, nullptr)) {}
+    Event& operator=(Event&& o) noexcept {
+        if (this != &o) {
+            release();
+            e = std::exchange(o.e, nullptr);
+        }
+        return *this;
+    }
+    ~Event() { release(); }
+    hipError_t create(unsigned flags = hipEventDefault) {   // an empty owner only
+        hipError_t rc = hipEventCreateWithFlags(&e, flags);
+        if (rc == hipSuccess) live_add(kLiveEvents, 1);
+        else e = nullptr;
+        return rc;
+    }
+    void release() {
+        if (e) {
+            (void)hipEventDestroy(e);
+            live_add(kLiveEvents, -1);
+        }
+        e = nullptr;
+    }
+    operator hipEvent_t() const { return e; }
+};
+
+template <typename Owner>
+constexpr bool owns_alone = !std::is_copy_constructible<Owner>::value && !std::is_copy_assignable<Owner>::value &&
+                            std::is_nothrow_move_constructible<Owner>::value && std::is_nothrow_move_assignable<Owner>::value;
+static_assert(owns_alone<DevBuf<float>> && owns_alone<PinBuf<float>> && owns_alone<Stream> && owns_alone<Event>,
+              "owners are not copyable and move without throwing (std::vector<Slot>, std::vector<Job>)");
+
 struct TimedRange {
     int cls;
-    hipEvent_t a, b;
+    Event a, b;
 };
 
 }  // namespace pc
 
 using pc::DevBuf;
+using pc::Event;
 using pc::PinBuf;
+using pc::Stream;
 using pc::TimedRange;
 using pc::fail;
 
@@ -109,6 +224,7 @@ using pc::fail;
 //   visiting order; the counters go to pinned memory (ev_b).  detect_finish() then reads the keypoint count -- and
 //   redoes the frame on the slow path (candidate count on the host, rocPRIM sort) if a fast-path bound was exceeded.
 struct DetectScratch {
+    Event ev_b;
     DevBuf<unsigned long long> keys, keys_bucketed, keys_sorted;
     DevBuf<unsigned long long> key_slots;  // kSortBuckets x kBucketSlots bucket slots of the fused chain (launch_nms), when it runs
     DevBuf<float> eig;                     // min-eig map (K2 -> K3, K5)
@@ -123,29 +239,10 @@ struct DetectScratch {
     DevBuf<uint32_t> sup_grid;             // min_distance > 64: the accepted corners by grid cell (kernels_gftt.hip), on demand
     DevBuf<uint32_t> bin_hist;             // keypoints per 64x64 tile (the analyzer's detections; stage-level calls use the context's)
     PinBuf<uint32_t> h_counters;           // counters[0..7] after the detection
-    hipEvent_t ev_b = nullptr;
     uint32_t cand_cap = 0;                 // candidates the fast path holds
     int counter_words = 0;                 // words of `counters` (header, cell maxima, bucket counts + cursors, tickets)
     uint32_t ticket_stride = 0;            // words between the three ticket arrays at the end of `counters`
     bool cleared = false;                  // `counters` were zeroed in front of the coming detection (by the frame's level-0 kernel)
-    void release() {
-        keys.release();
-        keys_bucketed.release();
-        key_slots.release();
-        keys_sorted.release();
-        eig.release();
-        cov.release();
-        box_rows.release();
-        cstate.release();
-        counters.release();
-        bucket_offsets.release();
-        per_block.release();
-        sup_grid.release();
-        bin_hist.release();
-        h_counters.release();
-        if (ev_b) (void)hipEventDestroy(ev_b);
-        ev_b = nullptr;
-    }
 };
 
 struct pc_context {
@@ -156,13 +253,14 @@ struct pc_context {
     // overlap, so the tail of one launch and the gap before the next are filled by the other lane's wavefronts.
     // (HIP multiplexes streams onto GPU_MAX_HW_QUEUES hardware queues, 4 unless raised, and a stream that shares a queue
     // waits behind the other's commands: pc_runtime_init raises the default before the first HIP call.)
-    hipStream_t stream = nullptr;
-    hipStream_t stream_b = nullptr;
+    // (Streams and events stand in front of the buffers: ~pc_context frees the buffers first and destroys the streams last.)
+    Stream stream;
+    Stream stream_b;
     hipStream_t lane_stream(int lane) const { return lane ? stream_b : stream; }
     // pc_analyzer runs frame preparation (gray, pyramid, detection, keypoint ordering) on its own
     // stream so that it overlaps the LK launch of the previous frame1 on `stream`.  `work` is the stream
     // the image / detection helpers enqueue on: `stream` by default, `prep_stream` inside the analyzer.
-    hipStream_t prep_stream = nullptr;
+    Stream prep_stream;
     // Detection follows the image path on prep_stream.
     hipError_t sync_side_streams() const {
         hipError_t e = copy_stream ? hipStreamSynchronize(copy_stream) : hipSuccess;
@@ -170,8 +268,8 @@ struct pc_context {
         if (stream_b && e == hipSuccess) e = hipStreamSynchronize(stream_b);
         return e;
     }
-    hipStream_t work = nullptr;
-    hipEvent_t prep_fence = nullptr;     // orders `stream` after everything queued on prep_stream so far
+    hipStream_t work = nullptr;          // not owned: `stream` or `prep_stream`
+    Event prep_fence;                    // orders `stream` after everything queued on prep_stream so far
     bool prep_dirty = false;
     // pc_context_set_gray_conversion: the channel weights and the float transfer table of the RGB frames put from now on
     int gray_w[3] = {9798, 19235, 3735};
@@ -181,14 +279,18 @@ struct pc_context {
     const uint8_t* gray_table_dev() const { return gray_table_on ? gray_table_buf[gray_table_cur].p : nullptr; }
     std::vector<uint8_t> gray_table_host;  // the table in force (pc_context_get_gray_conversion)
     bool gray_default_weights() const { return gray_w[0] == 9798 && gray_w[1] == 19235 && gray_w[2] == 3735; }
-    // staging of host-provided frames
-    DevBuf<uint8_t> staging;
     // the analyzer's host frames (PC_FRAME_PINNED_HOST): transfers on a stream of their own, two buffers in turn;
     // staging_ev[b] = {copy into b complete (copy stream), the kernel that reads b has run (preparation stream)}
-    hipStream_t copy_stream = nullptr;   // POLYCHASE_COPY_STREAM=0: none (the transfer is enqueued in front of the frame's kernels)
-    DevBuf<uint8_t> staging2[2];
-    hipEvent_t staging_ev[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
+    Stream copy_stream;                  // POLYCHASE_COPY_STREAM=0: none (the transfer is enqueued in front of the frame's kernels)
+    Event staging_ev[2][2];
     int staging_turn = 0;
+    // timing
+    unsigned timing_mask = 0;   // bit k: time kernel class k with HIP events
+    std::vector<TimedRange> ranges;
+    std::vector<Event> event_pool;
+    // staging of host-provided frames
+    DevBuf<uint8_t> staging;
+    DevBuf<uint8_t> staging2[2];
     // GFTT scratch
     DevBuf<int2> sup_offsets;              // suppression neighbourhood for sup_min_distance
     DevBuf<int> sup_rows;                  // the same as half-widths per row, [2 * sup_R + 1]
@@ -198,16 +300,16 @@ struct pc_context {
     // candidates of the latest finished detection + 25 %: the detections enqueued next size their launches for that many
     // (the count itself stays on the device; a frame with more is redone with launches for the full capacity)
     uint32_t cand_hint = 0;
-    struct DetectScratch* detect = nullptr;  // scratch of the stage-level pc_frame_detect
+    std::unique_ptr<DetectScratch> detect;   // scratch of the stage-level pc_frame_detect
     DevBuf<uint8_t> sort_temp;
-    const pc_frame* eig_owner = nullptr;
+    const pc_frame* eig_owner = nullptr;   // not owned: the frame whose response map `detect` holds
     // pc_frame_set_mask_polygons: the snapped vertices on their way to the device (the call waits for the launch that reads them)
     PinBuf<int32_t> poly_host;
     DevBuf<int32_t> poly_dev;
     // LK scratch
     // raw LK outputs, compaction scratch and packed records: one set per job lane of the analyzer (set 0: stage-level calls)
     DevBuf<float4> lk_rec[2];              // raw records in visiting order (kernels.hpp LKParams::out_rec)
-    const uint32_t* lk_slot_of[2] = {nullptr, nullptr};   // inverse visiting order of the latest launch into the set
+    const uint32_t* lk_slot_of[2] = {nullptr, nullptr};   // not owned (a frame's d_perm or lk_perm): inverse visiting order of the latest launch into the set
     DevBuf<float2> lk_cxy;
     DevBuf<uint8_t> lk_ustatus;            // pc_lk_track: unpacked status
     DevBuf<float> lk_cerr;
@@ -234,10 +336,7 @@ struct pc_context {
     // row offsets (128 B) | keypoints | src indices | tgt xy | errors, every part 16-byte aligned
     DevBuf<uint8_t> lk_pack[2];
     PinBuf<long long> h_row_offset;
-    // timing
-    unsigned timing_mask = 0;   // bit k: time kernel class k with HIP events
-    std::vector<TimedRange> ranges;
-    std::vector<hipEvent_t> event_pool;
+    // timing (the events: above)
     int launches[PC_K_COUNT] = {0};
     double total_ms[PC_K_COUNT] = {0};
     double busy_ms[PC_K_COUNT] = {0};    // time during which at least one launch of the class was executing
@@ -247,29 +346,29 @@ struct pc_frame {
     pc_context* ctx = nullptr;
     int w = 0, h = 0, win = 0, max_level = 0, nlevels = 0;
     pc::Level levels[PC_MAX_LEVELS];
-    uint8_t* slab = nullptr;
+    DevBuf<uint8_t> slab;
     size_t slab_bytes = 0;
-    float2* d_kps = nullptr;
+    DevBuf<float2> d_kps;
     int kp_cap = 0;
     int n_kps = -1;   // -1: none
     int n_cands = -1;
-    uint32_t* d_perm = nullptr;   // LK visiting order of d_kps (spatial bins) [perm_cap], then its inverse [perm_cap]; valid iff perm_valid
+    DevBuf<uint32_t> d_perm;      // LK visiting order of d_kps (spatial bins) [perm_cap], then its inverse [perm_cap]; valid iff perm_valid
     int perm_cap = 0;
     bool perm_valid = false;
     // detection mask (gftt.cc:45-83): a packed w x h plane of bytes, allocated the first time the frame is given one;
     // mask_on: the next detection of this frame honours it
-    uint8_t* d_mask = nullptr;
+    DevBuf<uint8_t> d_mask;
     bool mask_on = false;
     // target-side mask of a frame in an analyzer's ring (pc_analyzer_set_target_mask_margin): the margin the frame was put under
     // while a mask was in force -- rows that end in this frame are judged by d_mask (0) or by d_choked, its choked plane (> 0) --
     // or -1: the frame keeps every row.  d_choked is allocated the first time an analyzer needs it.
     int target_margin = -1;
-    uint8_t* d_choked = nullptr;
+    DevBuf<uint8_t> d_choked;
     // masked windows (pc_lk_track_window_masked): the weight planes W_l of the mask, one per level in the level's image geometry
     // (wt[l]: interior origin; the padding is on), and behind them the packed M_l of the levels >= 1.  One allocation, made the
     // first time the frame needs its weights; weights_valid: the planes are those of the mask in d_mask (every change of the mask
     // clears it).  An analyzer's frame: window_weights says that the frame was put with the option and a mask in force.
-    uint8_t* d_weights = nullptr;
+    DevBuf<uint8_t> d_weights;
     uint8_t* wt[PC_MAX_LEVELS] = {nullptr};
     uint8_t* wm[PC_MAX_LEVELS] = {nullptr};
     bool weights_valid = false;

@@ -28,6 +28,7 @@ SYMBOLS = [
     "pc_gray_quantize_weights", "pc_float_transfer_index",
     "pc_context_enable_timing", "pc_context_get_timing", "pc_context_get_busy_time", "pc_context_reset_timing",
     "pc_debug_lk_profile", "pc_debug_lk_x86_stats", "pc_debug_llt9", "pc_debug_lm_decide",
+    "pc_debug_live_resources",
     "pc_frame_create", "pc_frame_destroy", "pc_frame_set_rgb", "pc_frame_set_rgb_f32", "pc_frame_set_gray",
     "pc_host_buffer_alloc", "pc_host_buffer_free",
     "pc_frame_num_levels", "pc_frame_level_size", "pc_frame_download_gray", "pc_frame_download_level",
@@ -175,6 +176,7 @@ def load():
     L.pc_debug_lk_x86_stats.argtypes = [vp, C.c_int, C.POINTER(C.c_ulonglong)]
     L.pc_debug_llt9.argtypes = [vp, vp, vp, vp, vp, ip]
     L.pc_debug_lm_decide.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
+    L.pc_debug_live_resources.argtypes = [C.POINTER(C.c_int * 4)]
     L.pc_frame_create.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]
     L.pc_frame_destroy.argtypes = [vp]
     L.pc_frame_destroy.restype = None
@@ -302,6 +304,14 @@ def float_transfer_table(kind: str, gamma: float = 2.2, exposure: float = 0.0) -
     out = np.empty(TRANSFER_ENTRIES, np.uint8)
     _check(load().pc_float_transfer_table(TRANSFER_KINDS[kind], float(gamma), float(exposure), out.ctypes.data))
     return out
+
+
+def live_resources() -> tuple[int, int, int, int]:
+    """(device allocations, pinned allocations, streams, events) the library's objects own in this process right now
+    (pc_debug_live_resources)"""
+    out = (C.c_int * 4)()
+    _check(load().pc_debug_live_resources(C.byref(out)))
+    return tuple(out)
 
 
 def flow_options(**kw) -> FlowOptions:

@@ -38,6 +38,30 @@ def test_no_cpu_fallback_without_device():
     assert b"polychase_hip" in hip.load().pc_version()
 
 
+def test_refused_context_owns_nothing_without_device():
+    """pc_debug_live_resources in a fresh process without a device: nothing owned before, hip.Context(0) raises, nothing owned after"""
+    import subprocess
+    import sys
+
+    import torch
+    if torch.cuda.is_available():
+        pytest.skip("GPU present")
+    path = build.hip_library_path()
+    if not os.path.exists(path):
+        build.build_hip()
+    code = ("from polychase_amd import hip\n"
+            "before = hip.live_resources()\n"
+            "try:\n"
+            "    hip.Context(0)\n"
+            "    raised = False\n"
+            "except hip.PolychaseHipError:\n"
+            "    raised = True\n"
+            "print(before, raised, hip.live_resources())\n")
+    r = subprocess.run([sys.executable, "-c", code], cwd=ROOT, text=True, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert r.stdout.strip() == "(0, 0, 0, 0) True (0, 0, 0, 0)", r.stdout
+
+
 def test_default_options_match_reference():
     g = hip.gftt_options()
     assert (g.quality_level, g.min_distance, g.block_size, g.gradient_size, g.max_corners, g.use_harris,
