@@ -197,6 +197,14 @@ int pc_debug_lk_profile(pc_context* ctx, unsigned long long* out /* [PC_LK_PROFI
  * [1] evaluated in the x86 order, [2] (keypoint, level)s, [3] of those with the structure tensor in the x86 order.
  * enable != 0 (re)starts counting from zero, 0 stops it.  Counting costs a few atomics per wavefront. */
 int pc_debug_lk_x86_stats(pc_context* ctx, int enable, unsigned long long* out /* [4] */);
+/* Diagnostics of the detection: how the detections of this context ended, counted on the host where a detection's counters
+ * arrive (stage calls and analyzers alike) -- [0] detections finished, [1] of those on the fast path, then the detections
+ * redone on the slow path, one counter per reason (a detection can have several): [2] more candidates than the candidate
+ * buffers hold, [3] the keypoint count at the frame's keypoint capacity, [4] overflow bit 1 (a value bucket of the sort beyond
+ * its slots), [5] overflow bit 2, [6] overflow bit 4 (more candidates than the launches covered), [7] POLYCHASE_GFTT_SLOW_PATH.
+ * out (may be null) receives the counters; reset != 0 zeroes them afterwards.  No device work. */
+#define PC_DETECT_PATH_SLOTS 8
+int pc_debug_detection_paths(pc_context* ctx, int reset, unsigned long long* out /* [PC_DETECT_PATH_SLOTS] */);
 /* Diagnostics of the device-resident PnP solver: ONE damped 9x9 system through the in-kernel float32 Cholesky
  * factorisation and solve that pc_pnp_solve uses (row-major a81, only the lower triangle is read; l81 receives the
  * factor, x9 the solution of L L^T x = b; *positive_definite = 0 and x9 = 0 when the factorisation fails).  Exists so

@@ -320,6 +320,9 @@ static int detect_slow_path(pc_context* ctx, pc_frame* f, const pc::GfttGrid& gr
     const int w = f->w, h = f->h;
     const uint32_t npx = (uint32_t)((size_t)w * h);
     PC_HIP(hipStreamSynchronize(ctx->work));
+    // The context caches ONE suppression table.  An analyzer's detection is redone long after it was enqueued; a stage-level
+    // detection with another min_distance in between has replaced the table (tests/test_gftt_edges_product_gpu.py).
+    if (int urc = upload_suppression_offsets(ctx, opt)) return urc;
     PC_HIP(d.keys.ensure(npx));
     PC_HIP(d.keys_sorted.ensure(npx));
     PC_HIP(d.per_block.ensure((size_t)pc::suppress_num_blocks(npx) + 1));
@@ -371,10 +374,16 @@ int detect_finish(pc_context* ctx, pc_frame* f, const pc::GfttGrid& grid, const 
     const bool too_many_keypoints = hc[kCntKps] >= (uint32_t)f->kp_cap && !(opt.max_corners > 0 && opt.max_corners <= f->kp_cap);
     static const bool force_slow = getenv("POLYCHASE_GFTT_SLOW_PATH") != nullptr;   // tests: the slow path must give the same keypoints
     ctx->cand_hint = std::max<uint32_t>(4096u, hc[kCntCand] + hc[kCntCand] / 4);
+    // pc_debug_detection_paths: how this detection ended
+    const bool reasons[6] = {too_many_candidates, too_many_keypoints, (hc[kCntOverflow] & 1u) != 0, (hc[kCntOverflow] & 2u) != 0,
+                             (hc[kCntOverflow] & 4u) != 0, force_slow};
+    ctx->detect_paths[0]++;
+    for (int k = 0; k < 6; k++) ctx->detect_paths[2 + k] += reasons[k] ? 1u : 0u;
     if (too_many_candidates || too_many_keypoints || hc[kCntOverflow] != 0 || force_slow) {
         if (redone) *redone = true;
         return detect_slow_path(ctx, f, grid, opt, d, hist);
     }
+    ctx->detect_paths[1]++;
     if (hc[kCntStuck] != 0) return fail(PC_E_HIP, "suppression kernel did not converge (%u lanes gave up)", hc[kCntStuck]);
     f->n_cands = (int)hc[kCntCand];
     f->n_kps = (int)hc[kCntKps];
@@ -771,6 +780,15 @@ int pc_debug_lk_x86_stats(pc_context* c, int enable, unsigned long long* out) {
         PC_HIP(hipDeviceSynchronize());   // the fill is asynchronous and the LK launches run on non-blocking streams
     } else {
         c->lk_x86_stats.release();
+    }
+    return PC_OK;
+}
+
+int pc_debug_detection_paths(pc_context* c, int reset, unsigned long long* out) {
+    if (!c) return fail(PC_E_INVALID, "null context");
+    for (int k = 0; k < PC_DETECT_PATH_SLOTS; k++) {
+        if (out) out[k] = c->detect_paths[k];
+        if (reset) c->detect_paths[k] = 0;
     }
     return PC_OK;
 }

@@ -296,6 +296,7 @@ struct pc_context {
     DevBuf<int> sup_rows;                  // the same as half-widths per row, [2 * sup_R + 1]
     int sup_R = 0;
     double sup_min_distance = -1.0;
+    unsigned long long detect_paths[PC_DETECT_PATH_SLOTS] = {0};   // pc_debug_detection_paths; written by detect_finish only
     int n_sup_offsets = 0;
     // candidates of the latest finished detection + 25 %: the detections enqueued next size their launches for that many
     // (the count itself stays on the device; a frame with more is redone with launches for the full capacity)

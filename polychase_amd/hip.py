@@ -27,7 +27,7 @@ SYMBOLS = [
     "pc_gray_default_conversion", "pc_context_set_gray_conversion", "pc_context_get_gray_conversion", "pc_float_transfer_table",
     "pc_gray_quantize_weights", "pc_float_transfer_index",
     "pc_context_enable_timing", "pc_context_get_timing", "pc_context_get_busy_time", "pc_context_reset_timing",
-    "pc_debug_lk_profile", "pc_debug_lk_x86_stats", "pc_debug_llt9", "pc_debug_lm_decide",
+    "pc_debug_lk_profile", "pc_debug_lk_x86_stats", "pc_debug_detection_paths", "pc_debug_llt9", "pc_debug_lm_decide",
     "pc_debug_live_resources",
     "pc_frame_create", "pc_frame_destroy", "pc_frame_set_rgb", "pc_frame_set_rgb_f32", "pc_frame_set_gray",
     "pc_host_buffer_alloc", "pc_host_buffer_free",
@@ -63,6 +63,10 @@ SYMBOLS = [
 
 ARITH_CANONICAL, ARITH_LK_X86_ORDER, ARITH_SOBEL_FMA, ARITH_OPENCV_X86 = 0, 1, 2, 3
 ARITH_SOBEL_ROW_FMA = 4   # on top of the others (include/polychase_hip.h: PC_ARITH_SOBEL_ROW_FMA)
+# pc_debug_detection_paths (PC_DETECT_PATH_SLOTS counters, in this order)
+DETECT_PATH_NAMES = ("finished", "fast_path", "redo_candidates", "redo_keypoints", "redo_overflow_1", "redo_overflow_2",
+                     "redo_overflow_4", "redo_forced")
+DETECT_PATH_SLOTS = len(DETECT_PATH_NAMES)
 
 
 class GfttOptions(C.Structure):
@@ -174,6 +178,7 @@ def load():
     L.pc_context_reset_timing.argtypes = [vp]
     L.pc_debug_lk_profile.argtypes = [vp, C.POINTER(C.c_ulonglong)]
     L.pc_debug_lk_x86_stats.argtypes = [vp, C.c_int, C.POINTER(C.c_ulonglong)]
+    L.pc_debug_detection_paths.argtypes = [vp, C.c_int, C.POINTER(C.c_ulonglong)]
     L.pc_debug_llt9.argtypes = [vp, vp, vp, vp, vp, ip]
     L.pc_debug_lm_decide.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
     L.pc_debug_live_resources.argtypes = [C.POINTER(C.c_int * 4)]
@@ -411,6 +416,13 @@ class Context:
         _check(load().pc_debug_lk_x86_stats(self._h, 1 if enable else 0, out))
         return {"iterations_proven_exact": out[0], "iterations_x86_order": out[1], "keypoint_levels": out[2],
                 "keypoint_levels_x86_order": out[3]}
+
+    def detection_paths(self, reset: bool = False) -> dict:
+        """how the detections of this context ended since the last reset (include/polychase_hip.h:
+        pc_debug_detection_paths): finished, on the fast path, and redone on the slow path per reason"""
+        out = (C.c_ulonglong * DETECT_PATH_SLOTS)()
+        _check(load().pc_debug_detection_paths(self._h, 1 if reset else 0, out))
+        return dict(zip(DETECT_PATH_NAMES, (int(v) for v in out)))
 
     def llt9(self, a: np.ndarray, b: np.ndarray):
         """the device solver's 9x9 float32 Cholesky + solve -> (L, x, positive_definite)"""
