@@ -49,7 +49,7 @@ def hip_library_path() -> str:
 def build_hip(force: bool = False) -> str:
     os.makedirs(OBJ_DIR, exist_ok=True)
     headers = [os.path.join(HIP_DIR, h) for h in os.listdir(HIP_DIR) if h.endswith(".hpp")]
-    headers.append(os.path.join(ROOT, "include", "polychase_hip.h"))
+    headers += [os.path.join(ROOT, "include", h) for h in os.listdir(os.path.join(ROOT, "include"))]
     out = os.path.join(LIB_DIR, "libpolychase_hip.so")
     srcs = [os.path.join(HIP_DIR, s) for s in HIP_SOURCES]
     if not force and _newer(out, srcs + headers):
@@ -89,7 +89,7 @@ def build_core(force: bool = False) -> str:
     srcs = sorted([os.path.join(HOST_DIR, f) for f in os.listdir(HOST_DIR) if f.endswith(".cc")] +
                   [os.path.join(PYBIND_DIR, f) for f in os.listdir(PYBIND_DIR) if f.endswith(".cc")])
     headers = [os.path.join(d, f) for d in (HOST_DIR, PYBIND_DIR) for f in os.listdir(d) if f.endswith(".h")]
-    headers.append(os.path.join(ROOT, "include", "polychase_hip.h"))
+    headers += [os.path.join(ROOT, "include", h) for h in os.listdir(os.path.join(ROOT, "include"))]
     out = core_module_path()
     if not force and _newer(out, srcs + headers + [hip_library_path()]):
         return out

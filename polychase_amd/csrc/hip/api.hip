@@ -395,7 +395,7 @@ int detect_finish(pc_context* ctx, pc_frame* f, const pc::GfttGrid& grid, const 
 // order `stream` after it.
 int join_prep(pc_context* ctx) {
     if (!ctx->prep_dirty) return PC_OK;
-    for (hipStream_t s : {ctx->prep_stream.s, ctx->stream_b.s}) {
+    for (hipStream_t s : {ctx->prep_stream.s, ctx->lanes[1].stream}) {
         if (!s) continue;
         PC_HIP(hipEventRecord(ctx->prep_fence, s));
         PC_HIP(hipStreamWaitEvent(ctx->stream, ctx->prep_fence, 0));
@@ -506,9 +506,10 @@ int pc_context_create(int device_index, pc_context** out) {
     if (!c) return fail(PC_E_INVALID, "out of host memory");
     c->device = device_index;
     PC_HIP(c->stream.create(hipStreamNonBlocking));
+    c->lanes[0].stream = c->stream;
     {
         const char* g = getenv("POLYCHASE_LK_GATE");
-        c->lk_gate_on = !(g && atoi(g) == 0);
+        c->gate.on = !(g && atoi(g) == 0);
         // Under rocprofv3 the hand-over of dispatches is serialised: the gate's polling wavefront then sits in front of the
         // launch it waits for until its 50-ms bail-out (seen in round 2).  A profiled process runs without the gate unless it
         // is asked for explicitly (POLYCHASE_LK_GATE=1).
@@ -516,12 +517,13 @@ int pc_context_create(int device_index, pc_context** out) {
             extern char** environ;
             for (char** e2 = environ; e2 && *e2; ++e2)
                 if (strncmp(*e2, "ROCPROFILER_", 12) == 0 || strncmp(*e2, "ROCPROF_", 8) == 0 || strncmp(*e2, "ROCP_TOOL_LIB", 13) == 0) {
-                    c->lk_gate_on = false;
+                    c->gate.on = false;
                     break;
                 }
         }
     }
     PC_HIP(c->stream_b.create(hipStreamNonBlocking));
+    c->lanes[1].stream = c->stream_b;
     PC_HIP(c->prep_stream.create(hipStreamNonBlocking));
     PC_HIP(c->prep_fence.create(hipEventDisableTiming));
     c->work = c->stream;

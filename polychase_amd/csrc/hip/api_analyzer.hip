@@ -35,9 +35,17 @@ struct Job {
     int n_targets = 0;
     int32_t targets[PC_MAX_TARGETS];
     Event done;               // records of this job are in pinned memory (the job's lane)
-    PinBuf<uint8_t> h_pack;   // the job's records, same layout as pc_context::lk_pack
-    size_t o_kps = 0, o_idx = 0, o_xy = 0, o_err = 0, pack_bytes = 0;
-    bool host_records = true;       // the whole pack was downloaded (else its 128-byte header only)
+    PinBuf<uint8_t> h_pack;   // the job's records, a copy of its lane's pack
+    pc::RecordLayout layout;  // ... of both
+    bool host_records = true;       // the whole pack was downloaded (else its row offsets only)
+};
+
+// the resident slots a job reads
+struct JobSlots {
+    Slot* frame1 = nullptr;
+    int n_targets = 0;
+    Slot* target[PC_MAX_TARGETS];
+    const pc_frame* target_frame[PC_MAX_TARGETS];   // the same as run_lk_job takes them
 };
 
 // Issue priority of the helper kernels this analyzer enqueues (common.hpp: helper_priority), from what it observes.
@@ -92,14 +100,25 @@ struct pc_analyzer {
     std::vector<Slot> slots;
     std::vector<Job> jobs;
     size_t job_head = 0, job_count = 0;  // ring of in-flight jobs
-    uint64_t submitted = 0;              // jobs submitted so far: job k runs on lane k & 1 (stream, LK output set, pack)
-    bool one_lane = false;               // POLYCHASE_LK_LANES=1 when the analyzer was created: every job on lane 0
+    uint64_t submitted = 0;              // jobs submitted so far
+    // POLYCHASE_LK_LANES=1 when the analyzer was created: every job on lane 0, i.e. no two LK launches in flight -- a launch's
+    // start-to-end time is then its own duration (the recipe of tools/collect_profiles.sh under rocprofv3 and of bench.py's
+    // roofline time base); the product runs two lanes
+    bool one_lane = false;
     // "the LK launch of a job finished", per lane, handed out round-robin.  Slots remember the event of the last job
     // that read them; an event that has been re-recorded since marks a LATER launch of the same lane, which the
     // lane's stream order puts behind the remembered one -- waiting for it is still correct.
     static constexpr int kLaneEvents = 16;
     Event lk_done[2][kLaneEvents];
-    bool gate_armed = false;             // a gated launch is ahead: the next one waits for its "all dispatched" signal
+    // The lane (index into pc_context::lanes, Slot::last_read and lk_done) of the job submitted next -- job k runs on lane
+    // k & 1 -- and, in *done, the lane's lk_done event that is this job's turn
+    int next_lane(hipEvent_t* done) const {
+        const int lane = one_lane ? 0 : (int)(submitted & 1);
+        *done = lk_done[lane][(one_lane ? submitted : submitted >> 1) % kLaneEvents];
+        return lane;
+    }
+    // a gated launch of THIS analyzer is ahead: the next one waits for its "all dispatched" signal (the context's LkGate)
+    bool gate_armed = false;
     HelperPriorityControl prio;
     int32_t put_newest = 0, put_previous = 0;   // frame ids of the two most recent put_frame calls
     int puts = 0;
@@ -197,9 +216,6 @@ int pc_analyzer_create(pc_context* ctx, int width, int height, const pc_gftt_opt
     std::unique_ptr<pc_analyzer, void (*)(pc_analyzer*)> a(new (std::nothrow) pc_analyzer(), pc_analyzer_destroy);
     if (!a) return fail(PC_E_INVALID, "out of host memory");
     a->ctx = ctx;
-    // POLYCHASE_LK_LANES=1 (read per analyzer): every job on lane 0, i.e. no two LK launches in flight -- a launch's
-    // start-to-end time is then its own duration (the recipe of tools/collect_profiles.sh under rocprofv3 and of bench.py's
-    // roofline time base); the product runs two lanes
     a->one_lane = getenv("POLYCHASE_LK_LANES") && atoi(getenv("POLYCHASE_LK_LANES")) == 1;
     a->w = width;
     a->h = height;
@@ -234,14 +250,13 @@ int pc_analyzer_create(pc_context* ctx, int width, int height, const pc_gftt_opt
         // frames).  A burst of overlapping downloads makes it create them now.
         const size_t chunk = (size_t)4 << 20, burst = 12;
         Job& j0 = a->jobs[0];
-        PC_HIP(ctx->lk_pack[0].ensure(chunk));
-        PC_HIP(ctx->lk_pack[1].ensure(chunk));
+        for (LkLane& lane : ctx->lanes) PC_HIP(lane.pack.ensure(chunk));
         PC_HIP(j0.h_pack.ensure(chunk * burst));
-        hipStream_t streams[3] = {ctx->stream_b, ctx->prep_stream, ctx->stream};
+        hipStream_t streams[3] = {ctx->lanes[1].stream, ctx->prep_stream, ctx->lanes[0].stream};
         for (int round = 0; round < 3; round++) {
             hipError_t e = hipSuccess;
             for (size_t k = 0; k < burst; k++) {
-                const hipError_t ek = hipMemcpyAsync(j0.h_pack.p + k * chunk, ctx->lk_pack[k & 1].p, chunk, hipMemcpyDeviceToHost, streams[k % 3]);
+                const hipError_t ek = hipMemcpyAsync(j0.h_pack.p + k * chunk, ctx->lanes[k & 1].pack.p, chunk, hipMemcpyDeviceToHost, streams[k % 3]);
                 if (e == hipSuccess) e = ek;
             }
             for (hipStream_t st : streams) (void)hipStreamSynchronize(st);
@@ -412,157 +427,170 @@ int pc_analyzer_set_keypoints(pc_analyzer* a, int32_t frame_id, const float* xy,
     return PC_OK;
 }
 
+// ---- pc_analyzer_submit in its steps, in the one order they have: each is named for what it checks or enqueues ----
 
-int pc_analyzer_submit(pc_analyzer* a, int32_t frame1, const int32_t* targets, int n_targets) {
+static int submit_check(const pc_analyzer* a, const int32_t* targets, int n_targets) {
     if (!a || (n_targets > 0 && !targets)) return fail(PC_E_INVALID, "null argument");
     if (n_targets < 0 || n_targets > PC_MAX_TARGETS) return fail(PC_E_INVALID, "n_targets must be in [0,%d]", PC_MAX_TARGETS);
     if (a->job_count == a->jobs.size()) return fail(PC_E_STATE, "%zu jobs already in flight: call pc_analyzer_collect", a->job_count);
     if (int arc = check_affine(a->affine, a->normalize)) return arc;   // normalize may have been switched on after the refinement
     if (int src = check_search_radius(a->search_radius, a->normalize)) return src;   // ... or after the search
-    if (int wrc = check_mask_windows(a->mask_windows, a->normalize, a->affine, a->search_radius, a->min_correlation)) return wrc;
+    return check_mask_windows(a->mask_windows, a->normalize, a->affine, a->search_radius, a->min_correlation);
+}
+
+static int resolve_slots(pc_analyzer* a, int32_t frame1, const int32_t* targets, int n_targets, JobSlots* s) {
+    if (!(s->frame1 = find_slot(a, frame1))) return fail(PC_E_STATE, "frame1 %d is not resident", frame1);
+    s->n_targets = n_targets;
+    for (int t = 0; t < n_targets; t++) {
+        if (!(s->target[t] = find_slot(a, targets[t]))) return fail(PC_E_STATE, "target frame %d is not resident", targets[t]);
+        s->target_frame[t] = s->target[t]->frame;
+    }
+    return PC_OK;
+}
+
+// keypoints of frame1: the dense phase ran when the frame became resident; order them now.  *detected: by this run, not supplied
+static int finish_frame1_keypoints(pc_analyzer* a, Slot& s1, bool* detected) {
+    *detected = !s1.supplied;
+    if (s1.det == DET_DONE) return PC_OK;
+    SlowSection ss("submit/detect_finish");
+    *detected = true;
+    return detect_finish_slot(a, s1);
+}
+
+// the lane's LK launch needs this frame's keypoints and the pyramids of the frames it reads -- not the detection of frames that
+// were made resident for later
+static int enqueue_lane_waits(hipStream_t ls, const JobSlots& s) {
+    SlowSection ss("submit/waits");
+    PC_HIP(hipStreamWaitEvent(ls, s.frame1->kps_ready, 0));
+    PC_HIP(hipStreamWaitEvent(ls, s.frame1->img_ready, 0));
+    for (int t = 0; t < s.n_targets; t++) PC_HIP(hipStreamWaitEvent(ls, s.target[t]->img_ready, 0));
+    return PC_OK;
+}
+
+// refused before anything of the job is enqueued: more keypoints than the compaction handles, and a record that does not fit the
+// device log (the caller may redirect the log and submit again)
+static int refuse_job(const pc_analyzer* a, int n, const pc::RecordLayout& layout) {
+    if (n > pc::kCompactMaxKeypoints) return fail(PC_E_CAPACITY, "%d keypoints: more than the compaction handles (%d)", n, pc::kCompactMaxKeypoints);
+    const size_t end = a->log_used + pc::RecordLayout::kLogHeaderBytes + layout.bytes;
+    if (a->d_log && end > a->log_cap) return fail(PC_E_CAPACITY, "device log full (%zu of %zu bytes)", end, a->log_cap);
+    return PC_OK;
+}
+
+static int reserve_pack(Job& j, LkLane& lane) {
+    SlowSection ss("submit/ensure pack");
+    PC_HIP(j.h_pack.ensure(j.layout.bytes));
+    PC_HIP(lane.pack.ensure(j.layout.bytes));
+    return PC_OK;
+}
+
+// the gate between the lanes, then the job's launches, which follow each other on the lane; the gate is the forward launch's
+// alone, and the compaction filters on the status the last pass leaves
+static int enqueue_lk(pc_analyzer* a, LkLane& lane, const JobSlots& s) {
+    pc_context* ctx = a->ctx;
+    const pc_frame* const f1 = s.frame1->frame;
+    if (a->fopt.window_size != f1->win) return fail(PC_E_INVALID, "window size mismatch");
+    SlowSection ss("submit/run_lk");
+    uint32_t gate_value = 0;
+    if (ctx->gate.on && f1->n_kps > 0) {
+        // two job lanes: this launch starts when the one before it (other lane) has handed out its last workgroup --
+        // it fills that launch's tail and does not compete with its body
+        if (int rc = ctx->gate.wait_and_next(lane.stream, a->gate_armed, &gate_value)) return rc;
+        a->gate_armed = true;
+    }
+    LkPasses passes{.search_radius = a->search_radius, .affine = a->affine, .normalize = a->normalize,
+                    .min_correlation = a->min_correlation, .fb_threshold = a->fb_threshold, .mask_windows = a->mask_windows};
+    for (int t = 0; t < s.n_targets; t++) {
+        const pc_frame* const tg = s.target_frame[t];
+        if (tg->target_margin >= 0) passes.plane[t] = tg->target_margin > 0 ? tg->d_choked.p : tg->d_mask.p;
+        if (a->mask_windows) passes.weights_tgt[t] = tg->window_weights;
+    }
+    if (a->mask_windows) passes.weights_f1 = f1->window_weights;
+    return run_lk_job(ctx, lane, f1, s.target_frame, s.n_targets, &a->fopt, passes, gate_value);
+}
+
+// compaction (status filter) into the lane's pack, frame1's keypoints beside it, and `lk_done`
+static int enqueue_records(pc_analyzer* a, LkLane& lane, const JobSlots& s, const Job& j, int lane_i, hipEvent_t lk_done) {
+    hipStream_t const ls = lane.stream;
+    uint8_t* const pack = lane.pack.p;
+    PC_HIP(hipMemsetAsync(pack, 0, pc::RecordLayout::kRowOffsetBytes, ls));
+    if (j.n_targets > 0)
+        if (int rc = compact_lane(a->ctx, lane, j.n_kps, j.n_targets, reinterpret_cast<long long*>(pack), reinterpret_cast<uint32_t*>(pack + j.layout.o_idx),
+                                  reinterpret_cast<float2*>(pack + j.layout.o_xy), reinterpret_cast<float*>(pack + j.layout.o_err)))
+            return rc;
+    pc::launch_copy_keypoints(s.frame1->frame->d_kps.p, reinterpret_cast<float2*>(pack + j.layout.o_kps), j.n_kps, ls);
+    // Everything that reads the resident frames is enqueued: the pyramids (LK), frame1's keypoints (LK, the copy
+    // above) and its inverse visiting order (compaction).  A slot may be overwritten once this event has fired.
+    PC_HIP(hipEventRecord(lk_done, ls));
+    s.frame1->last_read[lane_i] = lk_done;
+    for (int t = 0; t < s.n_targets; t++) s.target[t]->last_read[lane_i] = lk_done;
+    return PC_OK;
+}
+
+// device log: header from pinned memory (that of the job's slot in the ring), the record itself is the pack (one device-to-device
+// copy); refuse_job has seen that it fits
+static int enqueue_log_append(pc_analyzer* a, LkLane& lane, const Job& j, size_t slot_i) {
+    constexpr size_t kHeader = pc::RecordLayout::kLogHeaderBytes;
+    if (a->log_hdr.size() != a->jobs.size()) a->log_hdr.resize(a->jobs.size());
+    PC_HIP(a->log_hdr[slot_i].ensure(kHeader / sizeof(long long)));
+    long long* hh = a->log_hdr[slot_i].p;
+    std::memset(hh, 0, kHeader);
+    hh[0] = PC_LOG_MAGIC;
+    hh[1] = j.frame1;
+    hh[2] = j.n_kps;
+    hh[3] = j.n_targets;
+    for (int t = 0; t < j.n_targets; t++) hh[4 + t] = j.targets[t];
+    hh[12] = (long long)j.n_kps * j.n_targets;
+    PC_HIP(hipMemcpyAsync(a->d_log + a->log_used, hh, kHeader, hipMemcpyHostToDevice, lane.stream));
+    PC_HIP(hipMemcpyAsync(a->d_log + a->log_used + kHeader, lane.pack.p, j.layout.bytes, hipMemcpyDeviceToDevice, lane.stream));
+    a->log_used += kHeader + j.layout.bytes;
+    return PC_OK;
+}
+
+// download: ONE copy with fixed endpoints (the lane's pack -> the job's pinned pack).  The runtime stalls the host for 5-8 ms the
+// first time it sees a buffer as a copy source, so per-frame buffers must not appear here.  Then the job's `done`
+static int enqueue_download(const pc_analyzer* a, LkLane& lane, Job& j) {
+    j.host_records = a->host_records;   // else the row offsets only
+    const size_t bytes = j.host_records ? j.layout.bytes : pc::RecordLayout::kRowOffsetBytes;
+    PC_HIP(hipMemcpyAsync(j.h_pack.p, lane.pack.p, bytes, hipMemcpyDeviceToHost, lane.stream));
+    PC_HIP(hipEventRecord(j.done, lane.stream));
+    return PC_OK;
+}
+
+int pc_analyzer_submit(pc_analyzer* a, int32_t frame1, const int32_t* targets, int n_targets) {
+    int rc = submit_check(a, targets, n_targets);
+    if (rc != PC_OK) return rc;
     pc_context* ctx = a->ctx;
     PC_HIP(hipSetDevice(ctx->device));
     HelperPriorityScope prio_scope(a->prio.hi);
-    Slot* s1 = find_slot(a, frame1);
-    if (!s1) return fail(PC_E_STATE, "frame1 %d is not resident", frame1);
-    const pc_frame* tg[PC_MAX_TARGETS];
-    for (int t = 0; t < n_targets; t++) {
-        Slot* st = find_slot(a, targets[t]);
-        if (!st) return fail(PC_E_STATE, "target frame %d is not resident", targets[t]);
-        tg[t] = st->frame;
-    }
-    int rc;
-    // (1) keypoints of frame1: the dense phase ran when the frame became resident; order them now
+    JobSlots s;
+    if ((rc = resolve_slots(a, frame1, targets, n_targets, &s)) != PC_OK) return rc;
     bool detected = false;
-    if (s1->det != DET_DONE) {
-        SlowSection ss("submit/detect_finish");
-        if ((rc = detect_finish_slot(a, *s1)) != PC_OK) return rc;
-        detected = true;
-    } else {
-        detected = !s1->supplied;
-    }
-    Job& j = a->jobs[(a->job_head + a->job_count) % a->jobs.size()];
-    // (2) the job's lane; its LK launch needs this frame's keypoints and the pyramids of the frames it reads -- not the
-    // detection of frames that were made resident for later
-    // POLYCHASE_LK_LANES=1: every job on lane 0, i.e. no two LK launches in flight -- the recipe for per-dispatch durations under
-    // rocprofv3 (tools/collect_profiles.sh); the product runs two lanes
-    const int lane = a->one_lane ? 0 : (int)(a->submitted & 1);
-    hipStream_t const ls = ctx->lane_stream(lane);
-    {
-        SlowSection ss("submit/waits");
-        PC_HIP(hipStreamWaitEvent(ls, s1->kps_ready, 0));
-        PC_HIP(hipStreamWaitEvent(ls, s1->img_ready, 0));
-        for (int t = 0; t < n_targets; t++) PC_HIP(hipStreamWaitEvent(ls, find_slot(a, targets[t])->img_ready, 0));
-    }
-    const int n = s1->frame->n_kps;
-    if (n > pc::kCompactMaxKeypoints)   // before anything of the job is enqueued
-        return fail(PC_E_CAPACITY, "%d keypoints: more than the compaction handles (%d)", n, pc::kCompactMaxKeypoints);
-    const size_t rows = (size_t)n * (size_t)std::max(n_targets, 0);
-    // packed record layout (= a device-log record without its 128-byte header)
-    auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
-    j.o_kps = 128;
-    j.o_idx = up16(j.o_kps + (size_t)n * 8);
-    j.o_xy = up16(j.o_idx + rows * 4);
-    j.o_err = up16(j.o_xy + rows * 8);
-    j.pack_bytes = up16(j.o_err + rows * 4);
-    // a record that does not fit the device log is refused before anything of the job is enqueued (the caller may
-    // redirect the log and submit again)
-    if (a->d_log && a->log_used + 128 + j.pack_bytes > a->log_cap)
-        return fail(PC_E_CAPACITY, "device log full (%zu of %zu bytes)", a->log_used + 128 + j.pack_bytes, a->log_cap);
-    {
-        SlowSection ss("submit/ensure pack");
-        PC_HIP(j.h_pack.ensure(j.pack_bytes));
-        PC_HIP(ctx->lk_pack[lane].ensure(j.pack_bytes));
-    }
+    if ((rc = finish_frame1_keypoints(a, *s.frame1, &detected)) != PC_OK) return rc;
+    const size_t slot_i = (a->job_head + a->job_count) % a->jobs.size();
+    Job& j = a->jobs[slot_i];
+    hipEvent_t lk_done = nullptr;
+    const int lane_i = a->next_lane(&lk_done);
+    LkLane& lane = ctx->lanes[lane_i];
+    if ((rc = enqueue_lane_waits(lane.stream, s)) != PC_OK) return rc;
+    const int n = s.frame1->frame->n_kps;
+    const pc::RecordLayout layout((size_t)n, (size_t)n * (size_t)n_targets);
+    if ((rc = refuse_job(a, n, layout)) != PC_OK) return rc;
+    j.layout = layout;
+    if ((rc = reserve_pack(j, lane)) != PC_OK) return rc;
     j.frame1 = frame1;
     j.n_kps = n;
     j.detected = detected;
     j.n_targets = n_targets;
     for (int t = 0; t < n_targets; t++) j.targets[t] = targets[t];
-    // (3) everything of this job goes onto its lane, in order: LK into the lane's output set, compaction (status
-    // filter) into the lane's pack, device-log append, download.  The other lane holds the neighbouring jobs, so the
-    // next LK launch does not wait for any of it.
+    // Everything of this job goes onto its lane, in order: LK into the lane's records, compaction into the lane's pack,
+    // device-log append, download.  The other lane holds the neighbouring jobs, so the next LK launch does not wait for any of it.
     ctx->prep_dirty = true;   // stage-level calls must order themselves behind the side streams
-    if (n_targets > 0) {
-        if (a->fopt.window_size != s1->frame->win) return fail(PC_E_INVALID, "window size mismatch");
-        SlowSection ss("submit/run_lk");
-        if (ctx->lk_gate_on && n > 0) {
-            // two job lanes: this launch starts when the one before it (other lane) has handed out its last workgroup --
-            // it fills that launch's tail and does not compete with its body
-            if (!ctx->lk_gate.p) {
-                PC_HIP(ctx->lk_gate.ensure(16));
-                PC_HIP(hipMemset(ctx->lk_gate.p, 0, 16 * sizeof(uint32_t)));
-                PC_HIP(ctx->lk_gate_timed_out.ensure(1));
-                ctx->lk_gate_timed_out.p[0] = 0u;
-            }
-            if (*static_cast<volatile uint32_t*>(ctx->lk_gate_timed_out.p) != 0u) {
-                // a gate kernel waited in vain: the lanes' streams share a hardware queue, the launch it waited for was
-                // queued BEHIND it.  No more gates in this context.
-                ctx->lk_gate_on = false;
-                if (pc::trace_allocations()) fprintf(stderr, "[polychase_hip] LK gate timed out (streams share a hardware queue): gate switched off\n");
-            }
-            if (a->gate_armed && ctx->lk_gate_on) pc::launch_lk_gate(ctx->lk_gate.p, ctx->lk_gate_seq, ctx->lk_gate_timed_out.p, ls);
-            ctx->lk_gate_next = ++ctx->lk_gate_seq;
-            if (ctx->lk_gate_next == 0) ctx->lk_gate_next = ++ctx->lk_gate_seq;
-            a->gate_armed = true;
-        }
-        // the launches follow each other on the lane; the gate is the forward launch's alone, and the compaction below filters
-        // on the status the last pass leaves
-        LkPasses passes{.search_radius = a->search_radius, .affine = a->affine, .normalize = a->normalize,
-                        .min_correlation = a->min_correlation, .fb_threshold = a->fb_threshold, .mask_windows = a->mask_windows};
-        for (int t = 0; t < n_targets; t++)
-            if (tg[t]->target_margin >= 0) passes.plane[t] = tg[t]->target_margin > 0 ? tg[t]->d_choked.p : tg[t]->d_mask.p;
-        if (a->mask_windows) {
-            passes.weights_f1 = s1->frame->window_weights;
-            for (int t = 0; t < n_targets; t++) passes.weights_tgt[t] = tg[t]->window_weights;
-        }
-        if ((rc = run_lk_job(ctx, s1->frame, tg, n_targets, &a->fopt, passes, lane)) != PC_OK) return rc;
-    }
+    if (n_targets > 0 && (rc = enqueue_lk(a, lane, s)) != PC_OK) return rc;
     SlowSection ss_post("submit/post enqueue");
-    uint8_t* const pack = ctx->lk_pack[lane].p;
-    long long* const p_ro = reinterpret_cast<long long*>(pack);
-    PC_HIP(hipMemsetAsync(pack, 0, 128, ls));
-    if (n_targets > 0) {
-        const size_t scratch_cap_before = ctx->lk_block_counts[lane].cap;   // a reallocation changes the capacity (the address may repeat)
-        PC_HIP(ctx->lk_block_counts[lane].ensure(pc::compact_scratch_words(n, n_targets)));
-        ScopedTimer t(ctx, PC_K_COMPACT, ls);
-        pc::launch_compact(ctx->lk_rec[lane].p, ctx->lk_slot_of[lane], n, n_targets, ctx->lk_block_counts[lane].p,
-                           ctx->lk_block_counts[lane].cap != scratch_cap_before, p_ro, reinterpret_cast<uint32_t*>(pack + j.o_idx),
-                           reinterpret_cast<float2*>(pack + j.o_xy), reinterpret_cast<float*>(pack + j.o_err), ls);
-    }
-    pc::launch_copy_keypoints(s1->frame->d_kps.p, reinterpret_cast<float2*>(pack + j.o_kps), n, ls);
-    // Everything that reads the resident frames is enqueued: the pyramids (LK), frame1's keypoints (LK, the copy
-    // above) and its inverse visiting order (compaction).  A slot may be overwritten once this event has fired.
-    hipEvent_t const lk_done = a->lk_done[lane][(a->one_lane ? a->submitted : (a->submitted >> 1)) % pc_analyzer::kLaneEvents];
-    PC_HIP(hipEventRecord(lk_done, ls));
-    s1->last_read[lane] = lk_done;
-    for (int t = 0; t < n_targets; t++) find_slot(a, targets[t])->last_read[lane] = lk_done;
-    if (a->d_log) {
-        // device log: header from pinned memory, the record itself is the pack (one device-to-device copy)
-        const size_t o_hdr = a->log_used, end = o_hdr + 128 + j.pack_bytes;
-        if (end > a->log_cap) return fail(PC_E_CAPACITY, "device log full (%zu of %zu bytes)", end, a->log_cap);
-        const size_t slot_i = (a->job_head + a->job_count) % a->jobs.size();
-        if (a->log_hdr.size() != a->jobs.size()) a->log_hdr.resize(a->jobs.size());
-        PC_HIP(a->log_hdr[slot_i].ensure(16));
-        long long* hh = a->log_hdr[slot_i].p;
-        for (int k = 0; k < 16; k++) hh[k] = 0;
-        hh[0] = PC_LOG_MAGIC;
-        hh[1] = frame1;
-        hh[2] = n;
-        hh[3] = n_targets;
-        for (int t = 0; t < n_targets; t++) hh[4 + t] = targets[t];
-        hh[12] = (long long)rows;
-        PC_HIP(hipMemcpyAsync(a->d_log + o_hdr, hh, 128, hipMemcpyHostToDevice, ls));
-        PC_HIP(hipMemcpyAsync(a->d_log + o_hdr + 128, pack, j.pack_bytes, hipMemcpyDeviceToDevice, ls));
-        a->log_used = end;
-    }
+    if ((rc = enqueue_records(a, lane, s, j, lane_i, lk_done)) != PC_OK) return rc;
+    if (a->d_log && (rc = enqueue_log_append(a, lane, j, slot_i)) != PC_OK) return rc;
     a->submitted++;
-    // (4) download: ONE copy with fixed endpoints (the lane's pack -> the job's pinned pack).  The runtime stalls the
-    // host for 5-8 ms the first time it sees a buffer as a copy source, so per-frame buffers must not appear here.
-    if (a->host_records) PC_HIP(hipMemcpyAsync(j.h_pack.p, pack, j.pack_bytes, hipMemcpyDeviceToHost, ls));
-    else PC_HIP(hipMemcpyAsync(j.h_pack.p, pack, 128, hipMemcpyDeviceToHost, ls));   // the row offsets only
-    j.host_records = a->host_records;
-    PC_HIP(hipEventRecord(j.done, ls));
+    if ((rc = enqueue_download(a, lane, j)) != PC_OK) return rc;
     a->job_count++;
     return PC_OK;
 }
@@ -742,20 +770,20 @@ int pc_analyzer_collect(pc_analyzer* a, pc_frame_result* out) {
     }
     // let the runtime retire the finished commands of the other streams now, a few at a time: left alone it does
     // so in one batch of several milliseconds every couple of hundred frames, inside some later launch
-    (void)hipStreamQuery(a->ctx->stream);
-    if (a->ctx->stream_b) (void)hipStreamQuery(a->ctx->stream_b);
+    for (const LkLane& lane : a->ctx->lanes)
+        if (lane.stream) (void)hipStreamQuery(lane.stream);
     (void)hipStreamQuery(a->ctx->prep_stream);
     out->frame1 = j.frame1;
     out->n_keypoints = j.n_kps;
     out->keypoints_detected = j.detected ? 1 : 0;
-    out->keypoints_xy = j.host_records ? reinterpret_cast<const float*>(j.h_pack.p + j.o_kps) : nullptr;
+    out->keypoints_xy = j.host_records ? reinterpret_cast<const float*>(j.h_pack.p + j.layout.o_kps) : nullptr;
     out->n_targets = j.n_targets;
     for (int t = 0; t < PC_MAX_TARGETS; t++) out->targets[t] = t < j.n_targets ? j.targets[t] : 0;
     const long long* h_ro = reinterpret_cast<const long long*>(j.h_pack.p);
     for (int t = 0; t <= PC_MAX_TARGETS; t++) out->row_offset[t] = (int64_t)h_ro[std::min(t, j.n_targets)];
-    out->src_indices = j.host_records ? reinterpret_cast<const uint32_t*>(j.h_pack.p + j.o_idx) : nullptr;
-    out->tgt_xy = j.host_records ? reinterpret_cast<const float*>(j.h_pack.p + j.o_xy) : nullptr;
-    out->flow_err = j.host_records ? reinterpret_cast<const float*>(j.h_pack.p + j.o_err) : nullptr;
+    out->src_indices = j.host_records ? reinterpret_cast<const uint32_t*>(j.h_pack.p + j.layout.o_idx) : nullptr;
+    out->tgt_xy = j.host_records ? reinterpret_cast<const float*>(j.h_pack.p + j.layout.o_xy) : nullptr;
+    out->flow_err = j.host_records ? reinterpret_cast<const float*>(j.h_pack.p + j.layout.o_err) : nullptr;
     a->job_head = (a->job_head + 1) % a->jobs.size();
     a->job_count--;
     return PC_OK;

@@ -108,12 +108,14 @@ struct LkPasses {
     bool weights_tgt[PC_MAX_TARGETS];
     uint8_t* touched;
 };
-// Enqueues a whole job into output set `set` on job lane `set` (0: the context's main stream): the forward launch and the passes,
-// in the one order they have.  Afterwards pc_context::lk_rec / lk_slot_of of the set hold the records and the inverse visiting
-// order, and with a search radius lk_search_d / lk_search_state of the set the displacements and states.  Consumes
-// pc_context::lk_gate_next.  The arguments have passed the checks above
-int run_lk_job(pc_context* ctx, const pc_frame* frame1, const pc_frame* const* targets, int n_targets, const pc_flow_options* opt,
-               const LkPasses& passes, int set);
+// Enqueues a whole job on `lane` (one of pc_context::lanes; the stage calls: lanes[0]): the forward launch and the passes, in the
+// one order they have.  Afterwards the lane's rec / slot_of hold the records and the inverse visiting order, and with a search
+// radius its search_d / search_state the displacements and states.  gate_value: what the forward launch stores into the
+// context's gate (LkGate::wait_and_next), 0: not gated.  The arguments have passed the checks above
+int run_lk_job(pc_context* ctx, LkLane& lane, const pc_frame* frame1, const pc_frame* const* targets, int n_targets,
+               const pc_flow_options* opt, const LkPasses& passes, uint32_t gate_value = 0);
+// Compacts the records run_lk_job left on `lane` (status filter; kernels.hpp launch_compact) into the four arrays, on the lane's stream
+int compact_lane(pc_context* ctx, LkLane& lane, int n, int n_targets, long long* row_offset, uint32_t* src_indices, float2* tgt_xy, float* err);
 // target-side masks: ensure_choked_plane allocates pc_frame::d_choked (once)
 int ensure_choked_plane(pc_frame* f);
 // masked windows: the weight planes (pc_frame::wt) of the mask in the frame's plane, allocated the first time

@@ -77,23 +77,22 @@ struct LkJob {
     double eps_sq;
     float min_eig_thr;
     int x86_order;
-    const uint32_t* perm;      // visiting order (slot -> keypoint) ...
-    const uint32_t* slot_of;   // ... and its inverse, pc_context::lk_slot_of of the set
-    float4* rec;               // the records of the set, in visiting order
+    const uint32_t* perm;      // visiting order (slot -> keypoint); its inverse: LkLane::slot_of
+    float4* rec;               // the lane's records, in visiting order
     hipStream_t stream;        // the lane's
 };
 
-int lk_job_begin(pc_context* ctx, const pc_frame* frame1, const pc_frame* const* targets, int n_targets, const pc_flow_options* opt,
-                 int set, LkJob* j) {
+int lk_job_begin(pc_context* ctx, LkLane& lane, const pc_frame* frame1, const pc_frame* const* targets, int n_targets,
+                 const pc_flow_options* opt, LkJob* j) {
     j->frame1 = frame1;
     j->targets = targets;
     j->n_targets = n_targets;
-    j->stream = ctx->lane_stream(set);
+    j->stream = lane.stream;
     j->n = frame1->n_kps;
     j->win = frame1->win;
-    PC_HIP(ctx->lk_rec[set].ensure(((size_t)j->n + 1) * pc::kRecStride));
-    j->rec = ctx->lk_rec[set].p;
-    ctx->lk_slot_of[set] = j->slot_of = j->perm = nullptr;
+    PC_HIP(lane.rec.ensure(((size_t)j->n + 1) * pc::kRecStride));
+    j->rec = lane.rec.p;
+    lane.slot_of = j->perm = nullptr;
     if (j->n == 0) return PC_OK;
     j->max_level = std::min(opt->max_level, frame1->nlevels - 1);
     for (int t = 0; t < n_targets; t++) j->max_level = std::min(j->max_level, targets[t]->nlevels - 1);
@@ -113,14 +112,15 @@ int lk_job_begin(pc_context* ctx, const pc_frame* frame1, const pc_frame* const*
         pc::launch_spatial_bins(frame1->d_kps.p, j->n, nullptr, frame1->w, frame1->h, ctx->lk_hist.p, ctx->lk_perm.p, ctx->lk_perm.p + j->n, j->stream);
     }
     j->perm = frame1->perm_valid ? frame1->d_perm.p : ctx->lk_perm.p;
-    ctx->lk_slot_of[set] = j->slot_of = j->perm + cap;
+    lane.slot_of = j->perm + cap;
     return PC_OK;
 }
 
 int unsupported_window(const LkJob& j) { return fail(PC_E_INVALID, "unsupported window size %d", j.win); }
 
-// forward launch; normalize: the brightness-normalised kernel (include/polychase_hip.h: pc_lk_track_normalized)
-int lk_forward(pc_context* ctx, const LkJob& j, int normalize) {
+// forward launch; normalize: the brightness-normalised kernel (include/polychase_hip.h: pc_lk_track_normalized); gate_value: what
+// it stores into the context's gate (0: not gated)
+int lk_forward(pc_context* ctx, const LkJob& j, int normalize, uint32_t gate_value) {
     pc::LKParams p;
     std::memset(&p, 0, sizeof(p));
     for (int l = 0; l <= j.max_level; l++) {
@@ -142,9 +142,8 @@ int lk_forward(pc_context* ctx, const LkJob& j, int normalize) {
     p.prof = nullptr;
     p.x86_order = j.x86_order;
     p.x86_stats = ctx->lk_x86_stats.p;
-    p.gate = ctx->lk_gate_next ? ctx->lk_gate.p : nullptr;
-    p.gate_value = ctx->lk_gate_next;
-    ctx->lk_gate_next = 0;
+    p.gate = gate_value ? ctx->gate.word.p : nullptr;
+    p.gate_value = gate_value;
     if (pc::lk_profile_enabled()) {   // diagnostics build: 16 words per wavefront, the latest launch only
         ctx->lk_prof_rows = (size_t)j.n / 2 + 1;
         PC_HIP(ctx->lk_prof.ensure(ctx->lk_prof_rows * PC_LK_PROFILE_SLOTS));
@@ -325,13 +324,13 @@ int lk_backward(pc_context* ctx, const LkJob& j, const LkPasses& passes, const s
 
 }  // namespace
 
-int run_lk_job(pc_context* ctx, const pc_frame* frame1, const pc_frame* const* targets, int n_targets, const pc_flow_options* opt,
-               const LkPasses& passes, int set) {
+int run_lk_job(pc_context* ctx, LkLane& lane, const pc_frame* frame1, const pc_frame* const* targets, int n_targets,
+               const pc_flow_options* opt, const LkPasses& passes, uint32_t gate_value) {
     LkJob j;
-    int rc = lk_job_begin(ctx, frame1, targets, n_targets, opt, set, &j);
+    int rc = lk_job_begin(ctx, lane, frame1, targets, n_targets, opt, &j);
     if (rc != PC_OK || j.n == 0) return rc;
     const size_t rows = (size_t)j.n * n_targets;
-    if ((rc = lk_forward(ctx, j, passes.normalize)) != PC_OK) return rc;
+    if ((rc = lk_forward(ctx, j, passes.normalize, gate_value)) != PC_OK) return rc;
     // masked windows: directly after the forward launch (none of the passes it is refused with follows); frame1 without weights:
     // nothing to weight, nothing enqueued but the zeros of `touched`
     if (passes.mask_windows) {
@@ -343,10 +342,10 @@ int run_lk_job(pc_context* ctx, const pc_frame* frame1, const pc_frame* const* t
     short2* search_d = nullptr;
     uint8_t* search_state = nullptr;
     if (passes.search_radius > 0) {
-        PC_HIP(ctx->lk_search_d[set].ensure(rows));
-        PC_HIP(ctx->lk_search_state[set].ensure(rows));
-        search_d = ctx->lk_search_d[set].p;
-        search_state = ctx->lk_search_state[set].p;
+        PC_HIP(lane.search_d.ensure(rows));
+        PC_HIP(lane.search_state.ensure(rows));
+        search_d = lane.search_d.p;
+        search_state = lane.search_state.p;
         if ((rc = lk_search(ctx, j, passes.search_radius, search_d, search_state)) != PC_OK) return rc;
     }
     // affine refinement: in front of every check, so that each of them judges the refined end points
@@ -360,6 +359,15 @@ int run_lk_job(pc_context* ctx, const pc_frame* frame1, const pc_frame* const* t
     if ((passes.min_correlation > 0.0 || passes.corr) && (rc = lk_correlation(ctx, j, passes.min_correlation, passes.corr)) != PC_OK) return rc;
     // forward-backward check: last, it rewrites the status of the records the caller then unpacks or compacts
     if (passes.fb_threshold > 0.0 && (rc = lk_backward(ctx, j, passes, search_d, search_state)) != PC_OK) return rc;
+    return PC_OK;
+}
+
+int compact_lane(pc_context* ctx, LkLane& lane, int n, int n_targets, long long* row_offset, uint32_t* src_indices, float2* tgt_xy, float* err) {
+    const size_t scratch_cap_before = lane.block_counts.cap;   // a reallocation changes the capacity (the address may repeat)
+    PC_HIP(lane.block_counts.ensure(pc::compact_scratch_words(n, n_targets)));
+    ScopedTimer t(ctx, PC_K_COMPACT, lane.stream);
+    pc::launch_compact(lane.rec.p, lane.slot_of, n, n_targets, lane.block_counts.p, lane.block_counts.cap != scratch_cap_before, row_offset,
+                       src_indices, tgt_xy, err, lane.stream);
     return PC_OK;
 }
 
@@ -432,6 +440,7 @@ int lk_track_impl(pc_context* ctx, const pc_frame* frame1, const pc_frame* const
     if ((rc = check_fb_threshold(passes.fb_threshold)) != PC_OK) return rc;
     PC_HIP(hipSetDevice(ctx->device));
     if (int jrc = join_prep(ctx)) return jrc;
+    LkLane& lane = ctx->lanes[0];
     if (passes.mask_windows) {
         // masked windows: the weight planes of every frame that has a mask on (a cache of the frame, made when the mask changed)
         passes.weights_f1 = frame1->mask_on;
@@ -443,7 +452,7 @@ int lk_track_impl(pc_context* ctx, const pc_frame* frame1, const pc_frame* const
     }
     const size_t rows = (size_t)frame1->n_kps * n_targets;
     if (rows == 0) {   // nothing to launch and nothing to write
-        if ((rc = run_lk_job(ctx, frame1, targets, n_targets, opt, passes, 0)) != PC_OK) return rc;
+        if ((rc = run_lk_job(ctx, lane, frame1, targets, n_targets, opt, passes)) != PC_OK) return rc;
         PC_HIP(hipStreamSynchronize(ctx->stream));
         return PC_OK;
     }
@@ -474,10 +483,10 @@ int lk_track_impl(pc_context* ctx, const pc_frame* frame1, const pc_frame* const
         if ((rc = side_reserve(ctx->lk_back_xy, out.back_xy, rows, &passes.back_xy)) != PC_OK) return rc;
         if ((rc = side_reserve(ctx->lk_back_status, out.back_status, rows, &passes.back_status)) != PC_OK) return rc;
     }
-    if ((rc = run_lk_job(ctx, frame1, targets, n_targets, opt, passes, 0)) != PC_OK) return rc;
+    if ((rc = run_lk_job(ctx, lane, frame1, targets, n_targets, opt, passes)) != PC_OK) return rc;
     const bool search = passes.search_radius > 0;   // its arrays are the job's own: the backward launches read them
-    if ((rc = side_download(ctx, out.search_d, search ? ctx->lk_search_d[0].p : nullptr, rows)) != PC_OK) return rc;
-    if ((rc = side_download(ctx, out.search_state, search ? ctx->lk_search_state[0].p : nullptr, rows)) != PC_OK) return rc;
+    if ((rc = side_download(ctx, out.search_d, search ? lane.search_d.p : nullptr, rows)) != PC_OK) return rc;
+    if ((rc = side_download(ctx, out.search_state, search ? lane.search_state.p : nullptr, rows)) != PC_OK) return rc;
     if ((rc = side_download(ctx, out.affine_m, passes.affine_m, rows)) != PC_OK) return rc;
     if ((rc = side_download(ctx, out.affine_state, passes.affine_state, rows)) != PC_OK) return rc;
     if ((rc = side_download(ctx, out.corr, passes.corr, rows)) != PC_OK) return rc;
@@ -488,8 +497,7 @@ int lk_track_impl(pc_context* ctx, const pc_frame* frame1, const pc_frame* const
     PC_HIP(ctx->lk_cxy.ensure(rows));
     PC_HIP(ctx->lk_cerr.ensure(rows));
     PC_HIP(ctx->lk_ustatus.ensure(rows));
-    pc::launch_unpack_records(ctx->lk_rec[0].p, ctx->lk_slot_of[0], frame1->n_kps, n_targets, ctx->lk_cxy.p,
-                              ctx->lk_ustatus.p, ctx->lk_cerr.p, ctx->stream);
+    pc::launch_unpack_records(lane.rec.p, lane.slot_of, frame1->n_kps, n_targets, ctx->lk_cxy.p, ctx->lk_ustatus.p, ctx->lk_cerr.p, ctx->stream);
     PC_HIP(hipMemcpyAsync(out.next_xy, ctx->lk_cxy.p, rows * sizeof(float2), hipMemcpyDeviceToHost, ctx->stream));
     PC_HIP(hipMemcpyAsync(out.status, ctx->lk_ustatus.p, rows, hipMemcpyDeviceToHost, ctx->stream));
     PC_HIP(hipMemcpyAsync(out.err, ctx->lk_cerr.p, rows * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
@@ -505,22 +513,17 @@ int lk_track_filtered_impl(pc_context* ctx, const pc_frame* frame1, const pc_fra
     if ((rc = check_fb_threshold(passes.fb_threshold)) != PC_OK) return rc;
     PC_HIP(hipSetDevice(ctx->device));
     if (int jrc = join_prep(ctx)) return jrc;
-    if ((rc = run_lk_job(ctx, frame1, targets, n_targets, opt, passes, 0)) != PC_OK) return rc;
+    LkLane& lane = ctx->lanes[0];
+    if ((rc = run_lk_job(ctx, lane, frame1, targets, n_targets, opt, passes)) != PC_OK) return rc;
     const int n = frame1->n_kps;
     const size_t rows = (size_t)n * n_targets;
     PC_HIP(ctx->lk_cxy.ensure(rows + 1));
     PC_HIP(ctx->lk_cerr.ensure(rows + 1));
     PC_HIP(ctx->lk_cidx.ensure(rows + 1));
     if (n > pc::kCompactMaxKeypoints) return fail(PC_E_CAPACITY, "%d keypoints: more than the compaction handles (%d)", n, pc::kCompactMaxKeypoints);
-    const size_t scratch_cap_before = ctx->lk_block_counts[0].cap;   // a reallocation changes the capacity (the address may repeat)
-    PC_HIP(ctx->lk_block_counts[0].ensure(pc::compact_scratch_words(n, n_targets)));
     PC_HIP(ctx->lk_row_offset.ensure(PC_MAX_TARGETS + 1));
     PC_HIP(ctx->h_row_offset.ensure(PC_MAX_TARGETS + 1));
-    {
-        ScopedTimer t(ctx, PC_K_COMPACT);
-        pc::launch_compact(ctx->lk_rec[0].p, ctx->lk_slot_of[0], n, n_targets, ctx->lk_block_counts[0].p,
-                           ctx->lk_block_counts[0].cap != scratch_cap_before, ctx->lk_row_offset.p, ctx->lk_cidx.p, ctx->lk_cxy.p, ctx->lk_cerr.p, ctx->stream);
-    }
+    if ((rc = compact_lane(ctx, lane, n, n_targets, ctx->lk_row_offset.p, ctx->lk_cidx.p, ctx->lk_cxy.p, ctx->lk_cerr.p)) != PC_OK) return rc;
     PC_HIP(hipMemcpyAsync(ctx->h_row_offset.p, ctx->lk_row_offset.p, (size_t)(n_targets + 1) * sizeof(long long), hipMemcpyDeviceToHost, ctx->stream));
     PC_HIP(hipStreamSynchronize(ctx->stream));
     for (int t = 0; t <= n_targets; t++) out.row_offset[t] = (int64_t)ctx->h_row_offset.p[t];

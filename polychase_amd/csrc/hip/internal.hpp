@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "../../../include/polychase_hip.h"
+#include "../../../include/polychase_records.h"
 #include "kernels.hpp"
 
 static_assert(pc::kMaxLevels == PC_MAX_LEVELS, "LKParams holds PC_MAX_LEVELS levels");
@@ -245,18 +246,62 @@ struct DetectScratch {
     bool cleared = false;                  // `counters` were zeroed in front of the coming detection (by the frame's level-0 kernel)
 };
 
+// One job lane: the stream a job's launches are enqueued on and what they write.  run_lk_job leaves the records in `rec` and the
+// inverse visiting order in `slot_of` (with a search radius the displacements and states in search_d / search_state), the
+// analyzer compacts them into `pack`.  pc_context holds two: lane 0 is the stage-level calls' lane, on pc_context::stream; the
+// analyzer alternates its jobs over lane 0 and lane 1 (pc_context::stream_b).
+struct LkLane {
+    hipStream_t stream = nullptr;          // not owned: pc_context::stream or stream_b
+    DevBuf<float4> rec;                    // raw records in visiting order (kernels.hpp LKParams::out_rec)
+    const uint32_t* slot_of = nullptr;     // not owned (a frame's d_perm or lk_perm): inverse visiting order of the latest job
+    DevBuf<uint32_t> block_counts;         // compaction scratch
+    DevBuf<short2> search_d;               // pc_lk_track_search: the displacements and the states of the latest job, [target][n]
+    DevBuf<uint8_t> search_state;          // (the backward launches read them)
+    DevBuf<uint8_t> pack;                  // the analyzer's compacted records of one job (pc::RecordLayout)
+};
+
+// The gate between the forward launches of the two lanes (kernels.hpp LKParams::gate): a gated launch stores its value into
+// `word` when its last workgroup starts, launch_lk_gate makes the other lane's stream wait for that value.
+struct LkGate {
+    DevBuf<uint32_t> word;                 // allocated (16 words, zeroed) by the first gated submit
+    PinBuf<uint32_t> timed_out;            // raised by a gate kernel that gave up
+    uint32_t seq = 0;                      // value the latest gated launch stores
+    bool on = true;                        // POLYCHASE_LK_GATE=0 (pc_context_create) and a timed-out wait switch it off
+    // Off for good once a wait has timed out: the lanes' streams share a hardware queue, the launch the gate kernel waited for
+    // was queued BEHIND it.
+    void drop_if_timed_out() {
+        if (*static_cast<volatile uint32_t*>(timed_out.p) == 0u) return;
+        on = false;
+        if (pc::trace_allocations()) fprintf(stderr, "[polychase_hip] LK gate timed out (streams share a hardware queue): gate switched off\n");
+    }
+    // Makes `s` wait for the previous gated launch, if there is one ahead (`armed`), and hands out the value the coming forward
+    // launch must store (run_lk_job's gate_value; never 0, which says "not gated").  Only while `on`.
+    int wait_and_next(hipStream_t s, bool armed, uint32_t* value) {
+        if (!word.p) {
+            PC_HIP(word.ensure(16));
+            PC_HIP(hipMemset(word.p, 0, 16 * sizeof(uint32_t)));
+            PC_HIP(timed_out.ensure(1));
+            timed_out.p[0] = 0u;
+        }
+        drop_if_timed_out();
+        if (armed && on) pc::launch_lk_gate(word.p, seq, timed_out.p, s);
+        if (++seq == 0) ++seq;
+        *value = seq;
+        return PC_OK;
+    }
+};
+
 struct pc_context {
     int device = 0;
     int arith = PC_ARITH_OPENCV_X86;     // pc_context_set_arithmetic; the default = what a stock x86-64 OpenCV build executes
     // Stage-level calls run on `stream`.  pc_analyzer alternates its jobs (LK launch + compaction + device-log append +
-    // record download of one frame1) over two job lanes, `stream` and `stream_b`: the launches of consecutive frames
+    // record download of one frame1) over two job lanes (`lanes`, on `stream` and `stream_b`): the launches of consecutive frames
     // overlap, so the tail of one launch and the gap before the next are filled by the other lane's wavefronts.
     // (HIP multiplexes streams onto GPU_MAX_HW_QUEUES hardware queues, 4 unless raised, and a stream that shares a queue
     // waits behind the other's commands: pc_runtime_init raises the default before the first HIP call.)
     // (Streams and events stand in front of the buffers: ~pc_context frees the buffers first and destroys the streams last.)
     Stream stream;
     Stream stream_b;
-    hipStream_t lane_stream(int lane) const { return lane ? stream_b : stream; }
     // pc_analyzer runs frame preparation (gray, pyramid, detection, keypoint ordering) on its own
     // stream so that it overlaps the LK launch of the previous frame1 on `stream`.  `work` is the stream
     // the image / detection helpers enqueue on: `stream` by default, `prep_stream` inside the analyzer.
@@ -265,7 +310,7 @@ struct pc_context {
     hipError_t sync_side_streams() const {
         hipError_t e = copy_stream ? hipStreamSynchronize(copy_stream) : hipSuccess;
         if (e == hipSuccess) e = hipStreamSynchronize(prep_stream);
-        if (stream_b && e == hipSuccess) e = hipStreamSynchronize(stream_b);
+        if (lanes[1].stream && e == hipSuccess) e = hipStreamSynchronize(lanes[1].stream);
         return e;
     }
     hipStream_t work = nullptr;          // not owned: `stream` or `prep_stream`
@@ -308,9 +353,8 @@ struct pc_context {
     PinBuf<int32_t> poly_host;
     DevBuf<int32_t> poly_dev;
     // LK scratch
-    // raw LK outputs, compaction scratch and packed records: one set per job lane of the analyzer (set 0: stage-level calls)
-    DevBuf<float4> lk_rec[2];              // raw records in visiting order (kernels.hpp LKParams::out_rec)
-    const uint32_t* lk_slot_of[2] = {nullptr, nullptr};   // not owned (a frame's d_perm or lk_perm): inverse visiting order of the latest launch into the set
+    LkLane lanes[2];                       // behind the streams: the lanes' buffers are freed before the streams are destroyed
+    LkGate gate;
     DevBuf<float2> lk_cxy;
     DevBuf<uint8_t> lk_ustatus;            // pc_lk_track: unpacked status
     DevBuf<float> lk_cerr;
@@ -319,23 +363,13 @@ struct pc_context {
     DevBuf<float> lk_corr;                 // pc_lk_track_correlated: the scores, [target][n]
     DevBuf<float4> lk_affine_m;            // pc_lk_track_affine: the matrices and the states, [target][n]
     DevBuf<uint8_t> lk_affine_state;
-    DevBuf<short2> lk_search_d[2];         // pc_lk_track_search: the displacements and the states of a job, [target][n], one set
-    DevBuf<uint8_t> lk_search_state[2];    // per job lane (the backward launches read them)
     DevBuf<uint8_t> lk_touched;            // pc_lk_track_window_masked: the keypoints the weights touched, [n]
     DevBuf<uint8_t> lk_choked;             // pc_lk_track_masked, pc_frame_download_choked_mask: the targets' choked planes
-    DevBuf<uint32_t> lk_cidx, lk_block_counts[2], lk_perm, lk_hist;
-    DevBuf<uint32_t> lk_gate;              // LKParams::gate of the analyzer's launches (one word)
-    PinBuf<uint32_t> lk_gate_timed_out;    // raised by a gate kernel that gave up (its stream shares a hardware queue with the other lane)
-    uint32_t lk_gate_seq = 0;              // value the latest gated launch stores
-    uint32_t lk_gate_next = 0;             // run_lk_job: value for the coming forward launch (0: not gated)
-    bool lk_gate_on = true;                // POLYCHASE_LK_GATE=0 switches the gate off
+    DevBuf<uint32_t> lk_cidx, lk_perm, lk_hist;
     DevBuf<unsigned long long> lk_prof;    // pc_debug_lk_profile: 16 words per wavefront of the latest launch
     size_t lk_prof_rows = 0;
     DevBuf<unsigned long long> lk_x86_stats;   // pc_debug_lk_x86_stats: four counters, or unallocated (not counting)
     DevBuf<long long> lk_row_offset;
-    // the analyzer's compacted records of one job, packed like a device-log record without its header:
-    // row offsets (128 B) | keypoints | src indices | tgt xy | errors, every part 16-byte aligned
-    DevBuf<uint8_t> lk_pack[2];
     PinBuf<long long> h_row_offset;
     // timing (the events: above)
     int launches[PC_K_COUNT] = {0};

@@ -23,6 +23,7 @@
 #include <thread>
 
 #include "../../../include/polychase_hip.h"
+#include "../../../include/polychase_records.h"
 #include "debug_images.h"
 #include "flow_database.h"
 #include "utils.h"
@@ -826,7 +827,6 @@ void OpticalFlowRecordWriter::Write(const uint8_t* log, size_t bytes, OpticalFlo
     OpticalFlowRunStats local;
     Keypoints known;
     const double t0 = Now();
-    auto up16 = [](size_t v) { return (v + 15) & ~static_cast<size_t>(15); };
     const char* batch_env = std::getenv("POLYCHASE_DB_BATCH_FRAMES");
     const int batch = std::max(1, batch_env ? std::atoi(batch_env) : 8);
     int in_batch = 0;
@@ -844,18 +844,19 @@ void OpticalFlowRecordWriter::Write(const uint8_t* log, size_t bytes, OpticalFlo
         }
     } rollback_guard{db, in_batch};
     while (o < bytes) {
-        // header (128 B): magic, frame1, keypoints, targets, target ids [8], rows; then the packed record:
-        // row offsets (128 B) | keypoints | src indices | tgt xy | errors, every part 16-byte aligned
-        if (o + 256 > bytes) throw std::runtime_error("truncated optical-flow record log");
+        // header: magic, frame1, keypoints, targets, target ids [8], rows; then the packed record (polychase_records.h)
+        const size_t o_pack = o + pc::RecordLayout::kLogHeaderBytes;   // 16-byte aligned, as every record's end is
+        if (o_pack + pc::RecordLayout::kRowOffsetBytes > bytes) throw std::runtime_error("truncated optical-flow record log");
         const long long* hdr = reinterpret_cast<const long long*>(log + o);
         if (hdr[0] != PC_LOG_MAGIC) throw std::runtime_error("corrupt optical-flow record log");
         const int32_t frame1 = static_cast<int32_t>(hdr[1]);
         const size_t n = static_cast<size_t>(hdr[2]), rows = static_cast<size_t>(hdr[12]);
         const int nt = static_cast<int>(hdr[3]);
         if (nt < 0 || nt > PC_MAX_TARGETS) throw std::runtime_error("corrupt optical-flow record log");
-        const long long* off = reinterpret_cast<const long long*>(log + o + 128);
-        const size_t o_kps = o + 256, o_idx = up16(o_kps + n * 8), o_xy = up16(o_idx + rows * 4), o_err = up16(o_xy + rows * 8);
-        const size_t end = up16(o_err + rows * 4);
+        const long long* off = reinterpret_cast<const long long*>(log + o_pack);
+        const pc::RecordLayout at(n, rows);
+        const size_t o_kps = o_pack + at.o_kps, o_idx = o_pack + at.o_idx, o_xy = o_pack + at.o_xy, o_err = o_pack + at.o_err;
+        const size_t end = o_pack + at.bytes;
         if (end > bytes) throw std::runtime_error("truncated optical-flow record log");
         if (in_batch == 0) db.Begin();
         if (!db.KeypointsExist(frame1)) {

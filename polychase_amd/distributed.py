@@ -157,10 +157,25 @@ def all_gather_device_log(log, used: int, group=None):
     return out, sizes
 
 
+LOG_HEADER_BYTES = 128       # int64 hdr[16]: magic, frame1, keypoints, targets, target ids [8], rows
+ROW_OFFSET_BYTES = 128       # int64 row_offset[16]
+
+
+def record_layout(n: int, rows: int):
+    """Where the parts of one device-log record lie, from the record's start (include/polychase_hip.h:
+    pc_analyzer_set_device_log; in C++: include/polychase_records.h): header | row offsets | keypoints [n] | src indices |
+    tgt xy | errors [rows each], every part 16-byte aligned.  -> (o_kps, o_idx, o_xy, o_err, end)."""
+    up16 = lambda v: (v + 15) & ~15
+    o_kps = LOG_HEADER_BYTES + ROW_OFFSET_BYTES
+    o_idx = up16(o_kps + n * 8)
+    o_xy = up16(o_idx + rows * 4)
+    o_err = up16(o_xy + rows * 8)
+    return o_kps, o_idx, o_xy, o_err, up16(o_err + rows * 4)
+
+
 def pack_device_log(records) -> np.ndarray:
     """records (frame1, kps [N,2] f32, {frame2: (idx, xy, err)}) -> the bytes pc_analyzer_set_device_log would have
     produced for them (include/polychase_hip.h), one record after the other."""
-    up16 = lambda v: (v + 15) & ~15
     chunks = []
     for frame1, kps, flows in records:
         items = sorted(flows.items())
@@ -177,12 +192,12 @@ def pack_device_log(records) -> np.ndarray:
             idx[o:o + m], xy[o:o + m], err[o:o + m] = i_, np.asarray(x_, np.float32).reshape(-1, 2), e_
             o += m
             off[t + 1] = o
-        rec = bytearray(hdr.tobytes() + off.tobytes() + kps.tobytes())
-        for part in (idx.tobytes(), xy.tobytes(), err.tobytes()):
-            rec += b"\0" * (up16(len(rec)) - len(rec)) + part
-        rec += b"\0" * (up16(len(rec)) - len(rec))
-        chunks.append(bytes(rec))
-    return np.frombuffer(b"".join(chunks), np.uint8).copy()
+        *starts, end = record_layout(len(kps), rows)
+        rec = np.zeros(end, np.uint8)
+        for at, part in zip([0, LOG_HEADER_BYTES] + starts, (hdr, off, kps, idx, xy, err)):
+            rec[at:at + part.nbytes] = part.reshape(-1).view(np.uint8)
+        chunks.append(rec)
+    return np.concatenate(chunks) if chunks else np.zeros(0, np.uint8)
 
 
 class ChunkedLogStitch:
@@ -552,16 +567,12 @@ def make_log_stitch(log, group=None, side_group=None, prefer: str = "rccl"):
 def parse_device_log(buf: np.ndarray, used: int):
     """buf: uint8 array of one rank's log.  -> records like pack_records' input."""
     out, o = [], 0
-    up16 = lambda v: (v + 15) & ~15
     while o < used:
-        hdr = buf[o:o + 128].view(np.int64)
+        hdr = buf[o:o + LOG_HEADER_BYTES].view(np.int64)
         assert int(hdr[0]) == LOG_MAGIC, "corrupt device log"
         frame1, n, nt, rows = int(hdr[1]), int(hdr[2]), int(hdr[3]), int(hdr[12])
-        off = buf[o + 128:o + 256].view(np.int64)
-        o_kps = o + 256
-        o_idx = up16(o_kps + n * 8)
-        o_xy = up16(o_idx + rows * 4)
-        o_err = up16(o_xy + rows * 8)
+        off = buf[o + LOG_HEADER_BYTES:o + LOG_HEADER_BYTES + ROW_OFFSET_BYTES].view(np.int64)
+        o_kps, o_idx, o_xy, o_err, end = (o + v for v in record_layout(n, rows))   # o is 16-byte aligned, as every record's end is
         kps = buf[o_kps:o_kps + n * 8].view(np.float32).reshape(n, 2).copy()
         idx = buf[o_idx:o_idx + rows * 4].view(np.uint32)
         xy = buf[o_xy:o_xy + rows * 8].view(np.float32).reshape(rows, 2)
@@ -571,5 +582,5 @@ def parse_device_log(buf: np.ndarray, used: int):
             a, b = int(off[t]), int(off[t + 1])
             flows[int(hdr[4 + t])] = (idx[a:b].copy(), xy[a:b].copy(), err[a:b].copy())
         out.append((frame1, kps, flows))
-        o = up16(o_err + rows * 4)
+        o = end
     return out
