@@ -172,6 +172,62 @@ int pc_context_get_gray_conversion(const pc_context* ctx, pc_gray_conversion* c,
 int pc_float_transfer_table(int kind, double gamma, double exposure, uint8_t* out);
 int pc_gray_quantize_weights(const double* rgb, pc_gray_conversion* out);
 int pc_float_transfer_index(const float* values, int n, uint32_t* out);
+
+/* ---- lens undistortion at ingest (not in the reference): frames are made pinhole as they are put ----
+ * Everything behind the gray plane -- detection, LK, masks, the tracker and the refiner -- assumes a pinhole camera.  With a lens
+ * map set, every frame put into the context is resampled into the undistorted camera's pixel grid, so keypoints, flow rows and
+ * masks live in ONE undistorted pixel space and none of that code knows a lens existed.  All arithmetic is integer on the device
+ * and fp64 on the host; every result is defined bit for bit.
+ *   lens map     int32 q[h][w][2]: for the undistorted pixel (u, v) the source position (sx, sy) in the original frame in units of
+ *                1 / 256 px (PC_LENS_FRAC_BITS = 8), pixel centres at integers (as in the polygon masks):
+ *                q = floor(s * 256 + 0.5), computed in fp64 and clamped to +-2^24.  A source position with a component that is not
+ *                finite writes PC_LENS_INVALID (INT32_MIN) to BOTH components.
+ *   remap        of the gray plane G (w x h, u8) into U, per (u, v) with entry (qx, qy): an entry with a component equal to
+ *                PC_LENS_INVALID gives U = 0.  Otherwise ix = qx >> 8 (arithmetic shift), wx = qx & 255, likewise iy, wy; the four
+ *                taps a, b, c, d are G at (clamp(ix, 0, w - 1) | clamp(ix + 1, 0, w - 1), clamp(iy, 0, h - 1) | clamp(iy + 1, 0, h - 1));
+ *                top = a (256 - wx) + b wx, bot = c (256 - wx) + d wx, U = (top (256 - wy) + bot wy + 32768) >> 16.
+ *                With q = 256 (u, v) this is G itself, bit for bit.
+ *   order        GRAY CONVERSION COMES FIRST: an RGB or float source is converted to gray per SOURCE pixel by the context's gray
+ *                conversion (default, weights or transfer table, exactly as without a map), and the gray plane is then remapped:
+ *                gray kernel -> remap kernel -> level kernel.  (A kernel that fuses the three would have to convert each tap
+ *                before blending.)
+ *   validity     pixel (u, v) is valid iff 0 <= qx <= (w - 1) 256 and 0 <= qy <= (h - 1) 256: a property of the map, computed on
+ *                the host.
+ * Two ways to a map, both host-only (no device, no context, like pc_float_transfer_table):
+ * pc_lens_build_map: the polynomial model.  The undistorted camera has the focal lengths fx zoom, fy zoom and the same principal
+ * point; in fp64, every operation rounded on its own in the order written (the library is built with contraction off):
+ *   x = (u - cx) / (fx zoom), y = (v - cy) / (fy zoom), r2 = x x + y y, rad = 1 + r2 (k1 + r2 (k2 + r2 k3)),
+ *   xd = x rad + 2 p1 x y + p2 (r2 + 2 x x), yd = y rad + p1 (r2 + 2 y y) + 2 p2 x y, sx = xd fx + cx, sy = yd fy + cy.
+ * pc_lens_default_model: fx = fy = 1, zoom = 1, everything else 0.
+ * pc_lens_map_from_stmap: a float32 st[h][w][2] in [0, 1] that another tool has written (anamorphic and fisheye lenses), pixel
+ * centre i at (i + 0.5) / w: sx = (double)s w - 0.5, sy = flip_v ? (1 - (double)t) h - 0.5 : (double)t h - 0.5.  Values outside
+ * [0, 1] are taken as they are (the remap clamps its taps); a NaN or an infinity makes the entry PC_LENS_INVALID.
+ * pc_lens_map_valid: the validity plane, 255 / 0, eroded: with erode = m >= 0 a pixel stays on iff every pixel of the (2m + 1)^2 box
+ * around it that lies inside the frame is valid.  *all_valid (may be null) = 1 iff every byte of `out` is 255.
+ * These four refuse with PC_E_INVALID and leave their output untouched: a null argument, a model value that is not finite, fx, fy
+ * or zoom <= 0, w or h outside what pc_frame_create takes (>= 1, w h <= 2^30), erode outside 0 .. PC_LENS_MAX_ERODE.
+ * pc_context_set_lens_map: q is host memory, copied into device memory the context owns together with two w x h planes; NULL
+ * clears the map and frees all three.  A per-run call: it may wait for the context's streams.  It takes effect for every frame put
+ * afterwards through pc_frame_set_rgb, _rgb_f32, _gray and pc_analyzer_put_frame[_f32] of this context, with every `on_device`
+ * value.  A frame whose size differs from the map's: PC_E_INVALID, the frame left untouched.  A refused setter (null context, a
+ * size pc_frame_create would not take) leaves the map in force.  Without a map these calls enqueue exactly what they enqueue
+ * without this call ever made.  The remap launch is counted under PC_K_GRAY.
+ * pc_context_get_lens_map_size: the size of the map in force, 0 x 0 without one. */
+#define PC_LENS_FRAC_BITS 8
+#define PC_LENS_INVALID INT32_MIN
+#define PC_LENS_MAX_ERODE 64
+typedef struct pc_lens_model {
+    double fx, fy, cx, cy; /* of the ORIGINAL frames, pixels */
+    double k1, k2, k3;     /* radial */
+    double p1, p2;         /* tangential */
+    double zoom;           /* 1: the undistorted camera keeps fx, fy */
+} pc_lens_model;
+void pc_lens_default_model(pc_lens_model* m);
+int pc_lens_build_map(const pc_lens_model* m, int w, int h, int32_t* q);
+int pc_lens_map_from_stmap(const float* st, int w, int h, int flip_v, int32_t* q);
+int pc_lens_map_valid(const int32_t* q, int w, int h, int erode, uint8_t* out /* 255 / 0 */, int* all_valid);
+int pc_context_set_lens_map(pc_context* ctx, const int32_t* q /* host */, int w, int h);
+int pc_context_get_lens_map_size(const pc_context* ctx, int* w, int* h);
 /* hipStream_t the context enqueues on (for callers that time with HIP events / torch streams). */
 void* pc_context_stream(pc_context* ctx);
 /* Timing of the context's kernels with HIP events on the stream each launch is enqueued on.  `class_mask` bit k

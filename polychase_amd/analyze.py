@@ -157,6 +157,10 @@ def main(argv=None) -> int:
                     help="transfer curve for float32 frames: scene-linear values through the sRGB curve or a power law (nothing for uint8 frames)")
     ap.add_argument("--float-gamma", type=float, default=2.2, metavar="G", help="--float-transfer gamma: the exponent's inverse, 1..4")
     ap.add_argument("--float-exposure", type=float, default=0.0, metavar="STOPS", help="gain in stops in front of the transfer curve, -16..16")
+    ap.add_argument("--lens", type=float, nargs=9, default=None, metavar=("FX", "FY", "CX", "CY", "K1", "K2", "K3", "P1", "P2"),
+                    help="lens undistortion at ingest: the polynomial model of the original frames; every frame is made pinhole as it is put, "
+                         "keypoints and flow rows are undistorted coordinates (the undistorted camera: FX * Z, FY * Z, CX, CY)")
+    ap.add_argument("--lens-zoom", type=float, default=1.0, metavar="Z", help="--lens: focal length of the undistorted camera relative to FX, FY")
     ap.add_argument("--search-radius", type=int, default=0, metavar="N",
                     help="search prepass: block matching within N pixels (1..256) in front of a second LK pass, for fast pans and the long skips (0: off; not with --normalize)")
     ap.add_argument("--mask-polygon", type=float, nargs="+", default=None, metavar="X Y",
@@ -229,6 +233,8 @@ def main(argv=None) -> int:
     fopt.float_transfer = args.float_transfer
     fopt.float_transfer_gamma = args.float_gamma
     fopt.float_exposure = args.float_exposure
+    if args.lens is not None:
+        fopt.lens = core.LensModel(*args.lens, zoom=args.lens_zoom)
     if int(os.environ.get("RANK", "0")) == 0 and os.path.exists(args.database):
         os.remove(args.database)
     if world > 1:

@@ -1010,6 +1010,10 @@ int pc_api::set_image(pc_context* ctx, pc_frame* f, const uint8_t* src, size_t r
     if (elem_size == 4 && ((reinterpret_cast<uintptr_t>(src) | row_pitch) & 3)) return fail(PC_E_INVALID, "float frame is not 4-byte aligned");
     const size_t row_bytes = (size_t)f->w * channels * elem_size;
     if (row_pitch < row_bytes) return fail(PC_E_INVALID, "row_pitch %zu < %zu", row_pitch, row_bytes);
+    // a lens map is made for one frame size (before anything is enqueued: the frame keeps its planes)
+    const bool lens = ctx->lens_w > 0;
+    if (lens && (f->w != ctx->lens_w || f->h != ctx->lens_h))
+        return fail(PC_E_INVALID, "frame is %dx%d, the context's lens map %dx%d", f->w, f->h, ctx->lens_w, ctx->lens_h);
     PC_HIP(hipSetDevice(ctx->device));
     if (ctx->work == ctx->stream) {
         int jrc = join_prep(ctx);
@@ -1055,7 +1059,54 @@ int pc_api::set_image(pc_context* ctx, pc_frame* f, const uint8_t* src, size_t r
         PC_HIP(hipMemcpy2DAsync(ctx->staging.p, d_pitch, src, row_pitch, row_bytes, f->h, hipMemcpyHostToDevice, ctx->work));
         d_src = ctx->staging.p;
     }
-    if (!unfused_pyramid() && level_fits_fused(f->levels[0], f->win)) {
+    // the unfused gray kernel of the source kind, into the interior of `l0`
+    auto gray_into = [&](const pc::Level& l0) {
+        ScopedTimer t(ctx, PC_K_GRAY);
+        const bool dw = ctx->gray_default_weights();
+        if (elem_size == 4 && (ctx->gray_table_on || !dw))
+            pc::launch_rgbf32_to_gray_converted(reinterpret_cast<const float*>(d_src), d_pitch, channels, l0, ctx->gray_w, ctx->gray_table_dev(),
+                                                ctx->work);
+        else if (elem_size == 4) pc::launch_rgbf32_to_gray(reinterpret_cast<const float*>(d_src), d_pitch, channels, l0, ctx->work);
+        else if (channels == 3 && !dw) pc::launch_rgb2gray_weighted(d_src, d_pitch, l0, ctx->gray_w, ctx->work);
+        else if (channels == 3) pc::launch_rgb2gray(d_src, d_pitch, l0, ctx->work);
+        else pc::launch_copy_gray(d_src, d_pitch, l0, ctx->work);
+    };
+    if (lens) {
+        // Lens undistortion (include/polychase_hip.h: pc_context_set_lens_map): gray conversion first, per source pixel, into the
+        // context's plane; the remap of that plane; then level 0 from the remapped plane as from a gray frame.
+        const bool fused = !unfused_pyramid() && level_fits_fused(f->levels[0], f->win);
+        if (clear && !fused) PC_HIP(hipMemsetAsync(clear, 0, (size_t)clear_words * sizeof(uint32_t), ctx->work));
+        pc::Level g{};
+        g.img = ctx->lens_gray.p;
+        g.w = f->w;
+        g.h = f->h;
+        g.pitch = ctx->lens_plane_pitch;
+        gray_into(g);
+        if (staged >= 0) PC_HIP(hipEventRecord(ctx->staging_ev[staged][1], ctx->work));   // the gray kernel is the last reader of the source
+        {
+            ScopedTimer t(ctx, PC_K_GRAY);
+            // the unfused chain starts from the level-0 interior, which the remap then writes itself
+            pc::launch_lens_remap(g.img, g.pitch, f->w, f->h, ctx->lens_map.p, ctx->lens_pitch, fused ? ctx->lens_out.p : f->levels[0].img,
+                                  fused ? ctx->lens_plane_pitch : f->levels[0].pitch, ctx->work);
+        }
+        if (fused) {
+            pc::LevelSource in{};
+            in.kind = pc::SRC_GRAY8;
+            in.src = ctx->lens_out.p;
+            in.src_pitch = (size_t)ctx->lens_plane_pitch;
+            in.channels = 1;
+            in.aligned = 1;
+            in.clear = clear;
+            in.clear_words = clear ? clear_words : 0;
+            {
+                ScopedTimer t(ctx, PC_K_PYRAMID);
+                pc::launch_level(in, f->levels[0], f->win, ctx->work);
+            }
+            build_pyramid(ctx, f, 1);
+        } else {
+            build_pyramid(ctx, f, 0);
+        }
+    } else if (!unfused_pyramid() && level_fits_fused(f->levels[0], f->win)) {
         // level 0 in one pass: gray conversion fused with the padding, the uint16 plane and the Scharr plane
         pc::LevelSource in{};
         // the default gray conversion: the instances (and the launch arguments they read) of a context that never set one
@@ -1080,17 +1131,7 @@ int pc_api::set_image(pc_context* ctx, pc_frame* f, const uint8_t* src, size_t r
         build_pyramid(ctx, f, 1);
     } else {
         if (clear) PC_HIP(hipMemsetAsync(clear, 0, (size_t)clear_words * sizeof(uint32_t), ctx->work));
-        {
-            ScopedTimer t(ctx, PC_K_GRAY);
-            const bool dw = ctx->gray_default_weights();
-            if (elem_size == 4 && (ctx->gray_table_on || !dw))
-                pc::launch_rgbf32_to_gray_converted(reinterpret_cast<const float*>(d_src), d_pitch, channels, f->levels[0], ctx->gray_w,
-                                                    ctx->gray_table_dev(), ctx->work);
-            else if (elem_size == 4) pc::launch_rgbf32_to_gray(reinterpret_cast<const float*>(d_src), d_pitch, channels, f->levels[0], ctx->work);
-            else if (channels == 3 && !dw) pc::launch_rgb2gray_weighted(d_src, d_pitch, f->levels[0], ctx->gray_w, ctx->work);
-            else if (channels == 3) pc::launch_rgb2gray(d_src, d_pitch, f->levels[0], ctx->work);
-            else pc::launch_copy_gray(d_src, d_pitch, f->levels[0], ctx->work);
-        }
+        gray_into(f->levels[0]);
         if (staged >= 0) PC_HIP(hipEventRecord(ctx->staging_ev[staged][1], ctx->work));
         build_pyramid(ctx, f, 0);
     }

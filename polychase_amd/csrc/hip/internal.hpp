@@ -324,6 +324,12 @@ struct pc_context {
     const uint8_t* gray_table_dev() const { return gray_table_on ? gray_table_buf[gray_table_cur].p : nullptr; }
     std::vector<uint8_t> gray_table_host;  // the table in force (pc_context_get_gray_conversion)
     bool gray_default_weights() const { return gray_w[0] == 9798 && gray_w[1] == 19235 && gray_w[2] == 3735; }
+    // pc_context_set_lens_map: the map of the frames put from now on (lens_w x lens_h entries in rows of lens_pitch, a multiple
+    // of 4), the gray plane of the source the remap reads and the plane it writes for the level-0 kernel (rows of
+    // lens_plane_pitch bytes each); all three allocated by the setter and freed when the map is cleared.  lens_w == 0: no map
+    DevBuf<int32_t> lens_map;
+    DevBuf<uint8_t> lens_gray, lens_out;
+    int lens_w = 0, lens_h = 0, lens_pitch = 0, lens_plane_pitch = 0;
     // the analyzer's host frames (PC_FRAME_PINNED_HOST): transfers on a stream of their own, two buffers in turn;
     // staging_ev[b] = {copy into b complete (copy stream), the kernel that reads b has run (preparation stream)}
     Stream copy_stream;                  // POLYCHASE_COPY_STREAM=0: none (the transfer is enqueued in front of the frame's kernels)

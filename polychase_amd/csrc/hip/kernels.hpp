@@ -34,6 +34,15 @@ void launch_widen(const Level& l, int win, hipStream_t s);
 // K6: Scharr derivative plane of the interior (needs the 1-px border to be filled)
 void launch_scharr(const Level& l, hipStream_t s);
 
+// ---- kernels_lens.hip ----
+// Lens undistortion at ingest (include/polychase_hip.h: pc_context_set_lens_map): dst(u, v) = the bilinear blend of the w x h gray
+// plane `src` at the position map[v][u] names in 1 / 256 px, taps clamped to the plane, an invalid entry -> 0.  map: h rows of
+// map_pitch (x, y) entries, map_pitch a multiple of 4 and >= w, 16-byte aligned; dst rows 4-byte aligned, written up to w.
+constexpr int kLensFracBits = 8;            // == PC_LENS_FRAC_BITS
+constexpr int32_t kLensInvalid = INT32_MIN; // == PC_LENS_INVALID
+void launch_lens_remap(const uint8_t* src, int src_pitch, int w, int h, const int32_t* map, int map_pitch, uint8_t* dst, int dst_pitch,
+                       hipStream_t s);
+
 // ---- kernels_pyramid.hip ----
 // One fused kernel per pyramid level: the level's pixels (gray conversion of the frame for level 0, pyrDown of the
 // parent's padded plane otherwise) -> u8 plane + REFLECT_101 padding + uint16 plane + Scharr plane.

@@ -32,6 +32,19 @@ struct GFTTOptions {
     int grid_cols = 4;
 };
 
+// Polynomial lens model of the ORIGINAL frames (include/polychase_hip.h: pc_lens_model has the formula; not in the reference).
+// The undistorted camera -- the one the tracker and the refiner must be given -- has fx * zoom, fy * zoom, cx, cy.
+struct LensModel {
+    double fx = 1.0, fy = 1.0, cx = 0.0, cy = 0.0;
+    double k1 = 0.0, k2 = 0.0, k3 = 0.0, p1 = 0.0, p2 = 0.0;
+    double zoom = 1.0;
+};
+// A ready-made lens map: int32 q[height][width][2], source positions in 1 / 256 px (pc_lens_build_map, pc_lens_map_from_stmap)
+struct LensMapData {
+    int width = 0, height = 0;
+    std::vector<int32_t> q;
+};
+
 // Pyramidal Lucas-Kanade.  max_level counts pyramid levels ABOVE level 0 (OpenCV semantics).
 struct OpticalFlowOptions {
     int window_size = 10;
@@ -77,6 +90,14 @@ struct OpticalFlowOptions {
     std::string float_transfer = "none";
     double float_transfer_gamma = 2.2;
     double float_exposure = 0.0;
+    // not in the reference: lens undistortion at ingest (include/polychase_hip.h: pc_context_set_lens_map).  Either a polynomial
+    // model, from which the run builds the map at the clip's size, or a ready-made map of the clip's size (an STmap of an
+    // anamorphic or fisheye lens); nothing = frames are taken as pinhole.  Every frame is resampled into the undistorted camera as
+    // it is put, AFTER its gray conversion: keypoints, flow rows and a caller's detection_mask are all in undistorted pixel
+    // coordinates, and the database must not be resumed under another lens.  Without a detection_mask of the caller the run masks
+    // the detection where the map leaves the original frame (pc_lens_map_valid eroded by window_size / 2 + 1), when any pixel does.
+    std::optional<LensModel> lens_model;
+    std::shared_ptr<const LensMapData> lens_map;
 };
 // std::invalid_argument for what no run accepts; every entry point calls it before it asks for a frame
 inline void CheckOpticalFlowOptions(const OpticalFlowOptions& o) {
@@ -99,6 +120,18 @@ inline void CheckOpticalFlowOptions(const OpticalFlowOptions& o) {
                 throw std::invalid_argument("channel_weights must be finite and >= 0, got " + std::to_string(c));
         const double s = w[0] + w[1] + w[2];
         if (!(s > 0.0 && std::isfinite(s))) throw std::invalid_argument("channel_weights must have a positive, finite sum");
+    }
+    if (o.lens_model && o.lens_map) throw std::invalid_argument("lens: a model or a map, not both");
+    if (o.lens_model) {
+        const LensModel& m = *o.lens_model;
+        for (double v : {m.fx, m.fy, m.cx, m.cy, m.k1, m.k2, m.k3, m.p1, m.p2, m.zoom})
+            if (!std::isfinite(v)) throw std::invalid_argument("lens model values must be finite, got " + std::to_string(v));
+        if (!(m.fx > 0.0 && m.fy > 0.0 && m.zoom > 0.0)) throw std::invalid_argument("lens model: fx, fy and zoom must be > 0");
+    }
+    if (o.lens_map) {
+        const LensMapData& m = *o.lens_map;
+        if (m.width < 1 || m.height < 1 || m.q.size() != static_cast<size_t>(m.width) * static_cast<size_t>(m.height) * 2)
+            throw std::invalid_argument("lens map must be int32 of shape (H, W, 2)");
     }
     if (o.float_transfer != "none" && o.float_transfer != "srgb" && o.float_transfer != "gamma")
         throw std::invalid_argument("float_transfer must be \"none\", \"srgb\" or \"gamma\", got \"" + o.float_transfer + "\"");

@@ -349,9 +349,48 @@ struct LogPiece {
 static void RunAnalysis(const VideoInfo& video_info, FrameAccessorFunction frame_accessor,
                         OpticalFlowProgressCallback callback, const std::string& database_path,
                         const GFTTOptions& detector_options, const OpticalFlowOptions& flow_options,
-                        OpticalFlowRunStats* stats, OpticalFlowShard* shard, bool write_images, const DetectionMask& detection_mask) {
+                        OpticalFlowRunStats* stats, OpticalFlowShard* shard, bool write_images, const DetectionMask& caller_mask) {
     CHECK(frame_accessor);
     CheckOpticalFlowOptions(flow_options);
+    const double t_begin = Now();   // the lens map below is part of the run's set-up (OpticalFlowRunStats::seconds_setup)
+    // The lens map of the run (host work only; before any GPU work, like the other refusals): built from the model at the clip's
+    // size, or the caller's.  Without a mask of the caller's the detection is kept off the pixels whose source lies outside the
+    // original frame, and off a band of half a window + 1 around them -- only when there are such pixels: an all-valid map sets no
+    // mask and allocates nothing.
+    std::shared_ptr<const LensMapData> lens = flow_options.lens_map;
+    if (flow_options.lens_model) {
+        const LensModel& lm = *flow_options.lens_model;
+        pc_lens_model m{lm.fx, lm.fy, lm.cx, lm.cy, lm.k1, lm.k2, lm.k3, lm.p1, lm.p2, lm.zoom};
+        auto built = std::make_shared<LensMapData>();
+        built->width = static_cast<int>(video_info.width);
+        built->height = static_cast<int>(video_info.height);
+        built->q.resize(static_cast<size_t>(video_info.width) * video_info.height * 2);
+        if (pc_lens_build_map(&m, built->width, built->height, built->q.data()) != PC_OK) throw std::invalid_argument(pc_last_error());
+        lens = built;
+    }
+    DetectionMask lens_mask;
+    if (lens) {
+        if (lens->width != static_cast<int>(video_info.width) || lens->height != static_cast<int>(video_info.height))
+            throw std::invalid_argument("lens map is " + std::to_string(lens->width) + " x " + std::to_string(lens->height) + ", the clip " +
+                                        std::to_string(video_info.width) + " x " + std::to_string(video_info.height));
+        if (caller_mask.empty()) {
+            auto plane = std::make_shared<std::vector<uint8_t>>(static_cast<size_t>(lens->width) * lens->height);
+            int all_valid = 0;
+            const int erode = std::min(flow_options.window_size / 2 + 1, PC_LENS_MAX_ERODE);
+            if (pc_lens_map_valid(lens->q.data(), lens->width, lens->height, std::max(erode, 0), plane->data(), &all_valid) != PC_OK)
+                throw std::invalid_argument(pc_last_error());
+            if (!all_valid) {
+                MaskView v;
+                v.data = plane->data();
+                v.rows = lens->height;
+                v.cols = lens->width;
+                v.row_pitch = static_cast<size_t>(lens->width);
+                v.owner = plane;
+                lens_mask.fixed = v;
+            }
+        }
+    }
+    const DetectionMask& detection_mask = lens_mask.fixed ? lens_mask : caller_mask;
     auto check_mask = [&](const MaskView& m) {
         if (m.polygons) return;   // any size of frame; the engine refuses bad polygons
         if (!m.data || m.rows != static_cast<int>(video_info.height) || m.cols != static_cast<int>(video_info.width) ||
@@ -360,7 +399,6 @@ static void RunAnalysis(const VideoInfo& video_info, FrameAccessorFunction frame
                                         " uint8 (the reference CHECKs CV_8UC1 and the image's size, gftt.cc:22-27)");
     };
     if (detection_mask.fixed) check_mask(*detection_mask.fixed);   // before any GPU work
-    const double t_begin = Now();
     std::unique_ptr<Database> db;
     if (!database_path.empty()) db = std::make_unique<Database>(database_path, /*bulk_writer=*/true);
     // Bulk load: rows go in under a rollback journal and the file is put back into WAL mode on every way out (done,
@@ -456,6 +494,9 @@ static void RunAnalysis(const VideoInfo& video_info, FrameAccessorFunction frame
         }
         if (pc_context_set_gray_conversion(eng.ctx, &conv) != PC_OK) ThrowHip("pc_context_set_gray_conversion");
     }
+    // ... the lens map, or none (a parked engine may hold the last run's) ...
+    if (pc_context_set_lens_map(eng.ctx, lens ? lens->q.data() : nullptr, lens ? lens->width : 0, lens ? lens->height : 0) != PC_OK)
+        ThrowHip("pc_context_set_lens_map");
     // ... the target-side margin, off without a mask to choke ...
     const int target_margin = detection_mask.empty() ? -1 : flow_options.target_mask_margin;
     if (pc_analyzer_set_target_mask_margin(eng.an, target_margin) != PC_OK) ThrowHip("pc_analyzer_set_target_mask_margin");

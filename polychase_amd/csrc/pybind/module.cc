@@ -99,6 +99,30 @@ std::optional<FrameView> FrameFromPython(const py::object& obj, std::deque<py::o
     return v;
 }
 
+using I32Array = py::array_t<int32_t, py::array::c_style>;
+
+// int32 (H, W, 2) -> an owned copy; ValueError for any other dtype or shape (no silent conversion: a float array is not a map)
+std::shared_ptr<const LensMapData> LensMapFromPython(const py::object& obj) {
+    if (!py::isinstance<py::array>(obj)) throw py::value_error("lens must be None, a LensModel or an int32 array of shape (H, W, 2)");
+    const py::array arr = py::reinterpret_borrow<py::array>(obj);
+    if (!arr.dtype().is(py::dtype::of<int32_t>())) throw py::value_error("a lens map must have dtype int32");
+    if (arr.ndim() != 3 || arr.shape(2) != 2 || arr.shape(0) < 1 || arr.shape(1) < 1) throw py::value_error("a lens map must have shape (H, W, 2)");
+    const I32Array a = I32Array::ensure(arr);
+    auto m = std::make_shared<LensMapData>();
+    m->height = static_cast<int>(a.shape(0));
+    m->width = static_cast<int>(a.shape(1));
+    m->q.assign(a.data(), a.data() + a.size());
+    return m;
+}
+
+py::array_t<int32_t> LensMapToPython(const LensMapData& m) {
+    py::array_t<int32_t> out({static_cast<py::ssize_t>(m.height), static_cast<py::ssize_t>(m.width), static_cast<py::ssize_t>(2)});
+    std::copy(m.q.begin(), m.q.end(), out.mutable_data());
+    return out;
+}
+
+pc_lens_model ToAbi(const LensModel& m) { return pc_lens_model{m.fx, m.fy, m.cx, m.cy, m.k1, m.k2, m.k3, m.p1, m.p2, m.zoom}; }
+
 // Python detection mask (numpy H x W uint8) -> MaskView owning a packed copy.  ValueError for any other dtype or shape: the
 // reference CHECKs CV_8UC1 and the image's size (gftt.cc:22-27); no silent conversion.
 MaskView MaskFromPython(const py::object& obj, const VideoInfo& video_info) {
@@ -470,6 +494,53 @@ PYBIND11_MODULE(polychase_core, m) {
         .def_readwrite("use_harris", &GFTTOptions::use_harris)
         .def_readwrite("harris_k", &GFTTOptions::harris_k);
 
+    // not in the reference: lens undistortion at ingest (include/polychase_hip.h: pc_lens_model, pc_context_set_lens_map)
+    py::class_<LensModel>(m, "LensModel")
+        .def(py::init([](double fx, double fy, double cx, double cy, double k1, double k2, double k3, double p1, double p2, double zoom) {
+                 return LensModel{fx, fy, cx, cy, k1, k2, k3, p1, p2, zoom};
+             }),
+             py::arg("fx"), py::arg("fy"), py::arg("cx"), py::arg("cy"), py::arg("k1") = 0.0, py::arg("k2") = 0.0, py::arg("k3") = 0.0,
+             py::arg("p1") = 0.0, py::arg("p2") = 0.0, py::arg("zoom") = 1.0)
+        .def_readwrite("fx", &LensModel::fx)
+        .def_readwrite("fy", &LensModel::fy)
+        .def_readwrite("cx", &LensModel::cx)
+        .def_readwrite("cy", &LensModel::cy)
+        .def_readwrite("k1", &LensModel::k1)
+        .def_readwrite("k2", &LensModel::k2)
+        .def_readwrite("k3", &LensModel::k3)
+        .def_readwrite("p1", &LensModel::p1)
+        .def_readwrite("p2", &LensModel::p2)
+        .def_readwrite("zoom", &LensModel::zoom)
+        // the lens map int32 (H, W, 2) the run builds from this model for a clip of that size (pc_lens_build_map)
+        .def("build_map", [](const LensModel& lm, int width, int height) {
+            const pc_lens_model abi = ToAbi(lm);
+            LensMapData d;
+            d.width = width;
+            d.height = height;
+            if (width >= 1 && height >= 1 && static_cast<long long>(width) * height <= (1ll << 30)) d.q.resize(static_cast<size_t>(width) * height * 2);
+            if (pc_lens_build_map(&abi, width, height, d.q.data()) != PC_OK) throw std::invalid_argument(pc_last_error());
+            return LensMapToPython(d);
+        }, py::arg("width"), py::arg("height"));
+    // float32 STmap (H, W, 2) in [0, 1] -> lens map (pc_lens_map_from_stmap); flip_v: t = 0 is the bottom row (the usual STmap)
+    m.def("lens_map_from_stmap", [](const py::array& st, bool flip_v) {
+        if (!st.dtype().is(py::dtype::of<float>()) || st.ndim() != 3 || st.shape(2) != 2 || st.shape(0) < 1 || st.shape(1) < 1)
+            throw py::value_error("an STmap must be a float32 array of shape (H, W, 2)");
+        const F32Array a = F32Array::ensure(st);
+        LensMapData d;
+        d.height = static_cast<int>(a.shape(0));
+        d.width = static_cast<int>(a.shape(1));
+        d.q.resize(static_cast<size_t>(a.size()));
+        if (pc_lens_map_from_stmap(a.data(), d.width, d.height, flip_v ? 1 : 0, d.q.data()) != PC_OK) throw std::invalid_argument(pc_last_error());
+        return LensMapToPython(d);
+    }, py::arg("st"), py::arg("flip_v") = true);
+    // the validity plane uint8 (H, W), 255 / 0, of a lens map, eroded by `erode` pixels (pc_lens_map_valid)
+    m.def("lens_map_valid", [](const py::object& q, int erode) {
+        const std::shared_ptr<const LensMapData> d = LensMapFromPython(q);
+        py::array_t<uint8_t> out({static_cast<py::ssize_t>(d->height), static_cast<py::ssize_t>(d->width)});
+        if (pc_lens_map_valid(d->q.data(), d->width, d->height, erode, out.mutable_data(), nullptr) != PC_OK) throw std::invalid_argument(pc_last_error());
+        return out;
+    }, py::arg("q"), py::arg("erode") = 0);
+
     py::class_<OpticalFlowOptions>(m, "OpticalFlowOptions")
         .def(py::init<>())
         .def_readwrite("window_size", &OpticalFlowOptions::window_size)
@@ -488,7 +559,27 @@ PYBIND11_MODULE(polychase_core, m) {
         .def_readwrite("channel_weights", &OpticalFlowOptions::channel_weights)           // None or three floats (r, g, b)
         .def_readwrite("float_transfer", &OpticalFlowOptions::float_transfer)             // "none", "srgb" or "gamma"
         .def_readwrite("float_transfer_gamma", &OpticalFlowOptions::float_transfer_gamma)
-        .def_readwrite("float_exposure", &OpticalFlowOptions::float_exposure);            // stops
+        .def_readwrite("float_exposure", &OpticalFlowOptions::float_exposure)             // stops
+        // not in the reference: lens undistortion at ingest -- None, a LensModel, or a lens map int32 (H, W, 2) of the clip's size
+        .def_property(
+            "lens",
+            [](const OpticalFlowOptions& o) -> py::object {
+                if (o.lens_model) return py::cast(*o.lens_model);
+                if (o.lens_map) return LensMapToPython(*o.lens_map);
+                return py::none();
+            },
+            [](OpticalFlowOptions& o, const py::object& v) {
+                if (v.is_none()) {
+                    o.lens_model.reset();
+                    o.lens_map.reset();
+                } else if (py::isinstance<LensModel>(v)) {
+                    o.lens_model = v.cast<LensModel>();
+                    o.lens_map.reset();
+                } else {
+                    o.lens_map = LensMapFromPython(v);
+                    o.lens_model.reset();
+                }
+            });
 
     py::class_<OpticalFlowProgress>(m, "OpticalFlowProgress")
         .def_readonly("progress", &OpticalFlowProgress::progress)

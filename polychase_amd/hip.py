@@ -26,6 +26,8 @@ SYMBOLS = [
     "pc_runtime_init", "pc_context_set_arithmetic", "pc_context_get_arithmetic", "pc_context_download",
     "pc_gray_default_conversion", "pc_context_set_gray_conversion", "pc_context_get_gray_conversion", "pc_float_transfer_table",
     "pc_gray_quantize_weights", "pc_float_transfer_index",
+    "pc_lens_default_model", "pc_lens_build_map", "pc_lens_map_from_stmap", "pc_lens_map_valid", "pc_context_set_lens_map",
+    "pc_context_get_lens_map_size",
     "pc_context_enable_timing", "pc_context_get_timing", "pc_context_get_busy_time", "pc_context_reset_timing",
     "pc_debug_lk_profile", "pc_debug_lk_x86_stats", "pc_debug_detection_paths", "pc_debug_llt9", "pc_debug_lm_decide",
     "pc_debug_live_resources",
@@ -87,6 +89,13 @@ class GrayConversion(C.Structure):
     _fields_ = [("weight_r", C.c_int32), ("weight_g", C.c_int32), ("weight_b", C.c_int32), ("float_table", C.c_void_p)]
 
 
+class LensModel(C.Structure):
+    """pc_lens_model (include/polychase_hip.h)."""
+    _fields_ = [(n, C.c_double) for n in ("fx", "fy", "cx", "cy", "k1", "k2", "k3", "p1", "p2", "zoom")]
+
+
+LENS_FRAC_BITS = 8                            # PC_LENS_FRAC_BITS
+LENS_INVALID = -2 ** 31                       # PC_LENS_INVALID
 TRANSFER_ENTRIES = 20481                      # PC_TRANSFER_ENTRIES
 TRANSFER_KINDS = {"srgb": 1, "gamma": 2}      # PC_TRANSFER_SRGB, PC_TRANSFER_GAMMA
 DEFAULT_GRAY_WEIGHTS = (9798, 19235, 3735)
@@ -171,6 +180,13 @@ def load():
     L.pc_float_transfer_table.argtypes = [C.c_int, C.c_double, C.c_double, vp]
     L.pc_gray_quantize_weights.argtypes = [C.POINTER(C.c_double), C.POINTER(GrayConversion)]
     L.pc_float_transfer_index.argtypes = [vp, C.c_int, vp]
+    L.pc_lens_default_model.argtypes = [C.POINTER(LensModel)]
+    L.pc_lens_default_model.restype = None
+    L.pc_lens_build_map.argtypes = [C.POINTER(LensModel), C.c_int, C.c_int, vp]
+    L.pc_lens_map_from_stmap.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp]
+    L.pc_lens_map_valid.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, ip]
+    L.pc_context_set_lens_map.argtypes = [vp, vp, C.c_int, C.c_int]
+    L.pc_context_get_lens_map_size.argtypes = [vp, ip, ip]
     L.pc_context_stream.restype = vp
     L.pc_context_enable_timing.argtypes = [vp, C.c_int]
     L.pc_context_get_timing.argtypes = [vp, C.c_int, ip, C.POINTER(C.c_double)]
@@ -311,6 +327,47 @@ def float_transfer_table(kind: str, gamma: float = 2.2, exposure: float = 0.0) -
     return out
 
 
+def lens_model(fx, fy, cx, cy, k1=0.0, k2=0.0, k3=0.0, p1=0.0, p2=0.0, zoom=1.0) -> LensModel:
+    """pc_lens_model of the ORIGINAL frames' camera (include/polychase_hip.h has the polynomial)"""
+    return LensModel(*(float(v) for v in (fx, fy, cx, cy, k1, k2, k3, p1, p2, zoom)))
+
+
+def _lens_map_array(q) -> np.ndarray:
+    q = np.asarray(q)
+    if q.dtype != np.int32 or q.ndim != 3 or q.shape[2] != 2:
+        raise ValueError(f"a lens map is int32 (H, W, 2), got {q.dtype} {q.shape}")
+    return np.ascontiguousarray(q)
+
+
+def lens_build_map(model: LensModel, width: int, height: int) -> np.ndarray:
+    """the lens map int32 (H, W, 2) of a polynomial model, on the host (pc_lens_build_map); ValueError for what it refuses"""
+    q = np.empty((max(int(height), 0), max(int(width), 0), 2), np.int32)
+    if load().pc_lens_build_map(C.byref(model), int(width), int(height), q.ctypes.data) != 0:
+        raise ValueError(load().pc_last_error().decode())
+    return q
+
+
+def lens_map_from_stmap(st, flip_v: bool = True) -> np.ndarray:
+    """float32 STmap (H, W, 2) in [0, 1] -> lens map int32 (H, W, 2), on the host (pc_lens_map_from_stmap)"""
+    st = np.asarray(st)
+    if st.dtype != np.float32 or st.ndim != 3 or st.shape[2] != 2:
+        raise ValueError(f"an STmap is float32 (H, W, 2), got {st.dtype} {st.shape}")
+    st = np.ascontiguousarray(st)
+    q = np.empty(st.shape, np.int32)
+    if load().pc_lens_map_from_stmap(st.ctypes.data, st.shape[1], st.shape[0], 1 if flip_v else 0, q.ctypes.data) != 0:
+        raise ValueError(load().pc_last_error().decode())
+    return q
+
+
+def lens_map_valid(q, erode: int = 0) -> np.ndarray:
+    """the validity plane uint8 (H, W), 255 / 0, of a lens map, eroded by `erode` pixels, on the host (pc_lens_map_valid)"""
+    q = _lens_map_array(q)
+    out = np.empty(q.shape[:2], np.uint8)
+    if load().pc_lens_map_valid(q.ctypes.data, q.shape[1], q.shape[0], int(erode), out.ctypes.data, None) != 0:
+        raise ValueError(load().pc_last_error().decode())
+    return out
+
+
 def live_resources() -> tuple[int, int, int, int]:
     """(device allocations, pinned allocations, streams, events) the library's objects own in this process right now
     (pc_debug_live_resources)"""
@@ -372,6 +429,21 @@ class Context:
         table = np.empty(TRANSFER_ENTRIES, np.uint8)
         _check(load().pc_context_get_gray_conversion(self._h, C.byref(c), table.ctypes.data))
         return (c.weight_r, c.weight_g, c.weight_b), (table if c.float_table else None)
+
+    def set_lens_map(self, q=None):
+        """Lens map of the frames put from now on (pc_context_set_lens_map): int32 (H, W, 2), the source position of every
+        undistorted pixel in 1 / 256 px (lens_build_map, lens_map_from_stmap); None clears it."""
+        if q is None:
+            _check(load().pc_context_set_lens_map(self._h, None, 0, 0))
+            return
+        q = _lens_map_array(q)
+        _check(load().pc_context_set_lens_map(self._h, q.ctypes.data, q.shape[1], q.shape[0]))
+
+    def lens_map_size(self) -> tuple:
+        """-> (width, height) of the lens map in force, (0, 0) without one (pc_context_get_lens_map_size)"""
+        w, h = C.c_int(), C.c_int()
+        _check(load().pc_context_get_lens_map_size(self._h, C.byref(w), C.byref(h)))
+        return w.value, h.value
 
     def synchronize(self):
         _check(load().pc_context_synchronize(self._h))

@@ -4,8 +4,10 @@ addon experiences), next to bench.py's HBM-resident number.  Not the headline me
 
   python tools/e2e_bench.py [--config c2|c3] [--frames 60] [--mask-fraction F [--mask-polygon] [--mask-outline N]
                              [--target-mask-margin R]] [--min-correlation V] [--normalize] [--affine]
-                             [--search-radius N] [--mask-windows] [--pan PX]
+                             [--search-radius N] [--mask-windows] [--pan PX] [--lens-k1 K]
 
+--lens-k1 K: OpticalFlowOptions.lens = LensModel(fx = fy = width, centred principal point, k1 = K) of every run, and the same map on
+the context of the per-class pass (the gray kernel and the remap are timed under class "gray").
 Modes: frames as torch CUDA tensors / host numpy arrays (PCIe upload included), with and without the
 SQLite insert.  --mask-fraction F: every run takes detection_mask = a centred rectangle of the frame's aspect covering F of
 its area (1.0: an all-on mask, the masked kernels with nothing masked out); the SQLite modes then also report the mean number
@@ -40,12 +42,14 @@ sys.path.insert(0, ROOT)
 
 
 def per_class_ms(w, h, ml, frames, mask, steps=40, polygons=None, target_margin=-1, min_correlation=0.0, normalize=False, affine=False, search_radius=0,
-                 mask_windows=False):
+                 mask_windows=False, lens_map=None):
     """one pipelined pass (polychase_amd.pipeline.ClipAnalyzer) with every kernel class timed: 20 untimed steps, then `steps`"""
     from polychase_amd import hip
     from polychase_amd.pipeline import ClipAnalyzer
 
     ctx = hip.Context(0)
+    if lens_map is not None:
+        ctx.set_lens_map(lens_map)
     an = ClipAnalyzer(ctx, w, h, 1, len(frames), lambda f: frames[f - 1], hip.gftt_options(), hip.flow_options(max_level=ml))
     if polygons is not None:
         an.an.set_mask_polygons(polygons)
@@ -86,6 +90,7 @@ def main():
     ap.add_argument("--search-radius", type=int, default=0)
     ap.add_argument("--mask-windows", action="store_true")
     ap.add_argument("--pan", type=int, default=0)
+    ap.add_argument("--lens-k1", type=float, default=None, metavar="K")
     a = ap.parse_args()
     import torch
     from polychase_amd import synth
@@ -107,6 +112,10 @@ def main():
     fo.affine_refinement = a.affine
     fo.search_radius = a.search_radius
     fo.mask_windows = a.mask_windows
+    lens_map = None
+    if a.lens_k1 is not None:
+        fo.lens = core.LensModel(float(w), float(w), (w - 1) / 2.0, (h - 1) / 2.0, k1=a.lens_k1)
+        lens_map = fo.lens.build_map(w, h)
     if a.mask_windows and a.mask_fraction is None:
         ap.error("--mask-windows needs a mask (--mask-fraction, optionally --mask-polygon / --mask-outline)")
     vi = core.VideoInfo(w, h, 1, a.frames)
@@ -156,11 +165,13 @@ def main():
         out["mask_windows"] = True
     if a.pan:
         out["pan_px_per_frame"] = a.pan
+    if a.lens_k1 is not None:
+        out["lens_k1"] = a.lens_k1
     if a.frames >= 39:
         out["gpu_ms_per_step"] = per_class_ms(w, h, ml, dev, mask, polygons=polygons,
                                               target_margin=a.target_mask_margin if a.mask_fraction is not None else -1,
                                               min_correlation=a.min_correlation, normalize=a.normalize, affine=a.affine,
-                                              search_radius=a.search_radius, mask_windows=a.mask_windows)
+                                              search_radius=a.search_radius, mask_windows=a.mask_windows, lens_map=lens_map)
     else:
         out["gpu_ms_per_step"] = {"skipped": "the per-class pass needs --frames 39 or more (20 untimed steps, then at least one)"}
     with tempfile.TemporaryDirectory() as td:

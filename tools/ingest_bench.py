@@ -1,13 +1,16 @@
 #!/usr/bin/env python3
 """Frame ingestion through polychase_core: host frames as uint8 RGB, as Blender's float32 RGBA and as
-scene-linear float32 RGB (the uint8 clip through the sRGB EOTF: what an EXR plate holds), no database.
+scene-linear float32 RGB (the uint8 clip through the sRGB EOTF: what an EXR plate holds), or device-resident uint8 RGB
+(uint8_rgb_device: no transfer at all, the GPU side of ingestion alone), no database.
 `POLYCHASE_COPY_THREADS=1` gives the single-threaded copy for comparison.
 
-    python tools/ingest_bench.py [--config c2] [--frames 120] [--clips uint8_rgb,float32_rgba,float32_rgb_linear]
+    python tools/ingest_bench.py [--config c2] [--frames 120] [--clips uint8_rgb,float32_rgba,float32_rgb_linear,uint8_rgb_device]
                                  [--channel-weights R G B] [--float-transfer none|srgb|gamma] [--float-gamma G] [--float-exposure STOPS]
+                                 [--lens-k1 K]
 
 The last four are OpticalFlowOptions' gray conversion (channel_weights, float_transfer, float_transfer_gamma, float_exposure) of
-every run; --repeat N times every clip N times and reports the median with min and max beside it.
+every run; --lens-k1 K is OpticalFlowOptions.lens = LensModel(fx = fy = width, centred principal point, k1 = K): every frame is
+undistorted as it is put; --repeat N times every clip N times and reports the median with min and max beside it.
 """
 import argparse
 import json
@@ -20,7 +23,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "polychase_amd", "core"))
 
-CLIPS = ("uint8_rgb", "float32_rgba", "float32_rgb_linear")
+CLIPS = ("uint8_rgb", "float32_rgba", "float32_rgb_linear", "uint8_rgb_device")
 
 
 def main():
@@ -33,6 +36,7 @@ def main():
     ap.add_argument("--float-transfer", choices=["none", "srgb", "gamma"], default="none")
     ap.add_argument("--float-gamma", type=float, default=2.2)
     ap.add_argument("--float-exposure", type=float, default=0.0)
+    ap.add_argument("--lens-k1", type=float, default=None, metavar="K")
     a = ap.parse_args()
     import numpy as np
     import torch  # noqa: F401
@@ -51,8 +55,14 @@ def main():
         c = np.arange(256) / 255.0
         eotf = np.where(c <= 0.04045, c / 12.92, ((c + 0.055) / 1.055) ** 2.4).astype(np.float32)
         clips["float32_rgb_linear"] = [np.ascontiguousarray(eotf[x]) for x in u8[:12]]
+    if "uint8_rgb_device" in names:
+        import torch
+        clips["uint8_rgb_device"] = [torch.from_numpy(x).cuda() for x in u8]
+        torch.cuda.synchronize()
     fo = core.OpticalFlowOptions()
     fo.max_level = ml
+    if a.lens_k1 is not None:
+        fo.lens = core.LensModel(float(w), float(w), (w - 1) / 2.0, (h - 1) / 2.0, k1=a.lens_k1)
     fo.channel_weights = tuple(a.channel_weights) if a.channel_weights else None
     fo.float_transfer = a.float_transfer
     fo.float_transfer_gamma = a.float_gamma
@@ -63,6 +73,8 @@ def main():
         out["channel_weights"] = a.channel_weights
     if a.float_transfer != "none":
         out["float_transfer"] = {"kind": a.float_transfer, "gamma": a.float_gamma, "exposure": a.float_exposure}
+    if a.lens_k1 is not None:
+        out["lens_k1"] = a.lens_k1
     for name in names:
         frames = clips[name]
         n = len(frames)
@@ -71,13 +83,18 @@ def main():
             t = (fid - 1) % (2 * n - 2)
             return frames[t if t < n else 2 * n - 2 - t]
         core.generate_optical_flow_database(core.VideoInfo(w, h, 1, 20), acc, None, "", core.GFTTOptions(), fo)   # warm-up
-        fps = []
+        fps, fps_run, setup = [], [], []
         for _ in range(max(1, a.repeat)):
             t0 = time.perf_counter()
-            core.generate_optical_flow_database(vi, acc, None, "", core.GFTTOptions(), fo)
-            fps.append(a.frames / (time.perf_counter() - t0))
+            st = core.generate_optical_flow_database(vi, acc, None, "", core.GFTTOptions(), fo)
+            dt = time.perf_counter() - t0
+            fps.append(a.frames / dt)
+            fps_run.append(a.frames / (dt - st.seconds_setup))   # without the per-run set-up (engine, lens map)
+            setup.append(st.seconds_setup)
         med = statistics.median(fps)
-        out[name] = {"fps": med, "host_GBps": med * frames[0].nbytes / 1e9}
+        nbytes = frames[0].nbytes if hasattr(frames[0], "nbytes") else frames[0].numel() * frames[0].element_size()
+        out[name] = {"fps": med, "host_GBps": med * nbytes / 1e9}
+        out[name].update(fps_without_setup=statistics.median(fps_run), seconds_setup=statistics.median(setup))
         if a.repeat > 1:
             out[name].update(fps_min=min(fps), fps_max=max(fps), runs=len(fps))
     print(json.dumps(out))
