@@ -18,7 +18,11 @@ HELPER_LDS_BUDGET = 18 * 1024     # two workgroups of a helper kernel per CU bes
 HELPERS = ["level_kernel", "min_eig_fused_kernelILi0", "min_eig_fused_kernelILi1",
            "min_eig_fused_kernelILi2", "min_eig_fused_kernelILi3", "nms_kernel", "bucket_scatter_kernel", "bucket_sort_kernel", "suppress_sorted_kernel",
            "accept_all_kernel", "accepted_scatter_kernel", "bin_scatter_kernel", "compact_count_kernel", "compact_scatter_kernel",
-           "copy_keypoints_kernel", "lk_gate_kernel"]
+           "copy_keypoints_kernel", "lk_gate_kernel", "bin_count_kernel", "bin_scan_kernel", "unpack_records_kernel"]
+# The small kernels every flow row passes through (kernels_lk.hip; parity: tests/test_lk_rows_gpu.py): allocated VGPRs (granularity
+# 8) and bytes of LDS of the build these limits were written against -- a condition against later growth, not a tuning target
+ROW_KERNELS = {"bin_count_kernel": (8, 0), "bin_scan_kernel": (16, 1024), "bin_scatter_kernel": (8, 0), "compact_count_kernel": (16, 2088),
+               "compact_scatter_kernel": (64, 1024), "unpack_records_kernel": (16, 0), "copy_keypoints_kernel": (8, 0)}
 
 
 def _code_objects(path):
@@ -82,6 +86,20 @@ def test_helper_kernels_fit_beside_three_lk_wavefronts(kernels):
                 assert k[".group_segment_fixed_size"] <= HELPER_LDS_BUDGET, f"{name}: {k['.group_segment_fixed_size']} B of LDS"
                 assert k.get(".private_segment_fixed_size", 0) == 0, f"{name}: spills to scratch"
     assert seen == set(HELPERS), f"kernels not found in the library: {set(HELPERS) - seen}"
+
+
+def test_row_kernels_have_not_grown(kernels):
+    seen = set()
+    for name, k in kernels.items():
+        for h, (vgprs, lds) in ROW_KERNELS.items():
+            if "2pc%d%sE" % (len(h), h) in name:          # the whole mangled name pc::<h>, not a substring of another kernel's
+                seen.add(h)
+                alloc = (k[".vgpr_count"] + 7) // 8 * 8
+                print(h, "VGPRs", k[".vgpr_count"], "allocated", alloc, "LDS", k[".group_segment_fixed_size"])
+                assert alloc <= vgprs, f"{name}: {k['.vgpr_count']} VGPRs, {vgprs} allowed"
+                assert k[".group_segment_fixed_size"] <= lds, f"{name}: {k['.group_segment_fixed_size']} B of LDS, {lds} allowed"
+                assert k.get(".private_segment_fixed_size", 0) == 0, f"{name}: spills to scratch"
+    assert seen == set(ROW_KERNELS), f"kernels not found in the library: {set(ROW_KERNELS) - seen}"
 
 
 def test_lk_kernel_allocation_is_what_the_budget_assumes(kernels):
