@@ -792,6 +792,32 @@ int pc_raycast_pixels(pc_context* ctx, const pc_mesh* mesh, const pc_ray_camera*
 int pc_raycast_pixels_sweep(pc_context* ctx, const pc_mesh* mesh, const pc_ray_camera* cam, const float* xy, int n,
                             int check_mask, uint8_t* hit, float* pos, uint32_t* prim, float* uvt);
 
+/* Mesh render: the mesh as a width x height frame sees it, in one launch and without a pixel list.  Pixel (px, py),
+ * 0 <= px < width, 0 <= py < height, casts exactly the ray pc_raycast_pixels casts for xy = ((float)px, (float)py) -- same
+ * unprojection, same camera, same Moeller-Trumbore; the closest hit wins, among equal t the lowest triangle index -- so pixel
+ * centres sit at integer coordinates, where GFTT puts its keypoints and the polygon masks their pixels.  Three packed planes
+ * (row pitch = width), each may be NULL (not computed, not written), not all three:
+ *   prim   int32: index of the closest triangle, -1 on a miss, WHATEVER the mesh's mask bits say (the ids a caller paints
+ *          masked_triangles with: the addon's triangle-index buffer, blender_addon/operators/pin_mode/masking_3d.py:17-45);
+ *   depth  float32: t of that triangle's hit, 0.0f on a miss: uvt[2] of pc_raycast_pixels with check_mask = 0.  The direction
+ *          is not normalised and its camera-space z is +-1: under a rigid model-view, the distance along the optical axis;
+ *   mask   uint8, 255 / 0: (1) on = hit && !(check_mask && closest triangle masked) -- a masked closest triangle is a miss, not
+ *          a pass-through (ray_casting.cc:104-106): hit[] of pc_raycast_pixels; (2) invert != 0 flips on; (3) the plane is
+ *          eroded by `margin` pixels, 0..PC_TARGET_MASK_MAX_MARGIN, by the choke rule of pc_lk_track_masked (square of
+ *          2 margin + 1 pixels, pixels outside the frame count as on).  Polarity first, erosion second: invert = 0 keeps the
+ *          object `margin` px inside its own silhouette, invert = 1 keeps everything else `margin` px away from it.
+ * Consequence: with invert = 0 every pixel that is on, cast by pc_raycast_pixels (RayCast, the tracker) under the same camera
+ * and check_mask at its integer coordinates, hits.
+ * on_device = 0: host pointers, filled before the call returns.  on_device = 1: device memory of the mesh's GPU, complete when
+ * the call returns -- the call synchronises the context's stream, so another context's stream may read the planes afterwards
+ * (pc_analyzer_set_mask(on_device = 1)).  Scratch (the un-eroded plane; the planes of a host call) lives with the mesh and is
+ * allocated by the first call that needs it.  PC_E_INVALID: a null handle or camera; all three planes NULL; width or height < 1
+ * or > PC_MESH_RENDER_MAX_SIDE; margin outside 0..PC_TARGET_MASK_MAX_MARGIN; mask == NULL with invert or margin set; a context
+ * other than the one the mesh was created in. */
+#define PC_MESH_RENDER_MAX_SIDE 65536
+int pc_mesh_render(pc_context* ctx, const pc_mesh* mesh, const pc_ray_camera* cam, int width, int height, int check_mask,
+                   int invert, int margin, int on_device, int32_t* prim, float* depth, uint8_t* mask);
+
 /* ---- 3D-2D correspondences of the frame being solved, built and kept on the GPU (cpp/tracker.cc:52-97) ----
  * SolveFrame gathers, per source frame that already has a pose, the matches of the flow source -> frame: the
  * source keypoint is cast onto the mesh under the source camera (tracker.cc:64-78), a hit is moved to world space

@@ -17,7 +17,7 @@ LIB_DIR = os.path.join(PKG, "lib")
 OBJ_DIR = os.path.join(PKG, "lib", "obj")
 HIP_DIR = os.path.join(PKG, "csrc", "hip")
 
-HIP_SOURCES = ["kernels_image.hip", "kernels_pyramid.hip", "kernels_gftt.hip", "kernels_mask.hip", "kernels_lens.hip", "kernels_lk.hip", "kernels_lk3.hip", "kernels_lk4a.hip", "kernels_lk4b.hip", "kernels_lk4c.hip", "kernels_lk_fb.hip", "kernels_lk_corr.hip", "kernels_lk_norm.hip", "kernels_lk_affine.hip", "kernels_lk_search.hip", "kernels_lk_wmask.hip", "kernels_tracker.hip", "kernels_lm_debug.hip", "kernels_refiner.hip", "kernels_bvh.hip", "api.hip", "api_lens.hip", "api_lk.hip", "api_analyzer.hip", "api_tracker.hip", "api_comm.hip"]
+HIP_SOURCES = ["kernels_image.hip", "kernels_pyramid.hip", "kernels_gftt.hip", "kernels_mask.hip", "kernels_lens.hip", "kernels_lk.hip", "kernels_lk3.hip", "kernels_lk4a.hip", "kernels_lk4b.hip", "kernels_lk4c.hip", "kernels_lk_fb.hip", "kernels_lk_corr.hip", "kernels_lk_norm.hip", "kernels_lk_affine.hip", "kernels_lk_search.hip", "kernels_lk_wmask.hip", "kernels_tracker.hip", "kernels_lm_debug.hip", "kernels_refiner.hip", "kernels_bvh.hip", "kernels_render.hip", "api.hip", "api_lens.hip", "api_lk.hip", "api_analyzer.hip", "api_tracker.hip", "api_comm.hip"]
 # -ffp-contract=off: the float stages must match the oracle bit-for-bit (no FMA fusion).
 HIP_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-Wall",
              "-Wno-unused-function"]

@@ -36,6 +36,10 @@ struct pc_mesh {
     DevBuf<uint8_t> d_hit;
     DevBuf<float> d_pos, d_uvt;
     DevBuf<uint32_t> d_prim;
+    // pc_mesh_render: the un-eroded plane of a call with a margin; the planes of a call with host pointers.  First use allocates
+    DevBuf<uint8_t> r_plane, r_mask;
+    DevBuf<int32_t> r_prim;
+    DevBuf<float> r_depth;
 };
 
 struct pc_pnp_problem {
@@ -252,6 +256,61 @@ int pc_raycast_pixels(pc_context* ctx, const pc_mesh* mesh, const pc_ray_camera*
 int pc_raycast_pixels_sweep(pc_context* ctx, const pc_mesh* mesh, const pc_ray_camera* cam, const float* xy, int n,
                             int check_mask, uint8_t* hit, float* pos, uint32_t* prim, float* uvt) {
     return raycast_pixels(ctx, mesh, cam, xy, n, check_mask, hit, pos, prim, uvt, true);
+}
+
+int pc_mesh_render(pc_context* ctx, const pc_mesh* mesh_c, const pc_ray_camera* cam, int width, int height, int check_mask, int invert,
+                   int margin, int on_device, int32_t* prim, float* depth, uint8_t* mask) {
+    if (!ctx || !mesh_c || !cam) return fail(PC_E_INVALID, "null argument");
+    if (mesh_c->ctx != ctx) return fail(PC_E_INVALID, "the mesh belongs to another context");
+    if (!prim && !depth && !mask) return fail(PC_E_INVALID, "no plane asked for");
+    if (width < 1 || height < 1 || width > PC_MESH_RENDER_MAX_SIDE || height > PC_MESH_RENDER_MAX_SIDE)
+        return fail(PC_E_INVALID, "frame of %d x %d", width, height);
+    if (margin < 0 || margin > PC_TARGET_MASK_MAX_MARGIN) return fail(PC_E_INVALID, "margin %d outside 0..%d", margin, PC_TARGET_MASK_MAX_MARGIN);
+    if (!mask && (invert || margin)) return fail(PC_E_INVALID, "invert / margin without a mask plane");
+    pc_mesh* mesh = const_cast<pc_mesh*>(mesh_c);
+    PC_HIP(hipSetDevice(ctx->device));
+    const size_t n = (size_t)width * (size_t)height;
+    // where the kernels write: the caller's device planes, or the mesh's scratch in front of a download
+    int32_t* d_prim = prim;
+    float* d_depth = depth;
+    uint8_t* d_mask = mask;
+    if (!on_device) {
+        if (prim) {
+            PC_HIP(mesh->r_prim.ensure(n));
+            d_prim = mesh->r_prim.p;
+        }
+        if (depth) {
+            PC_HIP(mesh->r_depth.ensure(n));
+            d_depth = mesh->r_depth.p;
+        }
+        if (mask) {
+            PC_HIP(mesh->r_mask.ensure(n));
+            d_mask = mesh->r_mask.p;
+        }
+    }
+    uint8_t* d_plane = d_mask;   // the un-eroded plane: the result itself without a margin
+    if (mask && margin > 0) {
+        PC_HIP(mesh->r_plane.ensure(n));
+        d_plane = mesh->r_plane.p;
+    }
+    pc::RayCamera rc;
+    std::memcpy(rc.m, cam->dir_matrix, sizeof(rc.m));
+    std::memcpy(rc.origin, cam->origin, sizeof(rc.origin));
+    rc.fx = cam->fx;
+    rc.fy = cam->fy;
+    rc.cx = cam->cx;
+    rc.cy = cam->cy;
+    rc.sign = cam->unproject_sign;
+    pc::launch_mesh_render(mesh->bvh(), mesh->mask.p, check_mask != 0, rc, width, height, invert != 0, d_prim, d_depth, d_plane, ctx->stream);
+    if (mask && margin > 0) pc::launch_mask_choke(d_plane, d_mask, width, height, margin, ctx->stream);
+    PC_HIP(hipGetLastError());
+    if (!on_device) {
+        if (prim) PC_HIP(hipMemcpyAsync(prim, d_prim, n * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+        if (depth) PC_HIP(hipMemcpyAsync(depth, d_depth, n * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+        if (mask) PC_HIP(hipMemcpyAsync(mask, d_mask, n, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    PC_HIP(hipStreamSynchronize(ctx->stream));
+    return PC_OK;
 }
 
 // ---- correspondence set ----------------------------------------------------------------------

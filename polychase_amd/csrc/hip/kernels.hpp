@@ -435,6 +435,12 @@ void launch_raycast(const BvhView& bvh, const uint32_t* mask, int check_mask, co
 void launch_raycast_sweep(const float* verts, const uint32_t* tris, int n_tris, const uint32_t* mask, int check_mask,
                           const RayCamera& cam, const float2* xy, int n, uint8_t* hit, float* pos, uint32_t* prim,
                           float* uvt, hipStream_t s);
+// ---- kernels_render.hip ----
+// Image-order closest hit, one ray per pixel of a w x h frame, the ray of launch_raycast for xy = (px, py).  Packed planes, each
+// may be null (not written then): prim = closest triangle or -1 and depth = its t or 0, both whatever the triangle mask says;
+// plane = 255 where the pixel is hit and (with check_mask) its closest triangle is not masked, else 0, flipped by `invert`.
+void launch_mesh_render(const BvhView& bvh, const uint32_t* tri_mask, int check_mask, const RayCamera& cam, int w, int h, int invert,
+                        int32_t* prim, float* depth, uint8_t* plane, hipStream_t s);
 // correspondences of one source frame (tracker.cc:52-92): gather + cast + model transform + order-preserving append
 struct CorrModel {
     float m[12];       // rows 0-2 of the model matrix, row-major

@@ -16,6 +16,8 @@
 #include <string>
 #include <vector>
 
+#include "../../../include/polychase_hip.h"
+
 // ---- options -----------------------------------------------------------------------------------
 
 // Shi-Tomasi detector with per-grid-cell quality threshold.  On the HIP path block_size and
@@ -178,8 +180,25 @@ struct PolygonMaskData {
     std::vector<int32_t> counts;    // vertices per polygon
     bool invert = false;
 };
+// Or a mesh under a pose (`mesh` set; the other fields unused): the silhouette pc_mesh_render draws for `cam` at the clip's size,
+// on the mesh's own context, into a device plane of the run -- so the frame's mask is on where a keypoint's ray (RayCast, the
+// tracker) would hit the mesh (invert: where it would not), `margin` pixels inside.  No plane crosses the bus.  The mesh lives on
+// the GPU of its context: a run on another device refuses the mask (std::invalid_argument) before any GPU work.
+struct MeshMaskData {
+    std::shared_ptr<const void> owner;     // keeps the mesh behind `gpu` alive
+    const pc_mesh* gpu = nullptr;
+    pc_context* ctx = nullptr;             // the context the mesh was created in
+    int device = 0;                        // ... and its HIP device
+    pc_ray_camera cam{};
+    bool check_mask = true;
+    bool invert = false;
+    int margin = 0;                        // 0..PC_TARGET_MASK_MAX_MARGIN
+    std::function<void()> sync_mask;       // sends the mesh's current masked_triangles (check_mask), or empty
+                                           // (called on the run's thread: the bits must not be edited while a run uses the mesh)
+};
 struct MaskView {
     std::shared_ptr<const PolygonMaskData> polygons;
+    std::shared_ptr<const MeshMaskData> mesh;
     const uint8_t* data = nullptr;
     int rows = 0;
     int cols = 0;
@@ -198,6 +217,7 @@ struct MaskView {
 struct DetectionMask {
     std::optional<MaskView> fixed;
     std::function<std::optional<MaskView>(int32_t frame_id)> per_frame;
+    int mesh_device = -1;   // >= 0: per_frame may answer with meshes of this device (a run on another refuses before any GPU work)
     bool empty() const { return !fixed && !per_frame; }
 };
 

@@ -25,7 +25,9 @@
 #include "../../../include/polychase_hip.h"
 #include "../../../include/polychase_records.h"
 #include "debug_images.h"
+#include "device_plane_ring.h"
 #include "flow_database.h"
+#include "gpu_context.h"
 #include "utils.h"
 
 namespace {
@@ -35,6 +37,7 @@ constexpr int kRing = 17;      // cpp/opticalflow_thread.h:34-79 (SequentialWrap
 constexpr int kGpuDepth = 3;                        // frame1 jobs kept in flight on the GPU
 constexpr int kWriteBacklog = 4;                    // collected records waiting for SQLite
 constexpr int kMaxJobs = kGpuDepth + kWriteBacklog + 1;  // pinned result slots: a slot is reused kMaxJobs submits later
+constexpr int kMeshPlanes = 4;                      // device planes of a run's mesh masks: the frames put but not yet ingested
 
 [[noreturn]] void ThrowHip(const char* what) {
     throw std::runtime_error(std::string(what) + ": " + pc_last_error());
@@ -391,14 +394,30 @@ static void RunAnalysis(const VideoInfo& video_info, FrameAccessorFunction frame
         }
     }
     const DetectionMask& detection_mask = lens_mask.fixed ? lens_mask : caller_mask;
+    // the device of the run: a rank of the multi-GPU analysis names its GPU itself
+    int device = 0;
+    if (shard && shard->device >= 0) device = shard->device;
+    else if (const char* env = std::getenv("POLYCHASE_DEVICE")) device = std::atoi(env);
+    auto check_mesh_device = [&](int mesh_device) {
+        if (mesh_device != device)
+            throw std::invalid_argument("detection mask: the mesh lives on GPU " + std::to_string(mesh_device) + ", the run is on GPU " +
+                                        std::to_string(device) + " (a mesh mask is rendered where the mesh is)");
+    };
     auto check_mask = [&](const MaskView& m) {
         if (m.polygons) return;   // any size of frame; the engine refuses bad polygons
+        if (m.mesh) {             // rendered at the clip's size
+            if (!m.mesh->gpu || !m.mesh->ctx || m.mesh->margin < 0 || m.mesh->margin > PC_TARGET_MASK_MAX_MARGIN)
+                throw std::invalid_argument("detection mask: a mesh mask needs a mesh and a margin in 0.." + std::to_string(PC_TARGET_MASK_MAX_MARGIN));
+            check_mesh_device(m.mesh->device);
+            return;
+        }
         if (!m.data || m.rows != static_cast<int>(video_info.height) || m.cols != static_cast<int>(video_info.width) ||
             m.row_pitch < static_cast<size_t>(m.cols))
             throw std::invalid_argument("detection mask must be " + std::to_string(video_info.height) + " x " + std::to_string(video_info.width) +
                                         " uint8 (the reference CHECKs CV_8UC1 and the image's size, gftt.cc:22-27)");
     };
     if (detection_mask.fixed) check_mask(*detection_mask.fixed);   // before any GPU work
+    if (detection_mask.mesh_device >= 0) check_mesh_device(detection_mask.mesh_device);
     std::unique_ptr<Database> db;
     if (!database_path.empty()) db = std::make_unique<Database>(database_path, /*bulk_writer=*/true);
     // Bulk load: rows go in under a rollback journal and the file is put back into WAL mode on every way out (done,
@@ -448,10 +467,17 @@ static void RunAnalysis(const VideoInfo& video_info, FrameAccessorFunction frame
 
     // owners of frames the GPU may still be reading; declared BEFORE the engine, i.e. destroyed AFTER it: on every way
     // out (exceptions included) the analyzer has synchronised its streams before a buffer goes back to the pool
+    // (in front of them the planes of the run's mesh masks: their tokens wait among the owners)
+    DevicePlaneRing mesh_planes(
+        kMeshPlanes, static_cast<size_t>(video_info.width) * video_info.height,
+        [device](size_t bytes) {
+            void* p = nullptr;
+            if (pc_peer_buffer_alloc(device, bytes, &p) != PC_OK) ThrowHip("pc_peer_buffer_alloc");
+            return p;
+        },
+        [device](void* p) { pc_peer_buffer_free(device, p); });
+    std::shared_ptr<void> fixed_mesh_plane;   // the token of a run with ONE mesh mask: rendered once, read at every put
     std::deque<std::pair<int32_t, std::shared_ptr<void>>> frames_in_flight;
-    int device = 0;
-    if (shard && shard->device >= 0) device = shard->device;   // a rank of the multi-GPU analysis names its GPU itself
-    else if (const char* env = std::getenv("POLYCHASE_DEVICE")) device = std::atoi(env);
     std::unique_ptr<Engine> engine = EngineCache::Take(device, video_info.width, video_info.height, gopt, fopt);
     const bool engine_reused = engine != nullptr;
     if (!engine) {
@@ -504,17 +530,56 @@ static void RunAnalysis(const VideoInfo& video_info, FrameAccessorFunction frame
     const bool mask_windows = flow_options.mask_windows && !detection_mask.empty();
     if (pc_analyzer_set_mask_windows(eng.an, mask_windows ? 1 : 0) != PC_OK) ThrowHip("pc_analyzer_set_mask_windows");
     // ... and so is the detection mask: the run's one mask, or none until the first frame's is asked for
-    auto set_mask = [&](const std::optional<MaskView>& m) {
+    // A frame handed over as device / pinned memory is read by the GPU after put_frame has returned: its owner is kept
+    // until the analyzer reports the pixels consumed (not "eight newer frames later", which a GPU busy with other work
+    // -- Blender rendering on the same device -- could outlast)
+    auto release_ingested = [&](bool wait) {
+        while (!frames_in_flight.empty()) {
+            if (!pc_analyzer_frame_ingested(eng.an, frames_in_flight.front().first)) {
+                if (!wait) break;
+                std::this_thread::sleep_for(std::chrono::microseconds(50));
+                continue;
+            }
+            frames_in_flight.pop_front();
+        }
+    };
+    // -> the owner that has to wait for the frames put under the mask (a mesh mask: the token of its plane), or nothing
+    auto set_mask = [&](const std::optional<MaskView>& m) -> std::shared_ptr<void> {
         if (m) check_mask(*m);
+        if (m && m->mesh) {
+            // The silhouette, rendered on the mesh's context into a plane of the run: complete when pc_mesh_render returns (it
+            // synchronises that context's stream), so the analyzer's streams may read it.  The plane stays taken until the frames
+            // put under it are ingested.
+            const MeshMaskData& mm = *m->mesh;
+            std::pair<uint8_t*, std::shared_ptr<void>> plane = mesh_planes.Take();
+            while (!plane.first) {   // every plane waits for a frame that is being ingested: the oldest one frees its plane
+                release_ingested(false);
+                plane = mesh_planes.Take();
+                if (!plane.first) std::this_thread::sleep_for(std::chrono::microseconds(50));
+            }
+            {
+                GpuSection section;   // the mesh's context is the process's shared one
+                if (mm.check_mask && mm.sync_mask) mm.sync_mask();
+                if (pc_mesh_render(mm.ctx, mm.gpu, &mm.cam, static_cast<int>(video_info.width), static_cast<int>(video_info.height),
+                                   mm.check_mask ? 1 : 0, mm.invert ? 1 : 0, mm.margin, 1, nullptr, nullptr, plane.first) != PC_OK)
+                    ThrowHip("pc_mesh_render");
+            }
+            if (pc_analyzer_set_mask(eng.an, plane.first, video_info.width, 1) != PC_OK) ThrowHip("pc_analyzer_set_mask");
+            return plane.second;
+        }
         if (m && m->polygons) {
             const PolygonMaskData& p = *m->polygons;
             if (pc_analyzer_set_mask_polygons(eng.an, p.xy.data(), p.counts.data(), static_cast<int>(p.counts.size()), p.invert ? 1 : 0) != PC_OK)
                 ThrowHip("pc_analyzer_set_mask_polygons");
-            return;
+            return nullptr;
         }
         if (pc_analyzer_set_mask(eng.an, m ? m->data : nullptr, m ? m->row_pitch : 0, m && m->on_device ? 1 : 0) != PC_OK) ThrowHip("pc_analyzer_set_mask");
+        return m && m->on_device ? m->owner : nullptr;
     };
-    set_mask(detection_mask.fixed);
+    {
+        std::shared_ptr<void> token = set_mask(detection_mask.fixed);
+        if (detection_mask.fixed && detection_mask.fixed->mesh) fixed_mesh_plane = std::move(token);
+    }
     // the threads that feed this GPU stay on its NUMA node (numa_pin.h): this one for the duration of the call, the writer and its
     // page-write worker (started below / when the database opens its file) for their lives
     numa::ScopedPin near_gpu(eng.ctx, "analysis: calling thread");
@@ -657,19 +722,6 @@ static void RunAnalysis(const VideoInfo& video_info, FrameAccessorFunction frame
         if (stats) *stats = local_stats;
     };
 
-    // A frame handed over as device / pinned memory is read by the GPU after put_frame has returned: its owner is kept
-    // until the analyzer reports the pixels consumed (not "eight newer frames later", which a GPU busy with other work
-    // -- Blender rendering on the same device -- could outlast)
-    auto release_ingested = [&](bool wait) {
-        while (!frames_in_flight.empty()) {
-            if (!pc_analyzer_frame_ingested(eng.an, frames_in_flight.front().first)) {
-                if (!wait) break;
-                std::this_thread::sleep_for(std::chrono::microseconds(50));
-                continue;
-            }
-            frames_in_flight.pop_front();
-        }
-    };
     int32_t highest_put = res_begin - 1;
     Keypoints known;
     for (int32_t frame_id1 = f1_begin; frame_id1 < f1_end; frame_id1++) {
@@ -711,8 +763,9 @@ static void RunAnalysis(const VideoInfo& video_info, FrameAccessorFunction frame
             const bool takes_mask = will_detect || target_margin >= 0 || mask_windows;
             if (takes_mask && detection_mask.per_frame) {
                 std::optional<MaskView> m = detection_mask.per_frame(fid);
-                set_mask(m);
-                if (m && m->on_device) mask_owner = std::move(m->owner);
+                mask_owner = set_mask(m);
+            } else if (takes_mask && detection_mask.fixed && detection_mask.fixed->mesh) {
+                mask_owner = fixed_mesh_plane;
             } else if (takes_mask && detection_mask.fixed && detection_mask.fixed->on_device) {
                 mask_owner = detection_mask.fixed->owner;
             }

@@ -7,6 +7,7 @@
 #include <mutex>
 
 pc_context* SharedGpuContext();  // throws std::runtime_error when no HIP device is usable
+int SharedGpuDevice();           // the HIP device of that context (of the one the next call would create)
 
 // The shared context is ONE HIP stream plus scratch buffers (its own, and the per-mesh ones of pc_mesh), and the C ABI
 // is not thread safe per context.  Python may call ray_cast / AcceleratedMesh / SolvePnP from its thread while a

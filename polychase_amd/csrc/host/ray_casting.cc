@@ -79,6 +79,18 @@ void AcceleratedMesh::RayCastPixels(const SceneTransformations& st, const float*
     }
 }
 
+void AcceleratedMesh::Render(const SceneTransformations& st, int width, int height, bool check_mask, int32_t* triangle_ids, float* depth,
+                             uint8_t* mask, bool invert, int margin) const {
+    GpuSection section;
+    pc_context* ctx = SharedGpuContext();
+    pc_ray_camera cam;
+    MakeRayCamera(st, &cam);
+    SyncMask();   // the mask can be edited through inner_mut(): always send the current bits
+    const int rc = pc_mesh_render(ctx, gpu_, &cam, width, height, check_mask ? 1 : 0, invert ? 1 : 0, margin, 0, triangle_ids, depth, mask);
+    if (rc == PC_E_INVALID) throw std::invalid_argument(std::string("pc_mesh_render: ") + pc_last_error());
+    if (rc != PC_OK) throw std::runtime_error(std::string("pc_mesh_render: ") + pc_last_error());
+}
+
 std::optional<RayHit> RayCast(const AcceleratedMesh& accel_mesh, const SceneTransformations& scene_transform, Vec2f pos,
                               bool check_mask) {
     std::vector<std::optional<RayHit>> hits;

@@ -29,6 +29,13 @@ class AcceleratedMesh {
     void RayCastPixels(const SceneTransformations& scene_transform, const float* xy, size_t n, bool check_mask,
                        std::vector<std::optional<RayHit>>& hits, bool exhaustive = false) const;
 
+    // The mesh as a width x height frame sees it (include/polychase_hip.h: pc_mesh_render): pixel (px, py) casts the ray RayCast
+    // casts for pos = (px, py).  Host planes of width * height elements, each may be null (not all three): triangle_ids (-1 on a
+    // miss, whatever the mask bits say), depth (t, 0 on a miss), mask (255 / 0: hit and -- with check_mask -- not masked, flipped
+    // by invert, eroded by margin).  Sends the current masked_triangles first.
+    void Render(const SceneTransformations& scene_transform, int width, int height, bool check_mask, int32_t* triangle_ids, float* depth,
+                uint8_t* mask = nullptr, bool invert = false, int margin = 0) const;
+
    private:
     Mesh mesh_;
     pc_mesh* gpu_ = nullptr;

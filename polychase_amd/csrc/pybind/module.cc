@@ -23,6 +23,8 @@
 
 #include "../host/numa_pin.h"
 #include "../host/track_sequence.h"
+#include "../host/gpu_context.h"
+#include "../host/ray_casting.h"
 #include "np_helpers.h"
 
 #ifdef PC_WITH_TRACKER
@@ -185,51 +187,141 @@ PolygonMaskPy MakePolygonMask(const py::object& polygons, bool invert) {
     return PolygonMaskPy{std::move(data), py::tuple(kept)};
 }
 
-// array | PolygonMask -> MaskView
-MaskView AnyMaskFromPython(const py::object& obj, const VideoInfo& video_info) {
+// polychase_core.MeshMask(accel_mesh, scene_transforms, check_mask=True, invert=False, margin=0): a detection mask as the
+// silhouette of a mesh under the poses a user has (csrc/host/analysis.h MeshMaskData; the rule: include/polychase_hip.h
+// pc_mesh_render).  scene_transforms: one SceneTransformations (every frame), or a dict {frame_id: SceneTransformations} (a frame
+// without an entry is detected without a mask).  The cameras are made at construction, so a singular view * model is an error
+// here; the object keeps the AcceleratedMesh alive.  With check_mask the mesh's masked_triangles are sent when a frame's mask is
+// rendered, on the run's thread (OpticalFlowThread: without the GIL): they must not be edited through inner_mut() while a run
+// uses the mesh -- the rule TrackerThread already has for its mesh.
+struct MeshMaskPy {
+    std::shared_ptr<const AcceleratedMesh> mesh;
+    std::optional<pc_ray_camera> one;
+    std::map<int32_t, pc_ray_camera> by_frame;
+    bool check_mask = true, invert = false;
+    int margin = 0;
+    int device = 0;
+
+    std::optional<MaskView> View(std::optional<int32_t> frame_id) const {
+        const pc_ray_camera* cam = one ? &*one : nullptr;
+        if (!cam && frame_id) {
+            const auto it = by_frame.find(*frame_id);
+            if (it != by_frame.end()) cam = &it->second;
+        }
+        if (!cam) return std::nullopt;
+        auto data = std::make_shared<MeshMaskData>();
+        data->owner = mesh;
+        data->gpu = mesh->Gpu();
+        data->ctx = SharedGpuContext();
+        data->device = device;
+        data->cam = *cam;
+        data->check_mask = check_mask;
+        data->invert = invert;
+        data->margin = margin;
+        const AcceleratedMesh* m = mesh.get();   // kept alive by `owner`
+        data->sync_mask = [m] { m->SyncMask(); };
+        MaskView v;
+        v.mesh = std::move(data);
+        return v;
+    }
+};
+
+MeshMaskPy MakeMeshMask(std::shared_ptr<const AcceleratedMesh> mesh, const py::object& scene_transforms, bool check_mask, bool invert, int margin) {
+    if (!mesh) throw py::value_error("MeshMask needs an AcceleratedMesh");
+    if (margin < 0 || margin > PC_TARGET_MASK_MAX_MARGIN)
+        throw py::value_error("MeshMask: margin must be in 0.." + std::to_string(PC_TARGET_MASK_MAX_MARGIN) + ", got " + std::to_string(margin));
+    MeshMaskPy out;
+    out.mesh = std::move(mesh);
+    out.check_mask = check_mask;
+    out.invert = invert;
+    out.margin = margin;
+    out.device = SharedGpuDevice();   // the mesh was created on the shared context
+    auto camera_of = [](const py::handle& h) {
+        if (!py::isinstance<SceneTransformations>(h)) throw py::value_error("MeshMask: scene_transforms is a SceneTransformations or a dict {frame_id: SceneTransformations}");
+        pc_ray_camera cam;
+        try {
+            MakeRayCamera(h.cast<const SceneTransformations&>(), &cam);
+        } catch (const std::runtime_error& e) {
+            throw py::value_error(std::string("MeshMask: ") + e.what());
+        }
+        return cam;
+    };
+    if (py::isinstance<py::dict>(scene_transforms)) {
+        for (const auto& kv : py::reinterpret_borrow<py::dict>(scene_transforms)) {
+            if (!py::isinstance<py::int_>(kv.first)) throw py::value_error("MeshMask: the keys of a dict are frame ids");
+            out.by_frame[kv.first.cast<int32_t>()] = camera_of(kv.second);
+        }
+    } else {
+        out.one = camera_of(scene_transforms);
+    }
+    return out;
+}
+
+// array | PolygonMask | MeshMask -> MaskView (a MeshMask of per-frame poses without one for `frame_id`: nothing)
+std::optional<MaskView> AnyMaskFromPython(const py::object& obj, const VideoInfo& video_info, std::optional<int32_t> frame_id) {
     if (py::isinstance<PolygonMaskPy>(obj)) {
         MaskView v;
         v.polygons = obj.cast<const PolygonMaskPy&>().data;
         return v;
     }
+    if (py::isinstance<MeshMaskPy>(obj)) return obj.cast<const MeshMaskPy&>().View(frame_id);
     return MaskFromPython(obj, video_info);
 }
 
-// detection_mask=None | array | PolygonMask | callable(frame_id) -> array | PolygonMask | None | dict {frame_id: PolygonMask |
-// None} (copied here; a missing key = no mask for that frame; an array as a value is refused: a clip of planes does not belong
-// in a dictionary).  `obj` must outlive the run (the callable is called with the GIL from the driver's thread).
-// allow_callable = false: OpticalFlowThread, whose protocol has no mask request -- its per-frame masks come as a dict.
+// detection_mask=None | array | PolygonMask | MeshMask | callable(frame_id) -> array | PolygonMask | MeshMask | None | dict
+// {frame_id: PolygonMask | MeshMask | None} (copied here; a missing key = no mask for that frame; an array as a value is refused:
+// a clip of planes does not belong in a dictionary).  `obj` must outlive the run (the callable is called with the GIL from the
+// driver's thread).
+// allow_callable = false: OpticalFlowThread, whose protocol has no mask request -- its per-frame masks come as a dict, or as a
+// MeshMask of per-frame poses.
 DetectionMask DetectionMaskFromPython(const py::object& obj, const VideoInfo& video_info, bool allow_callable = true) {
     DetectionMask m;
     if (obj.is_none()) return m;
     if (py::isinstance<py::dict>(obj)) {
-        auto table = std::make_shared<std::map<int32_t, std::shared_ptr<const PolygonMaskData>>>();
+        auto table = std::make_shared<std::map<int32_t, MaskView>>();
         for (const auto& kv : py::reinterpret_borrow<py::dict>(obj)) {
             if (!py::isinstance<py::int_>(kv.first)) throw py::value_error("detection_mask: the keys of a dict are frame ids");
             if (kv.second.is_none()) continue;
-            if (!py::isinstance<PolygonMaskPy>(kv.second)) throw py::value_error("detection_mask: the values of a dict are PolygonMask or None");
-            (*table)[kv.first.cast<int32_t>()] = kv.second.cast<const PolygonMaskPy&>().data;
+            const int32_t frame_id = kv.first.cast<int32_t>();
+            if (py::isinstance<MeshMaskPy>(kv.second)) {
+                const MeshMaskPy& mm = kv.second.cast<const MeshMaskPy&>();
+                if (std::optional<MaskView> v = mm.View(frame_id)) (*table)[frame_id] = *v;
+                m.mesh_device = mm.device;
+                continue;
+            }
+            if (!py::isinstance<PolygonMaskPy>(kv.second)) throw py::value_error("detection_mask: the values of a dict are PolygonMask, MeshMask or None");
+            MaskView v;
+            v.polygons = kv.second.cast<const PolygonMaskPy&>().data;
+            (*table)[frame_id] = v;
         }
         m.per_frame = [table](int32_t frame_id) -> std::optional<MaskView> {
             const auto it = table->find(frame_id);
             if (it == table->end()) return std::nullopt;
-            MaskView v;
-            v.polygons = it->second;
-            return v;
+            return it->second;
         };
         return m;
     }
+    if (py::isinstance<MeshMaskPy>(obj)) {
+        const MeshMaskPy mm = obj.cast<const MeshMaskPy&>();   // a copy of our own: the cameras and a reference to the mesh
+        if (mm.one) {
+            m.fixed = mm.View(std::nullopt);
+        } else {
+            m.mesh_device = mm.device;
+            m.per_frame = [mm](int32_t frame_id) { return mm.View(frame_id); };
+        }
+        return m;
+    }
     if (!py::isinstance<PolygonMaskPy>(obj) && PyCallable_Check(obj.ptr())) {
-        if (!allow_callable) throw py::value_error("detection_mask must be a uint8 array of shape (H, W), a PolygonMask, a dict of them or None");
+        if (!allow_callable) throw py::value_error("detection_mask must be a uint8 array of shape (H, W), a PolygonMask, a MeshMask, a dict of them or None");
         m.per_frame = [&obj, video_info](int32_t frame_id) -> std::optional<MaskView> {
             py::gil_scoped_acquire gil;
             const py::object r = obj(frame_id);
             if (r.is_none()) return std::nullopt;
-            return AnyMaskFromPython(r, video_info);
+            return AnyMaskFromPython(r, video_info, frame_id);
         };
         return m;
     }
-    m.fixed = AnyMaskFromPython(obj, video_info);
+    m.fixed = AnyMaskFromPython(obj, video_info, std::nullopt);
     return m;
 }
 
@@ -607,6 +699,19 @@ PYBIND11_MODULE(polychase_core, m) {
         .def(py::init(&MakePolygonMask), py::arg("polygons"), py::arg("invert") = false)
         .def_property_readonly("polygons", [](const PolygonMaskPy& p) { return p.polygons; })
         .def_property_readonly("invert", [](const PolygonMaskPy& p) { return p.data->invert; });
+
+    py::class_<MeshMaskPy>(m, "MeshMask")   // not in the reference
+        .def(py::init(&MakeMeshMask), py::arg("accel_mesh"), py::arg("scene_transforms"), py::arg("check_mask") = true,
+             py::arg("invert") = false, py::arg("margin") = 0)
+        .def_property_readonly("accel_mesh", [](const MeshMaskPy& p) { return std::const_pointer_cast<AcceleratedMesh>(p.mesh); })
+        .def_property_readonly("frame_ids", [](const MeshMaskPy& p) {
+            py::list ids;
+            for (const auto& kv : p.by_frame) ids.append(kv.first);
+            return ids;
+        })
+        .def_property_readonly("check_mask", [](const MeshMaskPy& p) { return p.check_mask; })
+        .def_property_readonly("invert", [](const MeshMaskPy& p) { return p.invert; })
+        .def_property_readonly("margin", [](const MeshMaskPy& p) { return p.margin; });
 
     py::class_<OpticalFlowThread>(m, "OpticalFlowThread")
         .def(py::init([](VideoInfo video_info, std::string database_path, GFTTOptions detector_options, OpticalFlowOptions flow_options,

@@ -313,6 +313,24 @@ void BindTracker(py::module_& m) {
         },
         py::arg("accel_mesh"), py::arg("scene_transform"), py::arg("pos"), py::arg("check_mask"));
 
+    // not in the reference: the headless counterpart of the addon's triangle-index buffer
+    // (blender_addon/operators/pin_mode/masking_3d.py:17-45), include/polychase_hip.h: pc_mesh_render
+    m.def(
+        "render_mesh",
+        [](const AcceleratedMesh& mesh, const SceneTransformations& st, int width, int height, bool check_mask) {
+            if (width < 1 || height < 1) throw py::value_error("render_mesh: width and height must be >= 1");
+            py::array_t<int32_t> ids({static_cast<py::ssize_t>(height), static_cast<py::ssize_t>(width)});
+            py::array_t<float> depth({static_cast<py::ssize_t>(height), static_cast<py::ssize_t>(width)});
+            int32_t* const p_ids = ids.mutable_data();
+            float* const p_depth = depth.mutable_data();
+            {
+                py::gil_scoped_release release;
+                mesh.Render(st, width, height, check_mask, p_ids, p_depth);
+            }
+            return py::make_tuple(ids, depth);
+        },
+        py::arg("accel_mesh"), py::arg("scene_transform"), py::arg("width"), py::arg("height"), py::arg("check_mask") = false);
+
     m.def("find_transformation", [](py::args, py::kwargs) { NotInThisBuild("find_transformation (pin mode)"); });
     m.def(
         "refine_trajectory",

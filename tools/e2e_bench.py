@@ -5,6 +5,16 @@ addon experiences), next to bench.py's HBM-resident number.  Not the headline me
   python tools/e2e_bench.py [--config c2|c3] [--frames 60] [--mask-fraction F [--mask-polygon] [--mask-outline N]
                              [--target-mask-margin R]] [--min-correlation V] [--normalize] [--affine]
                              [--search-radius N] [--mask-windows] [--pan PX] [--lens-k1 K]
+  python tools/e2e_bench.py --mask-mesh [--config c2] [--frames 120]
+
+--mask-mesh: what a mesh mask (polychase_core.MeshMask, DESIGN.md section 4 "Mesh render") costs and saves.  The benchmark's C5 mesh
+(the two-triangle plane) under a pose per frame that covers a quarter of the frame.  "product": frames/s of
+generate_optical_flow_database on device frames without a database -- no mask, the MeshMask, and the same planes as host byte
+masks from a callable (what polychase_core takes from a caller) -- median of three alternating runs each, and keypoints / flow
+rows per frame of a SQLite run with and without the mask.  "pipelined": the driver's loop over the C ABI
+(polychase_amd.pipeline.ClipAnalyzer) with, per frame put, either the caller's equivalent DEVICE byte mask or pc_mesh_render on a
+second context into a device plane followed by the same pc_analyzer_set_mask(on_device = 1) -- the difference is the render plus
+its synchronisation, per step.  Written into profiles/mesh_render.json under "product_<config>".
 
 --lens-k1 K: OpticalFlowOptions.lens = LensModel(fx = fy = width, centred principal point, k1 = K) of every run, and the same map on
 the context of the per-class pass (the gray kernel and the remap are timed under class "gray").
@@ -76,10 +86,159 @@ def per_class_ms(w, h, ml, frames, mask, steps=40, polygons=None, target_margin=
             "ms": {k: round(v[1] / steps, 4) for k, v in t.items()}, "launches": {k: v[0] for k, v in t.items()}}
 
 
+def mask_mesh(a):
+    import ctypes as C
+    import statistics
+
+    import numpy as np
+    import torch
+    from polychase_amd import hip, synth
+    from polychase_amd.pipeline import ClipAnalyzer
+    sys.path.insert(0, os.path.join(ROOT, "polychase_amd", "core"))
+    import polychase_core as core
+
+    w, h, ml = {"c2": (1920, 1080, 3), "c3": (3840, 2160, 4)}[a.config]
+    n = a.frames
+    clip = synth.NoiseClip(w, h, max(n, 30), device="cuda")
+    dev = [clip.frame_torch(t) for t in range(n)]
+    torch.cuda.synchronize()
+    # the C5 plane (tests/c5_endtoend.py), 6 units in front of a camera that drifts a little: half the frame wide and high
+    verts = np.array([[-2, -1.125, 0], [2, -1.125, 0], [2, 1.125, 0], [-2, 1.125, 0]], np.float32)
+    tris = np.array([[0, 1, 2], [0, 2, 3]], np.uint32)
+    f = 0.75 * w
+    origin = lambda fid: np.array([0.004 * fid, -0.002 * fid, -6.0], np.float32)   # noqa: E731
+    intr = core.CameraIntrinsics(fx=f, fy=f, cx=w / 2, cy=h / 2, aspect_ratio=1.0, width=w, height=h, convention=core.CameraConvention.OpenCV)
+
+    def pose(fid):
+        view = np.eye(4, dtype=np.float32)
+        view[:3, 3] = -origin(fid)
+        return core.SceneTransformations(np.eye(4, dtype=np.float32), view, intr)
+
+    mesh = core.AcceleratedMesh(verts, tris)
+    poses = {fid: pose(fid) for fid in range(1, n + 1)}
+    host_planes = {}
+    for fid in range(1, n + 1):
+        ids, _ = core.render_mesh(mesh, poses[fid], w, h)
+        host_planes[fid] = np.where(ids >= 0, 255, 0).astype(np.uint8)
+    out = {"config": a.config, "frames": n, "mesh": "c5_plane", "mask_fraction": float(np.mean([p.mean() / 255.0 for p in host_planes.values()]))}
+    fo = core.OpticalFlowOptions()
+    fo.max_level = ml
+    vi = core.VideoInfo(w, h, 1, n)
+    variants = {"no_mask": lambda: None, "mesh_mask": lambda: core.MeshMask(mesh, poses), "host_byte_mask": lambda: (lambda fid: host_planes[fid])}
+
+    def product(mask, db=""):
+        t0 = time.perf_counter()
+        st = core.generate_optical_flow_database(vi, lambda fid: dev[fid - 1], None, db, core.GFTTOptions(), fo, detection_mask=mask)
+        dt = time.perf_counter() - t0
+        return n / (dt - st.seconds_setup)
+
+    for make in variants.values():   # warm-up: engine, planes, allocations
+        core.generate_optical_flow_database(core.VideoInfo(w, h, 1, 12), lambda fid: dev[fid - 1], None, "", core.GFTTOptions(), fo, detection_mask=make())
+    fps = {k: [] for k in variants}
+    for _ in range(3):
+        for k, make in variants.items():
+            fps[k].append(product(make()))
+    out["product"] = {k: {"fps_median": statistics.median(v), "fps_runs": [round(x, 1) for x in v]} for k, v in fps.items()}
+    import sqlite3
+    with tempfile.TemporaryDirectory() as td:
+        for k in ("no_mask", "mesh_mask"):
+            db = os.path.join(td, k + ".db")
+            product(variants[k](), db)
+            con = sqlite3.connect(db)
+            out["product"][k]["mean_keypoints_per_frame"] = con.execute("select avg(rows) from keypoints").fetchone()[0]
+            out["product"][k]["mean_flow_rows_per_frame"] = con.execute("select sum(rows) from optical_flow").fetchone()[0] / n
+            con.close()
+    core.release_cached_engine()
+
+    # the driver's loop over the C ABI: a caller's device byte mask per frame against the render per frame
+    L = hip.load()
+    VP = C.c_void_p
+
+    class RayCamera(C.Structure):
+        _fields_ = [("dir_matrix", C.c_float * 9), ("origin", C.c_float * 3), ("fx", C.c_float), ("fy", C.c_float),
+                    ("cx", C.c_float), ("cy", C.c_float), ("unproject_sign", C.c_float)]
+
+    L.pc_mesh_create.argtypes = [VP, VP, C.c_int, VP, C.c_int, C.POINTER(VP)]
+    L.pc_mesh_destroy.argtypes = [VP]
+    L.pc_mesh_render.argtypes = [VP, VP, C.POINTER(RayCamera), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, VP, VP, VP]
+    mesh_ctx = hip.Context(0)
+    m = VP()
+    assert L.pc_mesh_create(mesh_ctx._h, verts.ctypes.data_as(VP), 4, tris.ctypes.data_as(VP), 2, C.byref(m)) == 0
+
+    def camera(fid):
+        cam = RayCamera()
+        cam.dir_matrix[:] = [1, 0, 0, 0, 1, 0, 0, 0, 1]
+        cam.origin[:] = [float(v) for v in origin(fid)]
+        cam.fx = cam.fy = f
+        cam.cx, cam.cy, cam.unproject_sign = w / 2, h / 2, 1.0
+        return cam
+
+    planes = {fid: torch.empty((h, w), dtype=torch.uint8, device="cuda:0") for fid in range(1, n + 1)}   # one per frame: none is reused
+    torch.cuda.synchronize()
+
+    def render(fid):
+        cam = camera(fid)
+        assert L.pc_mesh_render(mesh_ctx._h, m, C.byref(cam), w, h, 1, 0, 0, 1, None, None, VP(planes[fid].data_ptr())) == 0, L.pc_last_error()
+
+    for fid in planes:
+        render(fid)
+    assert all(np.array_equal(planes[fid].cpu().numpy(), host_planes[fid]) for fid in (1, n))
+    render_s = [0.0]
+
+    def loop(per_frame):
+        ctx = hip.Context(0)
+        state = {}
+
+        def source(fid):
+            per_frame(state["an"], fid)
+            return dev[fid - 1]
+
+        an = ClipAnalyzer(ctx, w, h, 1, n, source, hip.gftt_options(), hip.flow_options(max_level=ml))
+        state["an"] = an.an
+        an.run(range(1, 21), None, copy=False)
+        ctx.synchronize()
+        render_s[0] = 0.0
+        t0 = time.perf_counter()
+        an.run(range(21, n - 9), None, copy=False)
+        ctx.synchronize()
+        dt = time.perf_counter() - t0
+        an.close()
+        ctx.close()
+        return 1e3 * dt / (n - 9 - 21)
+
+    def with_device_mask(an, fid):
+        an.set_mask(planes[fid])
+
+    def with_render(an, fid):
+        t0 = time.perf_counter()
+        render(fid)
+        render_s[0] += time.perf_counter() - t0
+        an.set_mask(planes[fid])
+
+    ms = {"device_byte_mask": [], "render_per_frame": []}
+    render_ms = []
+    for _ in range(3):
+        ms["device_byte_mask"].append(loop(with_device_mask))
+        ms["render_per_frame"].append(loop(with_render))
+        render_ms.append(1e3 * render_s[0] / (n - 9 - 21))
+    a_ms, b_ms = statistics.median(ms["device_byte_mask"]), statistics.median(ms["render_per_frame"])
+    out["pipelined"] = {"ms_per_step": {k: {"median": statistics.median(v), "runs": [round(x, 4) for x in v]} for k, v in ms.items()},
+                        "render_call_ms_per_step": statistics.median(render_ms), "difference_ms": b_ms - a_ms,
+                        "difference_share_of_step": (b_ms - a_ms) / a_ms}
+    L.pc_mesh_destroy(m)
+    mesh_ctx.close()
+    prof = os.path.join(ROOT, "profiles", "mesh_render.json")
+    doc = json.load(open(prof)) if os.path.exists(prof) else {}
+    doc["product_" + a.config] = out
+    json.dump(doc, open(prof, "w"), indent=1)
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", default="c2")
     ap.add_argument("--frames", type=int, default=300)
+    ap.add_argument("--mask-mesh", action="store_true")
     ap.add_argument("--mask-fraction", type=float, default=None)
     ap.add_argument("--mask-polygon", action="store_true")
     ap.add_argument("--mask-outline", type=int, default=0)
@@ -92,6 +251,8 @@ def main():
     ap.add_argument("--pan", type=int, default=0)
     ap.add_argument("--lens-k1", type=float, default=None, metavar="K")
     a = ap.parse_args()
+    if a.mask_mesh:
+        return mask_mesh(a)
     import torch
     from polychase_amd import synth
     sys.path.insert(0, os.path.join(ROOT, "polychase_amd", "core"))
