@@ -57,7 +57,7 @@ constexpr int CW = TW + 2, CH = TH + 2;   // tile + ring: x0 - 1 .. x0 + 64, y0 
 // box sums are no longer exact and their ORDER shows in the last bit of one pixel in ~10^5.  The oracle's order is this one:
 // rows left to right, then the row sums top to bottom -- 0.0 + h[k] is exact, so (h[k] + h[k + 1]) + h[k + 2] is that order.
 // ------------------------------------------------------------------------------------------------
-constexpr int ME_R = 8;                       // output rows per lane
+constexpr int ME_R = 10;                      // output rows per lane, ME_R + 4 gray rows walked; 16 does not fit the helpers' registers
 constexpr int ME_TW = 64, ME_TH = 2 * ME_R;   // pixels per wavefront: 32 column pairs x 2 bands
 
 // SOBEL is a template parameter, not a launch argument: the extra code of PC_ARITH_SOBEL_FMA took the response kernel from 64
@@ -500,13 +500,17 @@ bool launch_corner_response(const Level& l0, float* eig, float* cov, double* box
 }
 
 // ------------------------------------------------------------------------------------------------
-// K3  threshold (per cell of the NEIGHBOUR) + 3x3 dilate + local-max test.  A workgroup walks a 64 x 64 block as four
-// 64 x 16 tiles of the min-eig map, each staged (already thresholded) in LDS with a 1-px ring; 4 pixels per lane.
+// K3  threshold (per cell of the NEIGHBOUR) + 3x3 dilate + local-max test.  A workgroup takes a 64 x 64 block of the
+// min-eig map in two parts of 64 x 32: a part is staged (already thresholded) in LDS with a 1-px ring -- 9 KB, a ring of
+// 196 positions per part where 64 x 16 tiles staged one after the other read 164 each -- then two rows of 4 pixels per lane.
 // Writes the candidate byte of EVERY pixel (so the map needs no clearing between frames) and appends keys =
 // ordered(value) << 32 | (y*w + x) with ONE global atomic per workgroup: appends to one counter from different CUs
 // cost ~23 ns each and serialise (a 64 x 16 workgroup per atomic took 0.19 ms at 4K for that reason alone).
 // ------------------------------------------------------------------------------------------------
-constexpr int NMS_SUB = 4;   // 64 x 16 tiles per workgroup
+constexpr int NMS_SUB = 4;    // 64 x 16 tiles per workgroup
+constexpr int NMS_PART = 2;   // tiles staged together (the helpers' LDS budget holds 34 of the block's 66 rows beside the thresholds)
+// a part + ring (34 rows) crosses at most this many boundaries of cells that are at least CH rows high
+constexpr int kNmsPartBoundaries = (NMS_PART * TH + 1) / CH + 1;
 
 // Bucket of a candidate for the sort (K4): the ordered-uint image of a float is monotone and piecewise linear in
 // log(value), so equal slices of it hold similar numbers of corner responses (measured on the benchmark clips with
@@ -546,8 +550,8 @@ __global__ __launch_bounds__(256) void nms_kernel(const float* __restrict__ eig,
                                                   int hi_prio, const uint8_t* __restrict__ mask) {
     helper_priority(hi_prio);
     __shared__ float s_thr[kMaxGridCells];
-    __shared__ uint32_t s_hi, s_lo;
-    __shared__ float s_v[CH][CW + 2];
+    __shared__ uint32_t s_hi, s_lo, s_neg;            // s_neg: some cell's threshold has its sign bit set
+    __shared__ float s_v[NMS_PART * TH + 2][CW + 2];  // a part's thresholded values + a 1-px ring
     __shared__ uint32_t s_wave[4];
     __shared__ uint32_t s_base;
     const int tid = threadIdx.x;
@@ -556,6 +560,7 @@ __global__ __launch_bounds__(256) void nms_kernel(const float* __restrict__ eig,
     if (tid == 0) {
         s_hi = 0u;
         s_lo = 0xffffffffu;
+        s_neg = 0u;
     }
     __syncthreads();
     for (int i = tid; i < ncells; i += 256) {
@@ -565,6 +570,7 @@ __global__ __launch_bounds__(256) void nms_kernel(const float* __restrict__ eig,
         // value range of the candidates (bucket sort, see bucket_of): above the smallest threshold, up to the largest maximum
         atomicMax(&s_hi, cell_max[i]);
         atomicMin(&s_lo, float_to_ordered(s_thr[i] > 0.f ? s_thr[i] : 0.f));
+        if (__float_as_uint(s_thr[i]) >> 31) atomicOr(&s_neg, 1u);
     }
     __syncthreads();
     const SortRange range = make_sort_range(s_lo, s_hi);
@@ -581,104 +587,163 @@ __global__ __launch_bounds__(256) void nms_kernel(const float* __restrict__ eig,
     for (int i = (blockIdx.y * gridDim.x + blockIdx.x) * 256 + tid; i < zero_words; i += gridDim.x * gridDim.y * 256) zero[i] = 0u;
     const int r = tid >> 4, q = tid & 15;
     const int x = x0 + 4 * q;
+    const bool in_x = x < w;
+    const bool quad = x + 3 < w && (w & 3) == 0;      // the lane's four pixels are one aligned 16-byte (map) / 4-byte (state, mask) access
+    // A staged part + ring spans at most two grid cells across and three down when the cells are at least a tile + ring large:
+    // the cell of a position is then a comparison with the next cell boundaries, not a division (block-uniform).
+    const bool big_cells = g.cell_w >= CW && g.cell_h >= CH;
+    const int ccx0 = max(x0 - 1, 0) / g.cell_w, bx = (ccx0 + 1) * g.cell_w;
     uint32_t flags = 0;                 // bit 4 * sub + i: pixel i of this lane's quad in tile `sub` is a candidate
-    float vals[NMS_SUB][4];
-#pragma unroll
-    for (int sub = 0; sub < NMS_SUB; sub++) {
-        const int y0 = (blockIdx.y * NMS_SUB + sub) * TH;
-        const int y = y0 + r;
-        __syncthreads();   // s_thr is complete / the previous tile's readers are done
-        // thresholded values; outside the image: 0 (cv::dilate ignores those positions, and a candidate is > 0).
-        // A tile + ring spans at most two grid cells per axis when the cells are at least that large: the cell of a
-        // position is then a comparison with the next cell boundary, not a division.
-        const bool big_cells = g.cell_w >= CW && g.cell_h >= CH;
-        const int ccx0 = max(x0 - 1, 0) / g.cell_w, ccy0 = max(y0 - 1, 0) / g.cell_h;     // block-uniform
-        const int bx = (ccx0 + 1) * g.cell_w, by = (ccy0 + 1) * g.cell_h;
-        auto thr_at = [&](int ax, int ay) -> float {
-            const int cx = big_cells ? ccx0 + (ax >= bx) : ax / g.cell_w;
-            const int cy = big_cells ? ccy0 + (ay >= by) : ay / g.cell_h;
-            return s_thr[cy * g.cols + cx];
-        };
-        if (y0 < h) {
-            // interior of the tile: one aligned float4 per lane where the row length allows it
-            float v[4] = {0.f, 0.f, 0.f, 0.f};
-            if (y < h && x < w) {
-                const float* row = eig + (size_t)y * w;
-                if (x + 3 < w && (w & 3) == 0) {
-                    const float4 e = *reinterpret_cast<const float4*>(row + x);
-                    v[0] = e.x; v[1] = e.y; v[2] = e.z; v[3] = e.w;
-                } else {
-                    for (int i = 0; i < 4 && x + i < w; i++) v[i] = row[x + i];
-                }
-#pragma unroll
-                for (int i = 0; i < 4; i++) v[i] = (x + i < w && v[i] > thr_at(x + i, y)) ? v[i] : 0.f;
-            }
-#pragma unroll
-            for (int i = 0; i < 4; i++) s_v[r + 1][4 * q + 1 + i] = v[i];
-            // ring: top and bottom rows (CW each), left and right columns (TH each)
-            if (tid < 2 * CW + 2 * TH) {
-                int cx, cy;
-                if (tid < 2 * CW) {
-                    cy = tid < CW ? 0 : CH - 1;
-                    cx = tid < CW ? tid : tid - CW;
-                } else {
-                    const int k = tid - 2 * CW;
-                    cy = 1 + (k >> 1);
-                    cx = (k & 1) ? CW - 1 : 0;
-                }
-                const int ax = x0 - 1 + cx, ay = y0 - 1 + cy;
-                float e = 0.f;
-                if (ax >= 0 && ax < w && ay >= 0 && ay < h) {
-                    e = eig[(size_t)ay * w + ax];
-                    e = (e > thr_at(ax, ay)) ? e : 0.f;
-                }
-                s_v[cy][cx] = e;
-            }
-        }
-        __syncthreads();
-#pragma unroll
-        for (int i = 0; i < 4; i++) vals[sub][i] = 0.f;
-        if (y < h && x < w) {
+    // The stencil of one tile, compiled twice.  ORDERED: no threshold of the frame is negative, so every staged value is +0 or
+    // positive and floats compare as their bit patterns -- a 3 x 3 maximum is then two and a half v_max3_u32 per pixel, where the
+    // float form (cv::dilate's `a > b ? a : b`, kept for frames with a negative threshold: Harris responses) takes a compare and a
+    // select per pair.  Same decisions: equal bits <=> equal values here, and zero is the all-zero pattern.
+    auto stencil = [&](auto ordered_tag, auto sub_tag, const bool any_value) {
+        constexpr bool ORDERED = decltype(ordered_tag)::value;
+        constexpr int sub = decltype(sub_tag)::value, lr = (sub % NMS_PART) * TH;   // lr: the tile's first row in s_v, less the ring
+        using T = std::conditional_t<ORDERED, uint32_t, float>;
+        const int y = (blockIdx.y * NMS_SUB + sub) * TH + r;
+        if (!(y < h && in_x)) return;
+        uint32_t f4 = 0;
+        if (any_value) {
+            const T(*sv)[CW + 2] = reinterpret_cast<const T(*)[CW + 2]>(s_v);
             // column maxima of the three rows for columns x - 1 .. x + 4
-            float cm[6];
+            T cm[6];
 #pragma unroll
             for (int i = 0; i < 6; i++) {
-                const float a = s_v[r][4 * q + i], b = s_v[r + 1][4 * q + i], c = s_v[r + 2][4 * q + i];
-                const float m = a > b ? a : b;
-                cm[i] = m > c ? m : c;
+                const T a = sv[lr + r][4 * q + i], b = sv[lr + r + 1][4 * q + i], c = sv[lr + r + 2][4 * q + i];
+                if constexpr (ORDERED) {
+                    cm[i] = max(max(a, b), c);
+                } else {
+                    const T m = a > b ? a : b;
+                    cm[i] = m > c ? m : c;
+                }
             }
-            uint32_t f4 = 0;
             uint32_t on = 0xfu;            // bit i: pixel i of the quad may be a candidate
             if (MASKED) {
                 const uint8_t* mk = mask + (size_t)y * w + x;
                 uint32_t m4 = 0;           // the quad's four mask bytes
-                if (x + 3 < w && ((w & 3) == 0)) {
+                if (quad) {
                     m4 = *reinterpret_cast<const uint32_t*>(mk);
                 } else {
                     for (int i = 0; i < 4 && x + i < w; i++) m4 |= (uint32_t)mk[i] << (8 * i);
                 }
                 on = ((m4 & 0xffu) ? 1u : 0u) | ((m4 & 0xff00u) ? 2u : 0u) | ((m4 & 0xff0000u) ? 4u : 0u) | ((m4 & 0xff000000u) ? 8u : 0u);
             }
+            if (!(y >= 1 && y < h - 1)) on = 0u;
 #pragma unroll
             for (int i = 0; i < 4; i++) {
-                const float val = s_v[r + 1][4 * q + 1 + i];
-                float m = cm[i] > cm[i + 1] ? cm[i] : cm[i + 1];
-                m = m > cm[i + 2] ? m : cm[i + 2];
-                const int xi = x + i;
-                if (val != 0.f && val == m && xi >= 1 && xi < w - 1 && y >= 1 && y < h - 1 && (!MASKED || ((on >> i) & 1u))) {
-                    f4 |= 1u << i;
-                    vals[sub][i] = val;
+                const T val = sv[lr + r + 1][4 * q + 1 + i];
+                T m;
+                if constexpr (ORDERED) {
+                    m = max(max(cm[i], cm[i + 1]), cm[i + 2]);
+                } else {
+                    m = cm[i] > cm[i + 1] ? cm[i] : cm[i + 1];
+                    m = m > cm[i + 2] ? m : cm[i + 2];
                 }
+                const int xi = x + i;
+                if (val != (T)0 && val == m && xi >= 1 && xi < w - 1 && ((on >> i) & 1u)) f4 |= 1u << i;
             }
             flags |= f4 << (4 * sub);
-            uint8_t* cs = cstate + (size_t)y * w + x;
-            if (x + 3 < w && ((w & 3) == 0)) {
-                *reinterpret_cast<uint32_t*>(cs) = (f4 & 1u) | ((f4 & 2u) << 7) | ((f4 & 4u) << 14) | ((f4 & 8u) << 21);
+        }
+        uint8_t* cs = cstate + (size_t)y * w + x;
+        if (quad) {
+            *reinterpret_cast<uint32_t*>(cs) = (f4 & 1u) | ((f4 & 2u) << 7) | ((f4 & 4u) << 14) | ((f4 & 8u) << 21);
+        } else {
+            for (int i = 0; i < 4 && x + i < w; i++) cs[i] = (uint8_t)((f4 >> i) & 1u);
+        }
+    };
+    // The block in parts of NMS_PART tiles (what the helpers' LDS holds): staged, then its tiles' stencils.
+    auto part = [&](auto part_tag) {
+        constexpr int P = decltype(part_tag)::value;
+        const int yp = (blockIdx.y * NMS_SUB + P * NMS_PART) * TH;        // first row of the part
+        if (yp >= h) return;               // block-uniform: no row of the part is in the image
+        const int cyb = max(yp - 1, 0) / g.cell_h;   // cell row of the part's top ring row
+        auto thr_at = [&](int ax, int ay) -> float { // any in-image position of the part + ring
+            int cx, cy;
+            if (big_cells) {
+                cx = ccx0 + (ax >= bx);
+                cy = cyb;
+#pragma unroll
+                for (int k = 1; k <= kNmsPartBoundaries; k++) cy += ay >= (cyb + k) * g.cell_h;
             } else {
-                for (int i = 0; i < 4 && x + i < w; i++) cs[i] = (uint8_t)((f4 >> i) & 1u);
+                cx = ax / g.cell_w;
+                cy = ay / g.cell_h;
+            }
+            return s_thr[cy * g.cols + cx];
+        };
+        if (P > 0) __syncthreads();        // the previous part's readers are done
+        // staging: the thresholded values of the part + ring; outside the image: 0 (cv::dilate ignores those positions, and
+        // a candidate is > 0).  `nz`: any non-zero value staged by this lane.
+        uint32_t nz = 0u;
+#pragma unroll
+        for (int t = 0; t < NMS_PART; t++) {
+            const int y0 = yp + t * TH;
+            const int y = y0 + r;
+            float v[4] = {0.f, 0.f, 0.f, 0.f};
+            if (y < h && in_x) {
+                const float* row = eig + (size_t)y * w;
+                if (quad) {
+                    const float4 e = *reinterpret_cast<const float4*>(row + x);
+                    v[0] = e.x; v[1] = e.y; v[2] = e.z; v[3] = e.w;
+                } else {
+                    for (int i = 0; i < 4 && x + i < w; i++) v[i] = row[x + i];
+                }
+                if (big_cells) {
+                    // the row's two cells (one, mostly): two thresholds per quad, a select per pixel.  Pixels past the image
+                    // are 0 and stay 0 under either threshold (0 > thr passes only to give 0 again).
+                    const int ccy0 = max(y0 - 1, 0) / g.cell_h;                               // block-uniform
+                    const float* trow = &s_thr[(ccy0 + (y >= (ccy0 + 1) * g.cell_h)) * g.cols + ccx0];
+                    const float t_lo = trow[0], t_hi = trow[min(x + 3, w - 1) >= bx ? 1 : 0];
+#pragma unroll
+                    for (int i = 0; i < 4; i++) v[i] = v[i] > (x + i >= bx ? t_hi : t_lo) ? v[i] : 0.f;
+                } else {
+#pragma unroll
+                    for (int i = 0; i < 4; i++) v[i] = (x + i < w && v[i] > thr_at(x + i, y)) ? v[i] : 0.f;
+                }
+            }
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+                s_v[t * TH + r + 1][4 * q + 1 + i] = v[i];
+                nz |= __float_as_uint(v[i]) << 1;      // -0.0 (a negative threshold lets it pass) counts as zero
             }
         }
-    }
+        // ring: the rows above and below the part (CW each), the columns left and right of it (NMS_PART * TH each): 196
+        // positions, one pass -- tile by tile it was 164 per tile
+        static_assert(2 * CW + 2 * NMS_PART * TH <= 256, "one ring position per lane");
+        if (tid < 2 * CW + 2 * NMS_PART * TH) {
+            int cx, cy;
+            if (tid < 2 * CW) {
+                cy = tid < CW ? 0 : NMS_PART * TH + 1;
+                cx = tid < CW ? tid : tid - CW;
+            } else {
+                const int j = tid - 2 * CW;
+                cy = 1 + (j >> 1);
+                cx = (j & 1) ? CW - 1 : 0;
+            }
+            const int ax = x0 - 1 + cx, ay = yp - 1 + cy;
+            float e = 0.f;
+            if (ax >= 0 && ax < w && ay >= 0 && ay < h) {
+                e = eig[(size_t)ay * w + ax];
+                e = (e > thr_at(ax, ay)) ? e : 0.f;
+            }
+            s_v[cy][cx] = e;
+            nz |= __float_as_uint(e) << 1;
+        }
+        // A part in which nothing passed its threshold has no candidate: its state bytes are written and that is all (a frame
+        // whose corners sit in a few places leaves most blocks here).  Also the barrier between staging and the stencils.
+        const bool any_value = __syncthreads_or(nz != 0u) != 0;
+        auto tiles = [&](auto ordered_tag) {
+            stencil(ordered_tag, std::integral_constant<int, P * NMS_PART>{}, any_value);
+            stencil(ordered_tag, std::integral_constant<int, P * NMS_PART + 1>{}, any_value);
+        };
+        static_assert(NMS_PART == 2, "two stencils per part");
+        if (s_neg == 0u) tiles(std::true_type{});
+        else tiles(std::false_type{});
+    };
+    part(std::integral_constant<int, 0>{});
+    part(std::integral_constant<int, 1>{});
+    static_assert(NMS_SUB == 2 * NMS_PART, "two parts per block");
     // workgroup-aggregated append
     const int lane = tid & 63, wave = tid >> 6;
     const uint32_t cnt = (uint32_t)__popc(flags);
@@ -698,30 +763,28 @@ __global__ __launch_bounds__(256) void nms_kernel(const float* __restrict__ eig,
     if (cnt != 0) {
         uint32_t pos = s_base + incl - cnt;
         for (int wv = 0; wv < wave; wv++) pos += s_wave[wv];
-#pragma unroll
-        for (int sub = 0; sub < NMS_SUB; sub++) {
-            const int y = (blockIdx.y * NMS_SUB + sub) * TH + r;
-#pragma unroll
-            for (int i = 0; i < 4; i++) {
-                if (flags & (1u << (4 * sub + i))) {
-                    const uint32_t ord = float_to_ordered(vals[sub][i]);
-                    if (pos < cap) {
-                        const unsigned long long key = ((unsigned long long)ord << 32) | (unsigned long long)(uint32_t)(y * w + x + i);
-                        const uint32_t b = bucket_of(ord, range);
-                        if (slots) {
-                            // straight into the bucket (no scatter launch); past its slots the bucket is flagged by the
-                            // sort, the frame is redone on the slow path and the suppression decides nothing (keys past
-                            // the slots are lost here); the last slot keeps a valid key for the launches behind it
-                            const uint32_t at = atomicAdd(&hist[b], 1u);
-                            slots[(size_t)b * kBucketSlots + min(at, (uint32_t)kBucketSlots - 1u)] = key;
-                        } else {
-                            keys[pos] = key;
-                            atomicAdd(&hist[b], 1u);
-                        }
-                    }
-                    pos++;
+        // The lane's candidates in the order of their bits (tile, then pixel).  One pass per candidate of the lane that has
+        // the most -- three or four on a busy frame -- where a pass per bit of `flags` ran all sixteen whenever any lane of the
+        // wavefront had that bit; a candidate's value is read back from the map (it passed its threshold unchanged).
+        for (uint32_t todo = flags; todo != 0u; todo &= todo - 1u) {
+            const int bit = __ffs((int)todo) - 1;
+            const uint32_t idx = (uint32_t)(((blockIdx.y * NMS_SUB + (bit >> 2)) * TH + r) * w + x + (bit & 3));
+            const uint32_t ord = float_to_ordered(eig[idx]);
+            if (pos < cap) {
+                const unsigned long long key = ((unsigned long long)ord << 32) | (unsigned long long)idx;
+                const uint32_t b = bucket_of(ord, range);
+                if (slots) {
+                    // straight into the bucket (no scatter launch); past its slots the bucket is flagged by the
+                    // sort, the frame is redone on the slow path and the suppression decides nothing (keys past
+                    // the slots are lost here); the last slot keeps a valid key for the launches behind it
+                    const uint32_t at = atomicAdd(&hist[b], 1u);
+                    slots[(size_t)b * kBucketSlots + min(at, (uint32_t)kBucketSlots - 1u)] = key;
+                } else {
+                    keys[pos] = key;
+                    atomicAdd(&hist[b], 1u);
                 }
             }
+            pos++;
         }
     }
     // K4, first step: the workgroup that finishes last turns the bucket counts into bucket offsets (descending value)
@@ -935,7 +998,7 @@ __device__ __forceinline__ bool suppress_decide(const unsigned long long* __rest
     const uint32_t i = blockIdx.x * SUP_BLOCK + threadIdx.x;
     const bool live = i < n;
     uint32_t my_val = 0, my_idx = 0;
-    uint32_t nb[SUP_NB];
+    uint32_t nb[SUP_NB] = {};   // slots 0 .. n_nb - 1 are valid
     int n_nb = 0;
     bool overflow = false;
     int x = 0, y = 0;
@@ -946,29 +1009,36 @@ __device__ __forceinline__ bool suppress_decide(const unsigned long long* __rest
         y = (int)(my_idx / (uint32_t)w);
         x = (int)(my_idx - (uint32_t)y * (uint32_t)w);
         // The neighbourhood (the offsets table: dx^2 + dy^2 < min_distance^2) row by row: row dy spans |dx| <= row_hw[dy + R].
-        // Its state bytes are read as aligned dwords -- ~40 independent loads per lane for min_distance 5 where the
+        // Its state bytes are read as aligned dwords -- ~40 loads per lane for min_distance 5 where the
         // offset-by-offset walk made 80 byte loads, each behind a branch.  Plain loads: "is a candidate" (non-zero) never
         // changes during this kernel, and a byte that changes 1 -> 2 / 3 under the load stays non-zero.
         for (int dy = -R; dy <= R; dy++) {
             const int ny = y + dy, hw = row_hw[dy + R];
             if (ny < 0 || ny >= h || hw < 0) continue;
             const uint32_t lin0 = (uint32_t)(ny * w + max(x - hw, 0)), lin1 = (uint32_t)(ny * w + min(x + hw, w - 1));
-            for (uint32_t a = lin0 & ~3u; a <= lin1; a += 4u) {
-                uint32_t v = *reinterpret_cast<const uint32_t*>(cstate + a);
-                // bytes of this dword outside [lin0, lin1]
-                if (a < lin0) v &= 0xffffffffu << (8u * (lin0 - a));
-                if (a + 3u > lin1) v &= 0xffffffffu >> (8u * (a + 3u - lin1));
-                while (v) {
-                    const uint32_t b = (uint32_t)(__ffs((int)v) - 1) >> 3;
-                    v &= ~(0xffu << (8u * b));
-                    const uint32_t nidx = a + b;
+            // 16 bytes at a time: the (up to) four dwords are loaded together -- one trip to memory per row of a 5-px radius,
+            // where a dword per trip made three or four -- and folded into one bit per byte; one loop then walks the set bits
+            for (uint32_t a0 = lin0 & ~3u; a0 <= lin1; a0 += 16u) {
+                uint32_t vv[4];
+#pragma unroll
+                for (int j = 0; j < 4; j++) vv[j] = a0 + 4u * j <= lin1 ? *reinterpret_cast<const uint32_t*>(cstate + a0 + 4u * j) : 0u;
+                uint32_t m = 0;   // bit k: byte a0 + k is a candidate (a state byte is 0 .. 3: non-zero <=> one of its two low bits)
+#pragma unroll
+                for (int j = 0; j < 4; j++) m |= ((((vv[j] | (vv[j] >> 1)) & 0x01010101u) * 0x01020408u) >> 24 & 0xfu) << (4 * j);
+                // bytes outside [lin0, lin1]
+                if (a0 < lin0) m &= 0xffffu << (lin0 - a0);
+                if (a0 + 15u > lin1) m &= 0xffffu >> (a0 + 15u - lin1);
+                for (; m != 0u; m &= m - 1u) {
+                    const uint32_t nidx = a0 + (uint32_t)(__ffs((int)m) - 1);
                     if (nidx == my_idx) continue;
                     const uint32_t nval = float_to_ordered(eig[nidx]);
                     if (!(nval > my_val || (nval == my_val && nidx > my_idx))) continue;  // lower priority
                     if (n_nb < SUP_NB) {
+                        // pushed at the front (the order of the cached neighbours is free): 12 moves, where selecting slot
+                        // n_nb took a compare and a select per slot
 #pragma unroll
-                        for (int k = 0; k < SUP_NB; k++)
-                            if (k == n_nb) nb[k] = nidx;
+                        for (int k = SUP_NB - 1; k > 0; k--) nb[k] = nb[k - 1];
+                        nb[0] = nidx;
                         n_nb++;
                     } else {
                         overflow = true;

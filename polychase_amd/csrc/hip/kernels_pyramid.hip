@@ -27,7 +27,6 @@ constexpr int CW = TW + 2, CH = TH + 2;           // + 1-px halo for the Scharr 
 constexpr int C_X0 = 3;                           // LDS column of the halo column x0 - 1 (interior starts 4-byte aligned)
 constexpr int C_PITCH = 72;
 constexpr int P_H = 2 * TH + 7;                   // parent rows a tile + halo needs (5x5 taps, stride 2)
-constexpr int P_PITCH = 144;                      // parent bytes per row: 2 * (TW + 4) + 8, loaded as 36 dwords
 constexpr int H_Q = (CW + 3) / 4;                 // horizontal pass: quads of outputs per row (17)
 constexpr int H_PITCH = 4 * H_Q;                  // uint16 per row (68)
 
@@ -84,7 +83,6 @@ template <int SRC>
 __global__ __launch_bounds__(256) void level_kernel(const LevelSource in, const Level out, const int win, int hi_prio) {
     helper_priority(hi_prio);
     __shared__ __attribute__((aligned(16))) uint8_t s_c[CH][C_PITCH];           // the level's tile + halo
-    __shared__ __attribute__((aligned(16))) uint8_t s_p[SRC == SRC_PYR ? P_H : 1][P_PITCH];
     __shared__ __attribute__((aligned(16))) uint16_t s_h[SRC == SRC_PYR ? P_H : 1][H_PITCH];
 
     const int tid = threadIdx.x;
@@ -98,20 +96,20 @@ __global__ __launch_bounds__(256) void level_kernel(const LevelSource in, const 
     // ---- phase A: every in-image pixel of [x0 - 1, x0 + TW] x [y0 - 1, y0 + TH] into s_c ----
     if constexpr (SRC == SRC_PYR) {
         const Level& P = in.parent;
-        const int px0 = 2 * x0 - 4, py0 = 2 * y0 - 4;     // parent position of s_p[0][0]; px0 is 4-byte aligned
+        const int px0 = 2 * x0 - 4, py0 = 2 * y0 - 4;     // parent position of the first byte the tile reads; px0 is 4-byte aligned
         const int ymin = -win, ymax = P.h + win - 1, xmax = P.pitch - kPadX - 4;
-        for (int i = tid; i < P_H * (P_PITCH / 4); i += 256) {
-            const int r = i / (P_PITCH / 4), d = i - r * (P_PITCH / 4);
-            // clamped positions are never consumed by an in-image output (they lie beyond the parent's 2-px reach)
-            const int yy = min(max(py0 + r, ymin), ymax), xx = min(px0 + 4 * d, xmax);
-            *reinterpret_cast<uint32_t*>(&s_p[r][4 * d]) = *reinterpret_cast<const uint32_t*>(P.img + (ptrdiff_t)yy * P.pitch + xx);
-        }
-        __syncthreads();
-        // horizontal [1 4 6 4 1] at stride 2: output c (level column x0 - 1 + c) reads parent bytes 2c .. 2c + 4 of the row
+        // horizontal [1 4 6 4 1] at stride 2, straight from the parent plane: output c (level column x0 - 1 + c) reads parent bytes
+        // 2c .. 2c + 4 of the row, a quad of outputs the three aligned dwords at bytes 8q .. 8q + 11.  (Staging the parent rows in
+        // LDS first -- 39 rows of 36 dwords -- cost a pass of address arithmetic and a barrier to save half a dword load per
+        // output: the quads' dwords overlap by one in three, and the L1 serves that.)
         for (int i = tid; i < P_H * H_Q; i += 256) {
             const int r = i / H_Q, q = i - r * H_Q;
-            const uint32_t* p = reinterpret_cast<const uint32_t*>(&s_p[r][8 * q]);
-            const uint32_t a = p[0], b = p[1], c = p[2];
+            // clamped positions are never consumed by an in-image output (they lie beyond the parent's 2-px reach)
+            const int yy = min(max(py0 + r, ymin), ymax);
+            const uint8_t* prow = P.img + (ptrdiff_t)yy * P.pitch;
+            const uint32_t a = *reinterpret_cast<const uint32_t*>(prow + min(px0 + 8 * q, xmax));
+            const uint32_t b = *reinterpret_cast<const uint32_t*>(prow + min(px0 + 8 * q + 4, xmax));
+            const uint32_t c = *reinterpret_cast<const uint32_t*>(prow + min(px0 + 8 * q + 8, xmax));
             int v[11];
             v[0] = a & 0xff; v[1] = (a >> 8) & 0xff; v[2] = (a >> 16) & 0xff; v[3] = a >> 24;
             v[4] = b & 0xff; v[5] = (b >> 8) & 0xff; v[6] = (b >> 16) & 0xff; v[7] = b >> 24;
@@ -210,21 +208,34 @@ __global__ __launch_bounds__(256) void level_kernel(const LevelSource in, const 
         rows[k][2] = p[2];
     }
     const uint32_t centre = rows[1][1];                  // pixels x .. x + 3
-    int t0[6], t1[6];
+    // Scharr on pairs of columns in packed 16-bit lanes: every intermediate fits 16 bits ((a + b) * 3 + c * 10 <= 4080, the
+    // differences +-4080) and only the low 16 bits of dx and dy are stored, so wrapping 16-bit arithmetic gives the same bits as
+    // the 32-bit form at half the instructions.  pr[k][j]: columns x - 1 + 2j, x + 2j of row k (bytes 3 + 2j, 4 + 2j of the 12).
+    typedef uint16_t u16x2 __attribute__((ext_vector_type(2)));
+    u16x2 pr[3][3];
 #pragma unroll
-    for (int i = 0; i < 6; i++) {
-        // byte (3 + i) of the 12-byte row
-        const int sh = 8 * ((3 + i) & 3), wd = (3 + i) >> 2;
-        const int a = (rows[0][wd] >> sh) & 0xff, c = (rows[1][wd] >> sh) & 0xff, b = (rows[2][wd] >> sh) & 0xff;
-        t0[i] = (a + b) * 3 + c * 10;
-        t1[i] = b - a;
+    for (int k = 0; k < 3; k++) {
+        pr[k][0] = __builtin_bit_cast(u16x2, __builtin_amdgcn_perm(rows[k][1], rows[k][0], 0x0c040c03u));
+        pr[k][1] = __builtin_bit_cast(u16x2, __builtin_amdgcn_perm(0u, rows[k][1], 0x0c020c01u));
+        pr[k][2] = __builtin_bit_cast(u16x2, __builtin_amdgcn_perm(rows[k][2], rows[k][1], 0x0c040c03u));
+    }
+    const u16x2 k3 = {3, 3}, k10 = {10, 10};
+    u16x2 t0[3], t1[3];                                  // columns x - 1 + 2j, x + 2j: (a + b) * 3 + c * 10 and b - a
+#pragma unroll
+    for (int j = 0; j < 3; j++) {
+        t0[j] = (pr[0][j] + pr[2][j]) * k3 + pr[1][j] * k10;
+        t1[j] = pr[2][j] - pr[0][j];
     }
     int32_t d[4];
 #pragma unroll
-    for (int i = 0; i < 4; i++) {
-        const int dx = t0[i + 2] - t0[i];
-        const int dy = (t1[i + 2] + t1[i]) * 3 + t1[i + 1] * 10;
-        d[i] = (int32_t)((uint32_t)(dx & 0xffff) | ((uint32_t)(dy & 0xffff) << 16));
+    for (int j = 0; j < 2; j++) {
+        // pixels x + 2j, x + 2j + 1: dx = t0[i + 2] - t0[i], dy = (t1[i + 2] + t1[i]) * 3 + t1[i + 1] * 10
+        const u16x2 dx = t0[j + 1] - t0[j];
+        const u16x2 mid = __builtin_bit_cast(u16x2, __builtin_amdgcn_alignbit(__builtin_bit_cast(uint32_t, t1[j + 1]), __builtin_bit_cast(uint32_t, t1[j]), 16u));
+        const u16x2 dy = (t1[j + 1] + t1[j]) * k3 + mid * k10;
+        const uint32_t dxu = __builtin_bit_cast(uint32_t, dx), dyu = __builtin_bit_cast(uint32_t, dy);
+        d[2 * j] = (int32_t)__builtin_amdgcn_perm(dyu, dxu, 0x05040100u);       // dx | dy << 16 of the even pixel
+        d[2 * j + 1] = (int32_t)__builtin_amdgcn_perm(dyu, dxu, 0x07060302u);   // ... of the odd one
     }
     const uint32_t w16lo = __builtin_amdgcn_perm(0u, centre, 0x0c010c00u) << 7;   // (p0, p1) << 7 as 16-bit lanes
     const uint32_t w16hi = __builtin_amdgcn_perm(0u, centre, 0x0c030c02u) << 7;
