@@ -311,6 +311,24 @@ int pc_host_buffer_alloc(size_t bytes, void** out);
 void pc_host_buffer_free(void* buffer);
 /* Same, from an 8-bit gray image (tests / callers that already hold gray). */
 int pc_frame_set_gray(pc_context* ctx, pc_frame* f, const uint8_t* gray, size_t row_pitch, int on_device);
+/* Same, from pixels of any type the library takes: H rows of W * channels channels of `pixel_type`, row_pitch_bytes apart (the
+ * last row need not have a full pitch).  Every channel becomes a byte on the GPU, by the rule of its type, and the frame is from
+ * then on what the byte frame would be (gray conversion by the context's weights, planes of 8 bits):
+ *   PC_PIXEL_U8   channels 1 (gray), 3 (RGB) or 4 (RGBA, alpha ignored): the byte itself.  1 and 3 are pc_frame_set_gray and
+ *                 pc_frame_set_rgb, bit for bit.
+ *   PC_PIXEL_U16  channels 3 or 4 (alpha ignored): b = (v * 255 + 32895) >> 16 in 32-bit unsigned arithmetic, the integer nearest
+ *                 to v / 257 (there are no ties).  v = 257 k gives k: a uint8 clip expanded by x * 257 gives the uint8 clip's
+ *                 planes.  (NOT the top byte v >> 8, which differs on 16256 values.)  No transfer curve applies, as for uint8.
+ *   PC_PIXEL_F16  channels 3 or 4 (alpha ignored): IEEE binary16, widened exactly to binary32 (subnormals, +-0, +-inf kept, NaN
+ *                 to a NaN), then the float32 rule -- the `(x * 255).astype(uint8)` rule or, under a float transfer table of
+ *                 pc_context_set_gray_conversion, the table entry of the widened value.  A frame h gives the planes of the
+ *                 float32 frame h.astype(float32), bit for bit.
+ *   PC_PIXEL_F32  channels 3 or 4: pc_frame_set_rgb_f32, bit for bit.
+ * PC_E_INVALID, with the frame's planes left as they were: pixels or row_pitch_bytes not a multiple of the channel's size (2 for
+ * the 16-bit types, 4 for float32), row_pitch_bytes below a row's bytes, any other channel count, an unknown pixel type. */
+enum pc_pixel_type { PC_PIXEL_U8 = 0, PC_PIXEL_U16 = 1, PC_PIXEL_F16 = 2, PC_PIXEL_F32 = 3 };
+int pc_frame_set_pixels(pc_context* ctx, pc_frame* f, const void* pixels, size_t row_pitch_bytes, int pixel_type, int channels,
+                        int on_device);
 
 int pc_frame_num_levels(const pc_frame* f); /* = maxLevel returned by buildOpticalFlowPyramid + 1 */
 int pc_frame_level_size(const pc_frame* f, int level, int* width, int* height);
@@ -663,6 +681,11 @@ int pc_analyzer_put_frame(pc_analyzer* a, int32_t frame_id, const uint8_t* rgb, 
 /* pc_analyzer_put_frame for a float32 frame (see pc_frame_set_rgb_f32). */
 int pc_analyzer_put_frame_f32(pc_analyzer* a, int32_t frame_id, const float* rgb, size_t row_pitch, int channels,
                               int on_device, int will_detect);
+/* pc_analyzer_put_frame for pixels of any type the library takes: the pixel types, channel counts, per-channel rules (uint16:
+ * (v * 255 + 32895) >> 16; float16: widened exactly, then the float32 rule; a fourth channel is ignored) and refusals of
+ * pc_frame_set_pixels.  A refused call leaves the ring as it was. */
+int pc_analyzer_put_frame_pixels(pc_analyzer* a, int32_t frame_id, const void* pixels, size_t row_pitch_bytes, int pixel_type,
+                                 int channels, int on_device, int will_detect);
 int pc_analyzer_has_frame(const pc_analyzer* a, int32_t frame_id);
 /* 1 when the pixels handed to pc_analyzer_put_frame for `frame_id` are no longer read (its gray conversion has
  * finished, or the frame has left the ring), 0 while the GPU may still read them.  Device / pinned sources are read

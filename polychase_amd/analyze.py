@@ -60,7 +60,7 @@ def analyze(width: int, height: int, first_frame: int, num_frames: int, frame_ac
             keypoints_per_frame: int | None = None, detection_mask=None):
     """Analyze frames first_frame .. first_frame + num_frames - 1 with all ranks of `group` (default: the world; one rank
     when torch.distributed is not initialised) and store the flow database at `database_path` (written by rank 0).
-    frame_accessor(frame_id) -> H x W x 3 uint8 (numpy, or a torch tensor on this rank's GPU), or float32 H x W x 3|4.
+    frame_accessor(frame_id) -> H x W x 3|4 uint8, uint16, float16 or float32 (numpy, or a torch tensor on this rank's GPU).
 
     Rank 0 runs its own shard straight into the database (the single-GPU path: inserts overlap the analysis); every other
     rank analyses its shard into a two-part device log and hands the log over in pieces of `piece_frames` frames, which
@@ -138,7 +138,7 @@ def _self_launch(n: int, argv) -> int:
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--synthetic", choices=["c1", "c2", "c3"], help="synthetic clip of that configuration (BASELINE.md section 4)")
-    ap.add_argument("--npy", help=".npy file of RGB frames, shape (N, H, W, 3) uint8")
+    ap.add_argument("--npy", help=".npy file of RGB(A) frames, shape (N, H, W, 3|4), uint8, uint16, float16 or float32 (converted on the GPU)")
     ap.add_argument("--frames", type=int, default=64)
     ap.add_argument("--first-frame", type=int, default=1)
     ap.add_argument("--max-level", type=int, default=None)
@@ -200,6 +200,8 @@ def main(argv=None) -> int:
     fopt = core.OpticalFlowOptions()
     if args.npy:
         stack = np.load(args.npy, mmap_mode="r")
+        if stack.ndim != 4 or stack.shape[3] not in (3, 4) or str(stack.dtype) not in ("uint8", "uint16", "float16", "float32"):
+            raise SystemExit(f"--npy: a stack must be (N, H, W, 3|4) uint8, uint16, float16 or float32, got {stack.dtype} {stack.shape}")
         n, h, w, _ = stack.shape
         n = min(n, args.frames)
         accessor = lambda fid: np.ascontiguousarray(stack[fid - args.first_frame])

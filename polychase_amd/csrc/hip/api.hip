@@ -999,16 +999,33 @@ int pc_api::fill_mask_polygons(pc_frame* f, const int32_t* d_poly, int n_vertice
     return PC_OK;
 }
 
-// channels: 1 / 3 = u8 gray / RGB; elem_size 4 = float32 RGB(A) with `channels` floats per pixel
 int pc_api::detect_counter_words(const DetectScratch& d) { return d.counter_words; }
 
+// the legal (pixel type, channels) pairs and the alignment each type needs; the float32 refusals keep the words they had
+int pc_api::check_pixels(const void* src, size_t row_pitch, int pixel_type, int channels) {
+    if (pixel_type < PC_PIXEL_U8 || pixel_type > PC_PIXEL_F32) return fail(PC_E_INVALID, "unknown pixel type %d", pixel_type);
+    if (pixel_type == PC_PIXEL_F32) {
+        if (channels != 3 && channels != 4) return fail(PC_E_INVALID, "float frames need 3 or 4 channels, got %d", channels);
+        if ((reinterpret_cast<uintptr_t>(src) | row_pitch) & 3) return fail(PC_E_INVALID, "float frame is not 4-byte aligned");
+    } else if (pixel_type == PC_PIXEL_U8) {
+        if (channels != 1 && channels != 3 && channels != 4) return fail(PC_E_INVALID, "uint8 frames need 1, 3 or 4 channels, got %d", channels);
+    } else {
+        if (channels != 3 && channels != 4) return fail(PC_E_INVALID, "16-bit frames need 3 or 4 channels, got %d", channels);
+        if ((reinterpret_cast<uintptr_t>(src) | row_pitch) & 1) return fail(PC_E_INVALID, "16-bit frame is not 2-byte aligned");
+    }
+    return PC_OK;
+}
+
+// pixel_type / channels: a pair check_pixels accepts
 int pc_api::set_image(pc_context* ctx, pc_frame* f, const uint8_t* src, size_t row_pitch, int on_device, int channels,
-                      int elem_size, uint32_t* clear, int clear_words) {
+                      int pixel_type, uint32_t* clear, int clear_words) {
     if (!ctx || !f || !src) return fail(PC_E_INVALID, "null argument");
     if (f->ctx != ctx) return fail(PC_E_INVALID, "frame belongs to another context");
-    if (elem_size == 4 && channels != 3 && channels != 4) return fail(PC_E_INVALID, "float frames need 3 or 4 channels, got %d", channels);
-    if (elem_size == 4 && ((reinterpret_cast<uintptr_t>(src) | row_pitch) & 3)) return fail(PC_E_INVALID, "float frame is not 4-byte aligned");
-    const size_t row_bytes = (size_t)f->w * channels * elem_size;
+    if (int crc = check_pixels(src, row_pitch, pixel_type, channels)) return crc;
+    const bool f32 = pixel_type == PC_PIXEL_F32;
+    // u8 RGBA and the 16-bit types: the kernels of pc_frame_set_pixels
+    const bool wide = pixel_type == PC_PIXEL_U16 || pixel_type == PC_PIXEL_F16 || (pixel_type == PC_PIXEL_U8 && channels == 4);
+    const size_t row_bytes = (size_t)f->w * channels * pc::pixel_type_bytes(pixel_type);
     if (row_pitch < row_bytes) return fail(PC_E_INVALID, "row_pitch %zu < %zu", row_pitch, row_bytes);
     // a lens map is made for one frame size (before anything is enqueued: the frame keeps its planes)
     const bool lens = ctx->lens_w > 0;
@@ -1063,10 +1080,13 @@ int pc_api::set_image(pc_context* ctx, pc_frame* f, const uint8_t* src, size_t r
     auto gray_into = [&](const pc::Level& l0) {
         ScopedTimer t(ctx, PC_K_GRAY);
         const bool dw = ctx->gray_default_weights();
-        if (elem_size == 4 && (ctx->gray_table_on || !dw))
+        if (wide)
+            pc::launch_pixels_to_gray(pixel_type, d_src, d_pitch, channels, l0, ctx->gray_w, pixel_type == PC_PIXEL_F16 ? ctx->gray_table_dev() : nullptr,
+                                      ctx->work);
+        else if (f32 && (ctx->gray_table_on || !dw))
             pc::launch_rgbf32_to_gray_converted(reinterpret_cast<const float*>(d_src), d_pitch, channels, l0, ctx->gray_w, ctx->gray_table_dev(),
                                                 ctx->work);
-        else if (elem_size == 4) pc::launch_rgbf32_to_gray(reinterpret_cast<const float*>(d_src), d_pitch, channels, l0, ctx->work);
+        else if (f32) pc::launch_rgbf32_to_gray(reinterpret_cast<const float*>(d_src), d_pitch, channels, l0, ctx->work);
         else if (channels == 3 && !dw) pc::launch_rgb2gray_weighted(d_src, d_pitch, l0, ctx->gray_w, ctx->work);
         else if (channels == 3) pc::launch_rgb2gray(d_src, d_pitch, l0, ctx->work);
         else pc::launch_copy_gray(d_src, d_pitch, l0, ctx->work);
@@ -1111,7 +1131,10 @@ int pc_api::set_image(pc_context* ctx, pc_frame* f, const uint8_t* src, size_t r
         pc::LevelSource in{};
         // the default gray conversion: the instances (and the launch arguments they read) of a context that never set one
         const bool dw = ctx->gray_default_weights();
-        if (elem_size == 4) in.kind = ctx->gray_table_on ? pc::SRC_RGBF32_T : (dw ? pc::SRC_RGBF32 : pc::SRC_RGBF32_W);
+        if (pixel_type == PC_PIXEL_U16) in.kind = pc::SRC_RGB16_W;
+        else if (pixel_type == PC_PIXEL_F16) in.kind = ctx->gray_table_on ? pc::SRC_RGBF16_T : pc::SRC_RGBF16_W;
+        else if (wide) in.kind = pc::SRC_RGBA8_W;
+        else if (f32) in.kind = ctx->gray_table_on ? pc::SRC_RGBF32_T : (dw ? pc::SRC_RGBF32 : pc::SRC_RGBF32_W);
         else in.kind = channels == 3 ? (dw ? pc::SRC_RGB8 : pc::SRC_RGB8_W) : pc::SRC_GRAY8;
         in.wr = (uint32_t)ctx->gray_w[0];
         in.wg = (uint32_t)ctx->gray_w[1];
@@ -1159,10 +1182,14 @@ int pc_frame_set_rgb(pc_context* ctx, pc_frame* f, const uint8_t* rgb, size_t ro
     return set_image(ctx, f, rgb, row_pitch, on_device, 3);
 }
 int pc_frame_set_rgb_f32(pc_context* ctx, pc_frame* f, const float* rgb, size_t row_pitch, int channels, int on_device) {
-    return set_image(ctx, f, reinterpret_cast<const uint8_t*>(rgb), row_pitch, on_device, channels, 4);
+    return set_image(ctx, f, reinterpret_cast<const uint8_t*>(rgb), row_pitch, on_device, channels, PC_PIXEL_F32);
 }
 int pc_frame_set_gray(pc_context* ctx, pc_frame* f, const uint8_t* gray, size_t row_pitch, int on_device) {
     return set_image(ctx, f, gray, row_pitch, on_device, 1);
+}
+
+int pc_frame_set_pixels(pc_context* ctx, pc_frame* f, const void* pixels, size_t row_pitch_bytes, int pixel_type, int channels, int on_device) {
+    return set_image(ctx, f, static_cast<const uint8_t*>(pixels), row_pitch_bytes, on_device, channels, pixel_type);
 }
 
 int pc_frame_set_mask(pc_context* ctx, pc_frame* f, const uint8_t* mask, size_t row_pitch, int on_device) {

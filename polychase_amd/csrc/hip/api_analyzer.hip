@@ -310,7 +310,7 @@ int pc_analyzer_reset(pc_analyzer* a) {
 }
 
 static int analyzer_put(pc_analyzer* a, int32_t frame_id, const uint8_t* rgb, size_t row_pitch, int on_device,
-                        int will_detect, int channels, int elem_size) {
+                        int will_detect, int channels, int pixel_type) {
     if (!a || !rgb) return fail(PC_E_INVALID, "null argument");
     const int n = (int)a->slots.size();
     Slot& s = a->slots[(size_t)(((frame_id % n) + n) % n)];
@@ -327,7 +327,7 @@ static int analyzer_put(pc_analyzer* a, int32_t frame_id, const uint8_t* rgb, si
     }
     // (the detection of a frame that was never submitted as frame1 is in front of this on prep_stream)
     // the detection that follows expects its counters zeroed: the frame's first kernel does it on the way
-    int rc = set_image(a->ctx, s.frame, rgb, row_pitch, on_device, channels, elem_size, will_detect ? s.scratch.counters.p : nullptr,
+    int rc = set_image(a->ctx, s.frame, rgb, row_pitch, on_device, channels, pixel_type, will_detect ? s.scratch.counters.p : nullptr,
                        detect_counter_words(s.scratch));
     s.scratch.cleared = rc == PC_OK && will_detect;
     if (rc != PC_OK) {
@@ -382,12 +382,22 @@ static int analyzer_put(pc_analyzer* a, int32_t frame_id, const uint8_t* rgb, si
 
 int pc_analyzer_put_frame(pc_analyzer* a, int32_t frame_id, const uint8_t* rgb, size_t row_pitch, int on_device,
                           int will_detect) {
-    return analyzer_put(a, frame_id, rgb, row_pitch, on_device, will_detect, 3, 1);
+    return analyzer_put(a, frame_id, rgb, row_pitch, on_device, will_detect, 3, PC_PIXEL_U8);
 }
 
 int pc_analyzer_put_frame_f32(pc_analyzer* a, int32_t frame_id, const float* rgb, size_t row_pitch, int channels,
                               int on_device, int will_detect) {
-    return analyzer_put(a, frame_id, reinterpret_cast<const uint8_t*>(rgb), row_pitch, on_device, will_detect, channels, 4);
+    return analyzer_put(a, frame_id, reinterpret_cast<const uint8_t*>(rgb), row_pitch, on_device, will_detect, channels, PC_PIXEL_F32);
+}
+
+int pc_analyzer_put_frame_pixels(pc_analyzer* a, int32_t frame_id, const void* pixels, size_t row_pitch_bytes, int pixel_type, int channels,
+                                 int on_device, int will_detect) {
+    if (!a || !pixels) return fail(PC_E_INVALID, "null argument");
+    // refused before the slot is touched: the ring stays as it was
+    if (int crc = check_pixels(pixels, row_pitch_bytes, pixel_type, channels)) return crc;
+    const size_t row_bytes = (size_t)a->w * channels * pc::pixel_type_bytes(pixel_type);
+    if (row_pitch_bytes < row_bytes) return fail(PC_E_INVALID, "row_pitch %zu < %zu", row_pitch_bytes, row_bytes);
+    return analyzer_put(a, frame_id, static_cast<const uint8_t*>(pixels), row_pitch_bytes, on_device, will_detect, channels, pixel_type);
 }
 
 int pc_analyzer_has_frame(const pc_analyzer* a, int32_t frame_id) {

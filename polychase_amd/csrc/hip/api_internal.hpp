@@ -125,9 +125,12 @@ int ensure_choked_plane(pc_frame* f);
 int alloc_window_weights(pc_frame* f, hipStream_t s);
 int make_window_weights(pc_frame* f, hipStream_t s);
 int ensure_window_weights(pc_frame* f, hipStream_t s);
-// gray (+ pyramid) of a frame from u8 gray / u8 RGB / float32 RGB(A) pixels, host or device, on the work stream
+// gray (+ pyramid) of a frame from pixels of `pixel_type` (pc_pixel_type) with `channels` channels, host or device, on the work
+// stream; the legal pairs are those of pc_frame_set_pixels, which check_pixels tests together with the alignment of pointer
+// and pitch (PC_OK, or PC_E_INVALID with the error set; nothing is enqueued)
 // `clear` (may be null): clear_words words zeroed in front of the frame's kernels (by the level-0 kernel where there is one)
-int set_image(pc_context* ctx, pc_frame* f, const uint8_t* src, size_t row_pitch, int on_device, int channels, int elem_size = 1,
+int check_pixels(const void* src, size_t row_pitch, int pixel_type, int channels);
+int set_image(pc_context* ctx, pc_frame* f, const uint8_t* src, size_t row_pitch, int on_device, int channels, int pixel_type = PC_PIXEL_U8,
               uint32_t* clear = nullptr, int clear_words = 0);
 int detect_counter_words(const DetectScratch& d);   // words of DetectScratch::counters a detection expects zeroed
 // detection mask of a frame: ensure_mask_plane allocates pc_frame::d_mask (w * h bytes, once); upload_mask copies `mask`

@@ -3,6 +3,7 @@
 
 #include "bvh.hpp"
 #include "common.hpp"
+#include "pixel_rules.hpp"
 
 namespace pc {
 
@@ -23,6 +24,11 @@ constexpr int kTransferEntries = 20481;   // == PC_TRANSFER_ENTRIES: black + 20 
 void launch_rgb2gray_weighted(const uint8_t* rgb, size_t rgb_pitch, const Level& l0, const int w[3], hipStream_t s);
 void launch_rgbf32_to_gray_converted(const float* rgb, size_t rgb_pitch, int channels, const Level& l0, const int w[3], const uint8_t* table,
                                      hipStream_t s);
+// u8 RGBA, uint16 RGB(A) and float16 RGB(A) frames (pixel_rules.hpp: PixelType and the rule of each channel) -> gray u8 in the
+// level-0 interior, one pixel per lane; weights and table as above, the table for PIXEL_F16 only.  src and src_pitch: multiples
+// of the channel's size.  false: not a combination of pixel type and channel count these kernels are for
+bool launch_pixels_to_gray(int pixel_type, const uint8_t* src, size_t src_pitch, int channels, const Level& l0, const int w[3],
+                           const uint8_t* table, hipStream_t s);
 // gray u8 (arbitrary pitch) -> level-0 interior
 void launch_copy_gray(const uint8_t* gray, size_t gray_pitch, const Level& l0, hipStream_t s);
 // K7: pyrDown 5x5 (src interior -> dst interior)
@@ -48,13 +54,17 @@ void launch_lens_remap(const uint8_t* src, int src_pitch, int w, int h, const in
 // parent's padded plane otherwise) -> u8 plane + REFLECT_101 padding + uint16 plane + Scharr plane.
 // SRC_RGB8_W / SRC_RGBF32_W / SRC_RGBF32_T: the RGB sources under a gray conversion other than the default -- channel weights
 // LevelSource::wr, wg, wb; _T: float channels through LevelSource::table instead of the `(x * 255).astype(uint8)` rule
-enum LevelSourceKind { SRC_PYR = 0, SRC_RGB8 = 1, SRC_GRAY8 = 2, SRC_RGBF32 = 3, SRC_RGB8_W = 4, SRC_RGBF32_W = 5, SRC_RGBF32_T = 6 };
+// SRC_RGBA8_W (u8 RGBA), SRC_RGB16_W (uint16 RGB / RGBA), SRC_RGBF16_W / _T (float16 RGB / RGBA without / with the table): the
+// pixel types of pc_frame_set_pixels, each channel by its rule of pixel_rules.hpp; the weights always come from the launch's
+// arguments (the default's weights give the default's bits), `channels` says whether there is an alpha to skip
+enum LevelSourceKind { SRC_PYR = 0, SRC_RGB8 = 1, SRC_GRAY8 = 2, SRC_RGBF32 = 3, SRC_RGB8_W = 4, SRC_RGBF32_W = 5, SRC_RGBF32_T = 6,
+                       SRC_RGBA8_W = 7, SRC_RGB16_W = 8, SRC_RGBF16_W = 9, SRC_RGBF16_T = 10 };
 struct LevelSource {
     int kind;
-    const uint8_t* src;   // level 0: the frame on the device (u8 RGB, u8 gray or float32 RGB / RGBA)
+    const uint8_t* src;   // level 0: the frame on the device (u8 RGB / RGBA / gray, uint16, float16 or float32 RGB / RGBA)
     size_t src_pitch;     // bytes per frame row
-    int channels;         // floats per pixel (SRC_RGBF32)
-    int aligned;          // src and src_pitch are multiples of 4: the u8 sources are read as dwords
+    int channels;         // floats per pixel (SRC_RGBF32); 16-bit words per pixel (SRC_RGB16_W, SRC_RGBF16_*)
+    int aligned;          // src and src_pitch are multiples of 4: the u8 and 16-bit sources are read as dwords
     Level parent;         // SRC_PYR
     uint32_t* clear;      // clear_words words zeroed by the launch (the detection's counters: saves the fill command
     int clear_words;      // in front of the detection chain), or null

@@ -130,6 +130,47 @@ void launch_rgbf32_to_gray_converted(const float* rgb, size_t rgb_pitch, int cha
                            (uint32_t)w[0], (uint32_t)w[1], (uint32_t)w[2], table);
 }
 
+// u8 RGBA, uint16 and float16 RGB(A) (pc_frame_set_pixels; the channel rules of pixel_rules.hpp), one pixel per lane, the channels
+// as loads of their own size: such a frame is aligned to its channel's size and to nothing more.
+// KIND: 0 u8 RGBA, 1 uint16, 2 float16, 3 float16 through the transfer table
+template <int KIND>
+__global__ __launch_bounds__(256) void pixels_to_gray_kernel(const uint8_t* __restrict__ src, size_t src_pitch, int channels,
+                                                             uint8_t* __restrict__ dst, int dst_pitch, int w, int h, uint32_t wr, uint32_t wg,
+                                                             uint32_t wb, const uint8_t* __restrict__ table) {
+    const int x = blockIdx.x * blockDim.x + threadIdx.x;
+    const int y = blockIdx.y;
+    if (x >= w) return;
+    const uint8_t* row = src + (size_t)y * src_pitch;
+    uint32_t c[3];
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        if constexpr (KIND == 0) {
+            c[k] = row[(size_t)x * 4 + k];
+        } else {
+            const uint32_t v = reinterpret_cast<const uint16_t*>(row)[(size_t)x * channels + k];
+            if constexpr (KIND == 1) c[k] = u16_to_u8(v);
+            else if constexpr (KIND == 3) c[k] = table[transfer_index(f16_bits_to_f32_bits(v))];
+            else c[k] = f32_bits_to_u8(f16_bits_to_f32_bits(v));
+        }
+    }
+    dst[(size_t)y * dst_pitch + x] = (uint8_t)((c[0] * wr + c[1] * wg + c[2] * wb + (1u << 14)) >> 15);
+}
+
+bool launch_pixels_to_gray(int pixel_type, const uint8_t* src, size_t src_pitch, int channels, const Level& l0, const int w[3],
+                           const uint8_t* table, hipStream_t s) {
+    dim3 grid((l0.w + 255) / 256, l0.h);
+    const uint32_t wr = (uint32_t)w[0], wg = (uint32_t)w[1], wb = (uint32_t)w[2];
+#define PC_PIXELS_TO_GRAY(KIND) \
+    hipLaunchKernelGGL(pixels_to_gray_kernel<KIND>, grid, dim3(256), 0, s, src, src_pitch, channels, l0.img, l0.pitch, l0.w, l0.h, wr, wg, wb, table)
+    if (pixel_type == PIXEL_U8 && channels == 4) PC_PIXELS_TO_GRAY(0);
+    else if (pixel_type == PIXEL_U16 && (channels == 3 || channels == 4)) PC_PIXELS_TO_GRAY(1);
+    else if (pixel_type == PIXEL_F16 && (channels == 3 || channels == 4) && !table) PC_PIXELS_TO_GRAY(2);
+    else if (pixel_type == PIXEL_F16 && (channels == 3 || channels == 4)) PC_PIXELS_TO_GRAY(3);
+    else return false;
+#undef PC_PIXELS_TO_GRAY
+    return true;
+}
+
 __global__ __launch_bounds__(256) void copy_gray_kernel(const uint8_t* __restrict__ src, size_t src_pitch,
                                                         uint8_t* __restrict__ dst, int dst_pitch, int w, int h) {
     const int x = blockIdx.x * blockDim.x + threadIdx.x;

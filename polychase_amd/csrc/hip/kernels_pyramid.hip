@@ -3,7 +3,8 @@
 // Replaces, per level l of cv::buildOpticalFlowPyramid (reference cpp/opticalflow.cc:180-187) and the
 // cv::cvtColor(COLOR_RGB2GRAY) in front of it (cpp/opticalflow.cc:259,:298):
 //     level 0:  RGB / gray / float RGB(A) frame  -> gray tile                      (RGB2Gray, 15-bit coefficients; or the
-//               context's gray conversion: channel weights, a transfer table for float channels)
+//               context's gray conversion: channel weights, a transfer table for float channels; or a u8 RGBA, uint16 or
+//               float16 RGB(A) frame, each channel made a byte by its rule of pixel_rules.hpp)
 //     level l:  parent level's padded plane      -> pyrDown tile (5x5, (sum + 128) >> 8, REFLECT_101)
 //   and then, from that tile in LDS (64 x 16 pixels + a 1-px halo), in the same kernel:
 //     the u8 image plane, its REFLECT_101 padding of `win` pixels (copyMakeBorder), the uint16 (pixel << 7) plane
@@ -45,8 +46,36 @@ __device__ __forceinline__ uint32_t float_channel_to_u8(float v) {
 // workgroup of the launch shares: it stays in the L1 / L2; DESIGN.md section 4, "Grey conversion")
 template <int SRC>
 __device__ __forceinline__ uint32_t gray_src(const LevelSource& in, uint32_t r, uint32_t g, uint32_t b) {
-    if constexpr (SRC == SRC_RGB8_W || SRC == SRC_RGBF32_W || SRC == SRC_RGBF32_T) return (r * in.wr + g * in.wg + b * in.wb + (1u << 14)) >> 15;
+    if constexpr (SRC == SRC_RGB8_W || SRC == SRC_RGBF32_W || SRC == SRC_RGBF32_T || SRC >= SRC_RGBA8_W)
+        return (r * in.wr + g * in.wg + b * in.wb + (1u << 14)) >> 15;
     else return gray_of(r, g, b);
+}
+// the sources of 16-bit channels (pixel_rules.hpp): uint16, and float16 widened to the float32 it equals
+template <int SRC>
+constexpr bool kSrc16 = SRC == SRC_RGB16_W || SRC == SRC_RGBF16_W || SRC == SRC_RGBF16_T;
+template <int SRC>
+__device__ __forceinline__ uint32_t channel16(const LevelSource& in, uint32_t v) {
+    if constexpr (SRC == SRC_RGB16_W) return u16_to_u8(v);
+    else if constexpr (SRC == SRC_RGBF16_T) return in.table[transfer_index(f16_bits_to_f32_bits(v))];
+    else return f32_bits_to_u8(f16_bits_to_f32_bits(v));
+}
+// four pixels of C 16-bit channels each from the 2 C aligned dwords that hold them (x a multiple of 4)
+template <int SRC, int C>
+__device__ __forceinline__ void quad16(const LevelSource& in, const uint8_t* row, int x, uint32_t px[4]) {
+    const uint32_t* s = reinterpret_cast<const uint32_t*>(row) + 2 * C * (x >> 2);
+    uint32_t d[2 * C];
+#pragma unroll
+    for (int k = 0; k < 2 * C; k++) d[k] = s[k];
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        uint32_t c[3];
+#pragma unroll
+        for (int j = 0; j < 3; j++) {
+            const int i = k * C + j;
+            c[j] = channel16<SRC>(in, (i & 1) ? d[i >> 1] >> 16 : d[i >> 1] & 0xffffu);
+        }
+        px[k] = gray_src<SRC>(in, c[0], c[1], c[2]);
+    }
 }
 template <int SRC>
 __device__ __forceinline__ uint32_t float_channel(const LevelSource& in, const float* s) {
@@ -62,6 +91,13 @@ __device__ __forceinline__ uint32_t source_gray(const LevelSource& in, int x, in
         return gray_src<SRC>(in, s[0], s[1], s[2]);
     } else if (SRC == SRC_GRAY8) {
         return row[x];
+    } else if (SRC == SRC_RGBA8_W) {
+        const uint8_t* s = row + 4 * (size_t)x;
+        return gray_src<SRC>(in, s[0], s[1], s[2]);
+    } else if (kSrc16<SRC>) {
+        // 16-bit loads: such a frame is 2-byte aligned, whatever else
+        const uint16_t* s = reinterpret_cast<const uint16_t*>(row) + (size_t)x * in.channels;
+        return gray_src<SRC>(in, channel16<SRC>(in, s[0]), channel16<SRC>(in, s[1]), channel16<SRC>(in, s[2]));
     } else {
         const float* s = reinterpret_cast<const float*>(row) + (size_t)x * in.channels;
         return gray_src<SRC>(in, float_channel<SRC>(in, s), float_channel<SRC>(in, s + 1), float_channel<SRC>(in, s + 2));
@@ -151,6 +187,16 @@ __global__ __launch_bounds__(256) void level_kernel(const LevelSource in, const 
                 } else if (SRC == SRC_GRAY8) {
                     const uint32_t d = *reinterpret_cast<const uint32_t*>(row + x);
                     px[0] = d & 0xff; px[1] = (d >> 8) & 0xff; px[2] = (d >> 16) & 0xff; px[3] = d >> 24;
+                } else if (SRC == SRC_RGBA8_W) {
+                    const uint32_t* s = reinterpret_cast<const uint32_t*>(row) + x;
+#pragma unroll
+                    for (int k = 0; k < 4; k++) {
+                        const uint32_t d = s[k];
+                        px[k] = gray_src<SRC>(in, d & 0xff, (d >> 8) & 0xff, (d >> 16) & 0xff);
+                    }
+                } else if (kSrc16<SRC>) {
+                    if (in.channels == 4) quad16<SRC, 4>(in, row, x, px);
+                    else quad16<SRC, 3>(in, row, x, px);
                 } else {
 #pragma unroll
                     for (int k = 0; k < 4; k++) px[k] = source_gray<SRC>(in, x + k, y);
@@ -285,6 +331,10 @@ void launch_level(const LevelSource& in, const Level& out, int win, hipStream_t 
         case SRC_RGB8_W: hipLaunchKernelGGL(level_kernel<SRC_RGB8_W>, grid, dim3(256), 0, s, in, out, win, helper_prio_arg()); break;
         case SRC_RGBF32_W: hipLaunchKernelGGL(level_kernel<SRC_RGBF32_W>, grid, dim3(256), 0, s, in, out, win, helper_prio_arg()); break;
         case SRC_RGBF32_T: hipLaunchKernelGGL(level_kernel<SRC_RGBF32_T>, grid, dim3(256), 0, s, in, out, win, helper_prio_arg()); break;
+        case SRC_RGBA8_W: hipLaunchKernelGGL(level_kernel<SRC_RGBA8_W>, grid, dim3(256), 0, s, in, out, win, helper_prio_arg()); break;
+        case SRC_RGB16_W: hipLaunchKernelGGL(level_kernel<SRC_RGB16_W>, grid, dim3(256), 0, s, in, out, win, helper_prio_arg()); break;
+        case SRC_RGBF16_W: hipLaunchKernelGGL(level_kernel<SRC_RGBF16_W>, grid, dim3(256), 0, s, in, out, win, helper_prio_arg()); break;
+        case SRC_RGBF16_T: hipLaunchKernelGGL(level_kernel<SRC_RGBF16_T>, grid, dim3(256), 0, s, in, out, win, helper_prio_arg()); break;
         default: hipLaunchKernelGGL(level_kernel<SRC_RGBF32>, grid, dim3(256), 0, s, in, out, win, helper_prio_arg()); break;
     }
 }

@@ -162,6 +162,10 @@ struct FrameView {
     int channels = 0;
     int elem_size = 1;     // 1: uint8 (channels == 3); 4: float32 as Blender hands frames out (channels 3 or 4),
                            // converted on the GPU like the addon's `(image * 255).astype(np.uint8)`
+    int pixel_type = -1;   // pc_pixel_type; -1: what elem_size says (uint8 or float32).  uint16 and float16 frames (elem_size 2,
+                           // channels 3 or 4) and uint8 frames with 4 channels are converted on the GPU by the rules of
+                           // pc_frame_set_pixels
+    int PixelType() const { return pixel_type >= 0 ? pixel_type : (elem_size == 4 ? 3 : 0); }
     size_t row_pitch = 0;  // bytes between rows
     bool on_device = false;
     bool pinned_host = false;   // with on_device: `data` is page-locked host memory (frame_pool.h) -> PC_FRAME_PINNED_HOST

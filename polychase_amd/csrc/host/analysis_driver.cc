@@ -28,6 +28,7 @@
 #include "device_plane_ring.h"
 #include "flow_database.h"
 #include "gpu_context.h"
+#include "pixel_convert.h"
 #include "utils.h"
 
 namespace {
@@ -641,8 +642,9 @@ static void RunAnalysis(const VideoInfo& video_info, FrameAccessorFunction frame
         if (f) {
             CHECK_EQ(static_cast<uint32_t>(f->rows), video_info.height);
             CHECK_EQ(static_cast<uint32_t>(f->cols), video_info.width);
-            if (f->elem_size == 4) CHECK(f->channels == 3 || f->channels == 4);
-            else CHECK_EQ(static_cast<uint32_t>(f->channels), 3u);
+            CHECK(f->PixelType() >= PC_PIXEL_U8 && f->PixelType() <= PC_PIXEL_F32);
+            CHECK_EQ(static_cast<size_t>(f->elem_size), PixelTypeBytes(f->PixelType()));
+            CHECK(f->channels == 3 || f->channels == 4);
         }
         return f;
     };
@@ -772,8 +774,12 @@ static void RunAnalysis(const VideoInfo& video_info, FrameAccessorFunction frame
             static const bool ingest_dma = !(std::getenv("POLYCHASE_INGEST_DMA") && std::atoi(std::getenv("POLYCHASE_INGEST_DMA")) == 0);
             const int where = !f->on_device ? 0 : (f->pinned_host && f->owner && ingest_dma ? PC_FRAME_PINNED_HOST : 1);
             StageClock put_clk(&local_stats.seconds_put);
+            const int ptype = f->PixelType();
+            // uint8 RGB and float32 through the calls they always took; the other types through the call that names the type
+            const bool by_type = ptype == PC_PIXEL_U16 || ptype == PC_PIXEL_F16 || (ptype == PC_PIXEL_U8 && f->channels == 4);
             const int put_rc =
-                f->elem_size == 4
+                by_type ? pc_analyzer_put_frame_pixels(eng.an, fid, f->data, f->row_pitch, ptype, f->channels, where, will_detect ? 1 : 0)
+                : f->elem_size == 4
                     ? pc_analyzer_put_frame_f32(eng.an, fid, reinterpret_cast<const float*>(f->data), f->row_pitch, f->channels,
                                                 where, will_detect ? 1 : 0)
                     : pc_analyzer_put_frame(eng.an, fid, f->data, f->row_pitch, where, will_detect ? 1 : 0);
@@ -792,11 +798,18 @@ static void RunAnalysis(const VideoInfo& video_info, FrameAccessorFunction frame
                 for (size_t y = 0; y < h; y++)
                     for (size_t x = 0; x < w; x++)
                         for (int c = 0; c < 3; c++) {
-                            if (f->elem_size == 4) {
-                                const float val = reinterpret_cast<const float*>(raw.data() + y * row)[x * f->channels + c] * 255.f;
+                            if (ptype == PC_PIXEL_F32 || ptype == PC_PIXEL_F16) {   // a half: widened, then as a float
+                                const uint32_t bits = FloatChannelBits(raw.data() + y * row, x * f->channels + c, ptype);
+                                float ch;
+                                std::memcpy(&ch, &bits, sizeof ch);
+                                const float val = ch * 255.f;
                                 img[(y * w + x) * 3 + c] = static_cast<uint8_t>(val < 0.f ? 0.f : (val > 255.f ? 255.f : val));
+                            } else if (ptype == PC_PIXEL_U16) {
+                                uint16_t v;
+                                std::memcpy(&v, raw.data() + y * row + 2 * (x * f->channels + c), sizeof v);
+                                img[(y * w + x) * 3 + c] = static_cast<uint8_t>(pc::u16_to_u8(v));
                             } else {
-                                img[(y * w + x) * 3 + c] = raw[y * row + x * 3 + c];
+                                img[(y * w + x) * 3 + c] = raw[y * row + x * f->channels + c];
                             }
                         }
             }

@@ -63,7 +63,7 @@ class OpticalFlowThread : public Worker<OpticalFlowThreadMessage> {
     // Deep copy on entry (cpp/opticalflow_thread.h:120-132): the caller's buffer is free on return.  The copy
     // lands in pinned memory, which the GPU reads directly (frame_pool.h).
     void ProvideFrame(int32_t frame_id, const uint8_t* data, int rows, int cols, int channels, size_t row_pitch,
-                      int elem_size = 1) {
+                      int elem_size = 1, int pixel_type = -1) {   // pixel_type: FrameView::pixel_type; elem_size its channel's bytes
         const size_t row_bytes = static_cast<size_t>(cols) * channels * elem_size;
         std::shared_ptr<void> pixels = AcquirePinnedFrameBuffer(static_cast<size_t>(rows) * row_bytes);
         uint8_t* dst = static_cast<uint8_t*>(pixels.get());
@@ -74,6 +74,7 @@ class OpticalFlowThread : public Worker<OpticalFlowThreadMessage> {
         view.cols = cols;
         view.channels = channels;
         view.elem_size = elem_size;
+        view.pixel_type = pixel_type;
         view.row_pitch = row_bytes;
         view.on_device = true;   // device-accessible (pinned) host memory
         view.pinned_host = true;

@@ -15,6 +15,7 @@
 #include "../host/flow_database.h"
 #include "../host/analysis.h"
 #include "../host/frame_pool.h"
+#include "../host/pixel_convert.h"
 #include "../host/analysis_thread.h"
 #include "../host/multi_gpu.h"
 #include "../host/stage_clock.h"
@@ -35,7 +36,34 @@ namespace {
 
 using U8Array = py::array_t<uint8_t, py::array::c_style>;
 
-// Python frame (numpy H x W x 3 uint8, or a torch CUDA tensor of that shape) -> FrameView.
+constexpr const char* kAcceptedFrames = "uint8 (H, W, 3|4), uint16 (H, W, 3|4), float16 (H, W, 3|4) or float32 (H, W, 3|4)";
+
+// dtype of a numpy frame -> pc_pixel_type, -1 for a dtype the library does not take (kind and size: 'e' is a kind 'f' of 2 bytes)
+int PixelTypeOfDtype(const py::dtype& dt) {
+    const char kind = dt.kind();
+    const py::ssize_t size = dt.itemsize();
+    if (kind == 'u' && size == 1) return PC_PIXEL_U8;
+    if (kind == 'u' && size == 2) return PC_PIXEL_U16;
+    if (kind == 'f' && size == 2) return PC_PIXEL_F16;
+    if (kind == 'f' && size == 4) return PC_PIXEL_F32;
+    return -1;
+}
+
+// a numpy frame of an accepted type, C-contiguous (copied if it is not) -> its pixel type; ValueError for anything else
+py::array AcceptedFrameArray(const py::object& obj, int* pixel_type) {
+    py::array arr = py::array::ensure(obj);
+    if (!arr) throw py::value_error(std::string("frame must be ") + kAcceptedFrames);
+    if (arr.dtype().kind() == 'b') arr = py::array_t<uint8_t>::ensure(arr);   // a bool array has always passed as bytes
+    *pixel_type = PixelTypeOfDtype(arr.dtype());
+    if (*pixel_type < 0 || arr.ndim() != 3 || (arr.shape(2) != 3 && arr.shape(2) != 4))
+        throw py::value_error(std::string("frame must be ") + kAcceptedFrames + ", got " + py::str(arr.dtype()).cast<std::string>() + " " +
+                              py::str(py::tuple(arr.attr("shape"))).cast<std::string>());
+    if (!(arr.flags() & py::array::c_style) || !arr.dtype().attr("isnative").cast<bool>())
+        arr = py::module_::import("numpy").attr("ascontiguousarray")(arr, arr.dtype().attr("newbyteorder")("="));
+    return arr;
+}
+
+// Python frame (numpy, or a torch CUDA tensor; the types of kAcceptedFrames) -> FrameView.
 // Host arrays are deep-copied under the GIL; device tensors are referenced (the caller keeps the
 // py::object alive, see GenerateOpticalFlowDatabasePy).
 std::optional<FrameView> FrameFromPython(const py::object& obj, std::deque<py::object>& keep_alive) {
@@ -46,11 +74,15 @@ std::optional<FrameView> FrameFromPython(const py::object& obj, std::deque<py::o
         // the analysis runs on its own HIP stream: wait for whatever produced the tensor
         py::module_::import("torch").attr("cuda").attr("current_stream")(t.attr("device")).attr("synchronize")();
         const auto shape = t.attr("shape").cast<std::vector<py::ssize_t>>();
-        if (shape.size() != 3) throw py::value_error("frame must have shape (H, W, 3)");
+        if (shape.size() != 3) throw py::value_error(std::string("frame must be ") + kAcceptedFrames);
         const std::string dtype = py::str(t.attr("dtype")).cast<std::string>();
-        if (dtype != "torch.uint8" && dtype != "torch.float32") throw py::value_error("frame must be uint8 or float32");
         FrameView v;
-        v.elem_size = dtype == "torch.float32" ? 4 : 1;
+        if (dtype == "torch.uint8") v.pixel_type = PC_PIXEL_U8;
+        else if (dtype == "torch.uint16") v.pixel_type = PC_PIXEL_U16;
+        else if (dtype == "torch.float16") v.pixel_type = PC_PIXEL_F16;
+        else if (dtype == "torch.float32") v.pixel_type = PC_PIXEL_F32;
+        else throw py::value_error(std::string("frame must be ") + kAcceptedFrames + ", got " + dtype);
+        v.elem_size = static_cast<int>(PixelTypeBytes(v.pixel_type));
         v.data = reinterpret_cast<const uint8_t*>(t.attr("data_ptr")().cast<uintptr_t>());
         v.rows = static_cast<int>(shape[0]);
         v.cols = static_cast<int>(shape[1]);
@@ -61,33 +93,15 @@ std::optional<FrameView> FrameFromPython(const py::object& obj, std::deque<py::o
         while (keep_alive.size() > 40) keep_alive.pop_front();
         return v;
     }
-    if (py::isinstance<py::array>(obj) && py::array(obj).dtype().is(py::dtype::of<float>())) {
-        // Blender's float pixels: converted on the GPU (no numpy `(x * 255).astype(uint8)` pass on the host)
-        F32Array fa = F32Array::ensure(obj);
-        if (!fa || fa.ndim() != 3) throw py::value_error("float frame must have shape (H, W, 3|4)");
-        std::shared_ptr<void> buf = AcquirePinnedFrameBuffer(static_cast<size_t>(fa.size()) * sizeof(float));
-        {
-            py::gil_scoped_release nogil;   // `fa` keeps the array alive
-            CopyFrameBytes(buf.get(), fa.data(), static_cast<size_t>(fa.size()) * sizeof(float));
-        }
-        FrameView v;
-        v.on_device = true;   // pinned host memory (frame_pool.h)
-        v.pinned_host = true;
-        v.data = static_cast<const uint8_t*>(buf.get());
-        v.rows = static_cast<int>(fa.shape(0));
-        v.cols = static_cast<int>(fa.shape(1));
-        v.channels = static_cast<int>(fa.shape(2));
-        v.elem_size = 4;
-        v.row_pitch = static_cast<size_t>(fa.shape(1) * fa.shape(2)) * sizeof(float);
-        v.owner = buf;
-        return v;
-    }
-    U8Array a = U8Array::ensure(obj);
-    if (!a || a.ndim() != 3) throw py::value_error("frame must be a uint8 array of shape (H, W, 3)");
-    std::shared_ptr<void> buf = AcquirePinnedFrameBuffer(static_cast<size_t>(a.size()));
+    // host pixels of every type are converted on the GPU (no numpy pass on the host: `(x * 255).astype(uint8)` of float frames,
+    // the widening of halves, the narrowing of 16-bit plates, the `[..., :3]` of RGBA bytes)
+    int pixel_type = -1;
+    const py::array a = AcceptedFrameArray(obj, &pixel_type);
+    const size_t bytes = static_cast<size_t>(a.size()) * PixelTypeBytes(pixel_type);
+    std::shared_ptr<void> buf = AcquirePinnedFrameBuffer(bytes);
     {
         py::gil_scoped_release nogil;   // `a` keeps the array alive
-        CopyFrameBytes(buf.get(), a.data(), static_cast<size_t>(a.size()));
+        CopyFrameBytes(buf.get(), a.data(), bytes);
     }
     FrameView v;
     v.on_device = true;   // pinned host memory (frame_pool.h)
@@ -96,9 +110,22 @@ std::optional<FrameView> FrameFromPython(const py::object& obj, std::deque<py::o
     v.rows = static_cast<int>(a.shape(0));
     v.cols = static_cast<int>(a.shape(1));
     v.channels = static_cast<int>(a.shape(2));
-    v.row_pitch = static_cast<size_t>(a.shape(1) * a.shape(2));
+    v.pixel_type = pixel_type;
+    v.elem_size = static_cast<int>(PixelTypeBytes(pixel_type));
+    v.row_pitch = static_cast<size_t>(a.shape(1) * a.shape(2)) * v.elem_size;
     v.owner = buf;
     return v;
+}
+
+// polychase_core.frame_channel_bytes: the (H, W, 3) bytes the default conversion makes of a frame's channels, on the host
+py::array_t<uint8_t> FrameChannelBytesPy(const py::object& frame) {
+    int pixel_type = -1;
+    const py::array a = AcceptedFrameArray(frame, &pixel_type);
+    py::array_t<uint8_t> out({a.shape(0), a.shape(1), static_cast<py::ssize_t>(3)});
+    FrameChannelBytes(static_cast<const uint8_t*>(a.data()), static_cast<int>(a.shape(0)), static_cast<int>(a.shape(1)),
+                      static_cast<int>(a.shape(2)), pixel_type, static_cast<size_t>(a.shape(1) * a.shape(2)) * PixelTypeBytes(pixel_type),
+                      out.mutable_data());
+    return out;
 }
 
 using I32Array = py::array_t<int32_t, py::array::c_style>;
@@ -728,18 +755,11 @@ PYBIND11_MODULE(polychase_core, m) {
         .def("try_pop", &OpticalFlowThread::TryPop)
         .def("empty", &OpticalFlowThread::Empty)
         .def("provide_frame", [](OpticalFlowThread& t, int32_t frame_id, const py::array& frame) {
-            if (frame.ndim() != 3) throw py::value_error("frame must be an array of shape (H, W, 3)");
-            if (frame.dtype().is(py::dtype::of<float>())) {   // Blender's float pixels, (H, W, 3|4)
-                const F32Array f = F32Array::ensure(frame);
-                t.ProvideFrame(frame_id, reinterpret_cast<const uint8_t*>(f.data()), static_cast<int>(f.shape(0)),
-                               static_cast<int>(f.shape(1)), static_cast<int>(f.shape(2)),
-                               static_cast<size_t>(f.shape(1) * f.shape(2)) * sizeof(float), 4);
-                return;
-            }
-            const U8Array u = U8Array::ensure(frame);
-            if (!u) throw py::value_error("frame must be a uint8 (H, W, 3) or float32 (H, W, 3|4) array");
-            t.ProvideFrame(frame_id, u.data(), static_cast<int>(u.shape(0)), static_cast<int>(u.shape(1)),
-                           static_cast<int>(u.shape(2)), static_cast<size_t>(u.shape(1) * u.shape(2)));
+            int pixel_type = -1;
+            const py::array a = AcceptedFrameArray(frame, &pixel_type);   // ValueError for any other dtype or shape
+            const int elem = static_cast<int>(PixelTypeBytes(pixel_type));
+            t.ProvideFrame(frame_id, static_cast<const uint8_t*>(a.data()), static_cast<int>(a.shape(0)), static_cast<int>(a.shape(1)),
+                           static_cast<int>(a.shape(2)), static_cast<size_t>(a.shape(1) * a.shape(2)) * elem, elem, pixel_type);
         });
 
     // not in the reference: the two halves of a multi-GPU analysis (polychase_amd/analyze.py launches them, one
@@ -755,6 +775,9 @@ PYBIND11_MODULE(polychase_core, m) {
         SaveImageForDebugging(img.data(), static_cast<int>(rgb.shape(1)), static_cast<int>(rgb.shape(0)), frame_id, dir, kps.data(),
                               static_cast<int>(kps.size() / 2));
     });
+    // not in the reference: what the default conversion makes of the channels of a frame of any accepted type, on the host by the
+    // rules the GPU applies (csrc/hip/pixel_rules.hpp) -- like float_transfer_table, the CPU-testable face of a device rule
+    m.def("frame_channel_bytes", &FrameChannelBytesPy, py::arg("frame"));
     m.def("_engine_cache_timer_running", &EngineCacheTimerRunning);   // testing aid
     // measurement aid (not in the reference): the stage totals of the last finished call of that kind -- "TrackCameraTrajectory",
     // "RefineTrajectory" -- as {label: (milliseconds or count, calls)} (csrc/host/stage_clock.h)

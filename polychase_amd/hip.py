@@ -31,7 +31,7 @@ SYMBOLS = [
     "pc_context_enable_timing", "pc_context_get_timing", "pc_context_get_busy_time", "pc_context_reset_timing",
     "pc_debug_lk_profile", "pc_debug_lk_x86_stats", "pc_debug_detection_paths", "pc_debug_llt9", "pc_debug_lm_decide",
     "pc_debug_live_resources",
-    "pc_frame_create", "pc_frame_destroy", "pc_frame_set_rgb", "pc_frame_set_rgb_f32", "pc_frame_set_gray",
+    "pc_frame_create", "pc_frame_destroy", "pc_frame_set_rgb", "pc_frame_set_rgb_f32", "pc_frame_set_gray", "pc_frame_set_pixels",
     "pc_host_buffer_alloc", "pc_host_buffer_free",
     "pc_frame_num_levels", "pc_frame_level_size", "pc_frame_download_gray", "pc_frame_download_level",
     "pc_frame_download_deriv", "pc_frame_download_level16", "pc_frame_detect", "pc_frame_download_min_eig", "pc_frame_num_candidates",
@@ -44,7 +44,7 @@ SYMBOLS = [
     "pc_lk_track_search", "pc_analyzer_set_search_radius",
     "pc_lk_track_window_masked", "pc_frame_download_window_weights", "pc_analyzer_set_mask_windows",
     "pc_lk_track", "pc_lk_track_filtered", "pc_lk_track_fb", "pc_lk_track_filtered_fb",
-    "pc_analyzer_create", "pc_analyzer_destroy", "pc_analyzer_reset", "pc_analyzer_put_frame", "pc_analyzer_put_frame_f32",
+    "pc_analyzer_create", "pc_analyzer_destroy", "pc_analyzer_reset", "pc_analyzer_put_frame", "pc_analyzer_put_frame_f32", "pc_analyzer_put_frame_pixels",
     "pc_analyzer_has_frame", "pc_analyzer_frame_ingested",
     "pc_analyzer_set_keypoints", "pc_analyzer_submit", "pc_analyzer_pending", "pc_analyzer_collect",
     "pc_analyzer_set_device_log", "pc_analyzer_device_log_used", "pc_analyzer_redirect_device_log",
@@ -205,6 +205,7 @@ def load():
     L.pc_frame_set_rgb.argtypes = [vp, vp, vp, C.c_size_t, C.c_int]
     L.pc_frame_set_gray.argtypes = [vp, vp, vp, C.c_size_t, C.c_int]
     L.pc_frame_set_rgb_f32.argtypes = [vp, vp, vp, C.c_size_t, C.c_int, C.c_int]
+    L.pc_frame_set_pixels.argtypes = [vp, vp, vp, C.c_size_t, C.c_int, C.c_int, C.c_int]
     L.pc_frame_num_levels.argtypes = [vp]
     L.pc_frame_level_size.argtypes = [vp, C.c_int, ip, ip]
     L.pc_frame_download_gray.argtypes = [vp, vp, vp]
@@ -243,6 +244,7 @@ def load():
     L.pc_analyzer_destroy.restype = None
     L.pc_analyzer_put_frame.argtypes = [vp, C.c_int32, vp, C.c_size_t, C.c_int, C.c_int]
     L.pc_analyzer_put_frame_f32.argtypes = [vp, C.c_int32, vp, C.c_size_t, C.c_int, C.c_int, C.c_int]
+    L.pc_analyzer_put_frame_pixels.argtypes = [vp, C.c_int32, vp, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int]
     L.pc_analyzer_has_frame.argtypes = [vp, C.c_int32]
     L.pc_analyzer_frame_ingested.argtypes = [vp, C.c_int32]
     L.pc_analyzer_set_keypoints.argtypes = [vp, C.c_int32, vp, C.c_int]
@@ -579,6 +581,32 @@ def _is_float32(a) -> bool:
     return str(a.dtype) in ("float32", "torch.float32")
 
 
+PIXEL_U8, PIXEL_U16, PIXEL_F16, PIXEL_F32 = 0, 1, 2, 3   # pc_pixel_type of include/polychase_hip.h
+_PIXEL_TYPES = {"uint8": PIXEL_U8, "uint16": PIXEL_U16, "float16": PIXEL_F16, "float32": PIXEL_F32}
+_PIXEL_CHANNELS = {PIXEL_U8: (1, 3, 4), PIXEL_U16: (3, 4), PIXEL_F16: (3, 4), PIXEL_F32: (3, 4)}
+ACCEPTED_FRAMES = "uint8 (H, W, 3|4), uint16 (H, W, 3|4), float16 (H, W, 3|4) or float32 (H, W, 3|4)"
+
+
+def pixel_type_of(a) -> int:
+    """the pc_pixel_type of a numpy array's or a torch tensor's dtype; ValueError for a dtype the library does not take"""
+    name = str(a.dtype).replace("torch.", "")
+    if name not in _PIXEL_TYPES:
+        raise ValueError(f"a frame must be {ACCEPTED_FRAMES}, got dtype {a.dtype}")
+    return _PIXEL_TYPES[name]
+
+
+def _pixels_args(img, w: int, h: int):
+    """frame of any accepted type -> (address, row_pitch_bytes, pixel_type, channels, on_device); uint8 (H, W) is a gray frame.
+    ValueError for any other dtype or shape."""
+    ptype = pixel_type_of(img)
+    shape = tuple(img.shape)
+    channels = 1 if len(shape) == 2 else (shape[2] if len(shape) == 3 else 0)
+    if shape[:2] != (h, w) or channels not in _PIXEL_CHANNELS[ptype]:
+        raise ValueError(f"a {w} x {h} frame must be {ACCEPTED_FRAMES}, got {img.dtype} {shape}")
+    p, dev, pitch = _ptr(img)
+    return p, pitch, ptype, int(channels), dev
+
+
 class Frame:
     """Gray image + LK pyramid + keypoints of one video frame, resident in HBM."""
 
@@ -608,6 +636,14 @@ class Frame:
             assert tuple(rgb.shape) == (self.h, self.w, 3), rgb.shape
             _check(load().pc_frame_set_rgb(self.ctx._h, self._h, p, pitch, dev))
         self._keep = rgb  # device sources must outlive the async kernels
+
+    def set_pixels(self, img):
+        """A frame of any type the library takes (pc_frame_set_pixels): uint8 (H, W, 3|4) or (H, W), uint16, float16 or float32
+        (H, W, 3|4); numpy, or a torch tensor on the host or the device.  Every channel becomes a byte on the GPU by the rule of
+        its type; the planes stay 8-bit."""
+        p, pitch, ptype, channels, dev = _pixels_args(img, self.w, self.h)
+        _check(load().pc_frame_set_pixels(self.ctx._h, self._h, p, pitch, ptype, channels, dev))
+        self._keep = img  # device sources must outlive the async kernels
 
     def set_gray(self, gray):
         assert tuple(gray.shape) == (self.h, self.w), gray.shape
@@ -887,6 +923,14 @@ class Analyzer:
             self._keep[frame_id % self.ring] = rgb  # device sources must outlive the async kernels
         # ... and so must the device mask this frame's detection copies: until the slot takes its next frame, whatever
         # set_mask is given in between
+        self._keep_masks[frame_id % self.ring] = self._keep_mask if will_detect or self._target_margin >= 0 else None
+
+    def put_frame_pixels(self, frame_id: int, img, will_detect: bool = True):
+        """put_frame for a frame of any type the library takes (pc_analyzer_put_frame_pixels; Frame.set_pixels has the list)"""
+        p, pitch, ptype, channels, dev = _pixels_args(img, self.w, self.h)
+        _check(load().pc_analyzer_put_frame_pixels(self._h, frame_id, p, pitch, ptype, channels, dev, 1 if will_detect else 0))
+        if dev:
+            self._keep[frame_id % self.ring] = img
         self._keep_masks[frame_id % self.ring] = self._keep_mask if will_detect or self._target_margin >= 0 else None
 
     def has_frame(self, frame_id: int) -> bool:

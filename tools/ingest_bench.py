@@ -1,10 +1,12 @@
 #!/usr/bin/env python3
 """Frame ingestion through polychase_core: host frames as uint8 RGB, as Blender's float32 RGBA and as
 scene-linear float32 RGB (the uint8 clip through the sRGB EOTF: what an EXR plate holds), or device-resident uint8 RGB
-(uint8_rgb_device: no transfer at all, the GPU side of ingestion alone), no database.
+(uint8_rgb_device: no transfer at all, the GPU side of ingestion alone), no database.  uint8_rgba (the same bytes with an alpha
+channel), uint16_rgb (x * 257) and float16_rgba (the float32 RGBA clip rounded to half) are the same pictures in the pixel types
+a decoder, a 16-bit plate and an EXR hand out: converted on the GPU like the others, so the clips differ in bytes moved only.
 `POLYCHASE_COPY_THREADS=1` gives the single-threaded copy for comparison.
 
-    python tools/ingest_bench.py [--config c2] [--frames 120] [--clips uint8_rgb,float32_rgba,float32_rgb_linear,uint8_rgb_device]
+    python tools/ingest_bench.py [--config c2] [--frames 120] [--clips uint8_rgb,float32_rgba,float32_rgb_linear,uint8_rgb_device,uint8_rgba,uint16_rgb,float16_rgba]
                                  [--channel-weights R G B] [--float-transfer none|srgb|gamma] [--float-gamma G] [--float-exposure STOPS]
                                  [--lens-k1 K]
 
@@ -23,7 +25,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "polychase_amd", "core"))
 
-CLIPS = ("uint8_rgb", "float32_rgba", "float32_rgb_linear", "uint8_rgb_device")
+CLIPS = ("uint8_rgb", "float32_rgba", "float32_rgb_linear", "uint8_rgb_device", "uint8_rgba", "uint16_rgb", "float16_rgba")
 
 
 def main():
@@ -51,6 +53,13 @@ def main():
     clips = {"uint8_rgb": u8}
     if "float32_rgba" in names:
         clips["float32_rgba"] = [np.concatenate([x.astype(np.float32) / 255.0, np.ones((h, w, 1), np.float32)], axis=2) for x in u8[:12]]
+    if "uint8_rgba" in names:
+        clips["uint8_rgba"] = [np.concatenate([x, np.full((h, w, 1), 255, np.uint8)], axis=2) for x in u8]
+    if "uint16_rgb" in names:
+        clips["uint16_rgb"] = [x.astype(np.uint16) * np.uint16(257) for x in u8[:12]]
+    if "float16_rgba" in names:
+        clips["float16_rgba"] = [np.concatenate([x.astype(np.float32) / 255.0, np.ones((h, w, 1), np.float32)], axis=2).astype(np.float16)
+                                 for x in u8[:12]]
     if "float32_rgb_linear" in names:
         c = np.arange(256) / 255.0
         eotf = np.where(c <= 0.04045, c / 12.92, ((c + 0.055) / 1.055) ** 2.4).astype(np.float32)
